@@ -1,8 +1,13 @@
 """bench.py — env-steps/sec of the batched CrowdSimDict hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--envs E] [--humans H] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--envs E] [--humans H] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does only what the headline figure needs: set-up, W warm-up launches, the K timed launches, the
+outputs of the last timed step to DIR/<name>.npy when --dump-outputs is given, and the JSON line. --full adds
+every other measurement to the same line: the steady_state window, the C3 / C5 / C4 side windows and the CPU
+baseline (each can still be left out with --no-steady / --no-side / --no-cpu-baseline).
 
 `python bench.py --gpus N` (N > 1) without WORLD_SIZE launches the N rank processes itself (a child
 torch.distributed.run on 127.0.0.1, before this process touches the GPU) and exits with its code -- the
@@ -19,7 +24,7 @@ Multi-GPU: envs shard with no collective (env g of rank r is global env r*E+g; t
 global) -> weak scaling; timing = max over ranks between barriers.
 One JSON line on rank 0 (bench contract in the task statement). The main window is the K launches after
 W warm-up launches after cn_reset (the driver's --steps 20 --warmup 5: launches 6-25 of the first
-episodes, few auto-resets); `steady_state` in the same line is SURVEY §8d's window on the same engine:
+episodes, few auto-resets); with --full, `steady_state` in the same line is SURVEY §8d's window on the same engine:
 100 more warm-up launches, then 2,000 timed ones including all their auto-resets (`resets` = episodes
 ended and restarted inside the window, counted from the engine's per-env reset counters).
 """
@@ -54,6 +59,30 @@ def algorithmic_bytes_per_env_step(N):
     """B_step(N) = 2*(S_r + N*S_h) + 8 (action) + 4*(9 + 2N) (obs) + 4 (reward) + 2 (done, event),
     S_r = 112 B, S_h = 96 B  ->  2,274 B at N = 10."""
     return 2 * (112 + 96 * N) + 8 + 4 * (9 + 2 * N) + 4 + 2
+
+
+DUMP_MAX_BYTES = 64 << 20   # --dump-outputs: all files of a run together stay below this
+
+
+def dump_outputs(dirname, arrays, rank=0, world=1):
+    """--dump-outputs: {name: array} -> dirname/<name>.npy (ranks past 0: <name>.rank<r>.npy), float64 arrays
+    as float64 and every other dtype as float32. An array over its share of DUMP_MAX_BYTES is cut to a fixed
+    sample of its flattened elements (indices drawn once from RandomState(0), sorted), the same in every run."""
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_MAX_BYTES // max(world, 1) // max(len(arrays), 1)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+        if a.nbytes > share:
+            idx = np.sort(np.random.RandomState(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.ravel()[idx]
+        np.save(os.path.join(dirname, name + (".rank%d" % rank if rank else "") + ".npy"), a)
+
+
+def engine_outputs(eng):
+    """Host copies of what step() / step_seq() returned last (the engine's own output buffers)."""
+    return {k: getattr(eng, k).cpu().numpy() for k in ("robot_node", "temporal_edges", "spatial_edges", "reward",
+                                                        "done", "event", "info", "ep_return", "ep_len")}
 
 
 DIAG = None   # --diag (counter attribution runs only, never the line of record): "nogoal" = no goal changing
@@ -301,7 +330,7 @@ def dsrnn_flop_per_env_step(N, c):
     return enc + (N + 1) * edge_gru + att + node + heads
 
 
-def run_c4(torch, dist, device, rank, world, E, N, K, W):
+def run_c4(torch, dist, device, rank, world, E, N, K, W, dump=None):
     """env-steps/s over PPO updates, counted like train.py:342-352 (rollout of num_steps
     steps of every env with DSRNN act() in the loop, then the PPO update, all inside the timed region).
     A "step" here is one update = 128 x E env steps per GPU; W untimed updates first (the first eager,
@@ -357,6 +386,11 @@ def run_c4(torch, dist, device, rank, world, E, N, K, W):
         dist.all_reduce(t[1:], op=dist.ReduceOp.SUM)
         elapsed, episodes = float(t[0].item()), int(t[1].item())
     timing, ops.FUSED_TIMING = ops.FUSED_TIMING, None
+    if dump and K > 0:   # what the last timed update returned and left behind: its losses and the policy
+        arrays = {k: np.float64(st[k]) for k in ("value_loss", "action_loss", "dist_entropy", "episodes",
+                                                 "mean_episode_return")}
+        arrays["policy_params"] = torch.cat([p.detach().reshape(-1) for p in pol.parameters()]).cpu().numpy()
+        dump_outputs(dump, arrays, rank, world)
     roof = gru_gemm_roofline(torch, device, E // c.ppo.num_mini_batch * N, 256) if rank == 0 else None
     if rank == 0 and timing:
         # the roofline of record: the same kernel timed IN the loop (all its launches of the timed updates)
@@ -497,7 +531,7 @@ def dry_run(args, world, rank):
         dist.destroy_process_group()
 
 
-def run_env(torch, dist, device, rank, world, workload, E, N, K, W, steady, rng="mt19937", launch="seq"):
+def run_env(torch, dist, device, rank, world, workload, E, N, K, W, steady, rng="mt19937", launch="seq", dump=None):
     """The env hot path alone (c2 / c3 / c5): W untimed launches after cn_reset, then K timed ones
     (barrier + synchronize on both sides, max over ranks); with `steady` also SURVEY §8d's window on the
     same engine (100 more warm-up launches, then 2,000 timed ones). launch = "seq" (default): each timed
@@ -614,6 +648,8 @@ def run_env(torch, dist, device, rank, world, workload, E, N, K, W, steady, rng=
            "launch": "hipGraph replay" if use_graph else ("cn_step_seq (native loop of cn_step launches)"
                                                           if launch == "seq" else "host-issued cn_step per step")}
     out["main"] = timed_window(acts, W, K)
+    if dump:   # the outputs of the window's last launch, before any later window overwrites the buffers
+        dump_outputs(dump, engine_outputs(eng), rank, world)
     out["done_frac"] = float(eng.done.float().mean().item())   # envs that ended an episode at the last step
     out["steady"] = None
     if steady:
@@ -651,7 +687,7 @@ def env_window_obj(m, world, which="main"):
             "roofline": roofline_obj(m["bpl"] / ks / 1e9, m["bpl"], pmc)}
 
 
-# SURVEY §8d side measurements carried by the default line (driver-observed C3 / C4 / C5):
+# SURVEY §8d side measurements carried by the --full line (driver-observed C3 / C4 / C5):
 # (workload, warm-up, timed steps); C4 counts PPO updates (the first warm-up update runs eagerly, the second
 # captures the rollout's HIP graph)
 SIDE_WINDOWS = (("c3", 100, 200), ("c5", 100, 200), ("c4", 2, 2))
@@ -661,13 +697,21 @@ SIDE_DEADLINE_S = 300.0
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=2000)
-    ap.add_argument("--warmup", type=int, default=100)
+    ap.add_argument("--steps", type=int, default=None,
+                    help="timed steps (default 2000; --workload c4: timed PPO updates, default 10)")
+    ap.add_argument("--warmup", type=int, default=None,
+                    help="untimed steps before them (default 100; --workload c4: updates, default 2)")
     ap.add_argument("--envs", type=int, default=4096, help="envs per GPU")
     ap.add_argument("--humans", type=int, default=10)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-steady", action="store_true", help="skip the steady_state window (100 + 2000 launches)")
-    ap.add_argument("--no-side", action="store_true", help="skip the C3 / C4 / C5 side windows of the c2 line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned to DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the steady_state window, the C3 / C4 / C5 side windows and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-steady", action="store_true",
+                    help="with --full: skip the steady_state window (100 + 2000 launches)")
+    ap.add_argument("--no-side", action="store_true",
+                    help="with --full: skip the C3 / C4 / C5 side windows of the c2 line")
     ap.add_argument("--cpu-budget", type=float, default=12.0)
     ap.add_argument("--launch", choices=["seq", "host", "graph"], default="seq",
                     help="timed env windows as one cn_step_seq call (default: K launches back to back from "
@@ -681,6 +725,10 @@ def main():
     ap.add_argument("--dry-run", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--diag", choices=["nogoal"], default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps is None:
+        args.steps = 10 if args.workload == "c4" else 2000
+    if args.warmup is None:
+        args.warmup = 2 if args.workload == "c4" else 100
     global DIAG
     DIAG = args.diag
 
@@ -717,7 +765,7 @@ def main():
 
     E, N, K, W = args.envs, args.humans, args.steps, args.warmup
     if args.workload == "c4":
-        line = run_c4(torch, dist, device, rank, world, E, N, K if K != 2000 else 10, W if W != 100 else 2)
+        line = run_c4(torch, dist, device, rank, world, E, N, K, W, args.dump_outputs)
         if rank == 0:
             print(json.dumps(line), flush=True)
         if dist is not None:
@@ -729,8 +777,9 @@ def main():
         E = 8192
     if args.workload == "c5":
         N = 5
-    steady = not args.no_steady and (K < 2000 or W < 100)
-    m = run_env(torch, dist, device, rank, world, args.workload, E, N, K, W, steady, args.rng, args.launch)
+    steady = args.full and not args.no_steady and (K < 2000 or W < 100)
+    m = run_env(torch, dist, device, rank, world, args.workload, E, N, K, W, steady, args.rng, args.launch,
+                args.dump_outputs)
     line = None
     if rank == 0:
         main_w = env_window_obj(m, world)
@@ -768,10 +817,10 @@ def main():
             st = env_window_obj(m, world, "steady")
             st["window"] += " (SURVEY 8d: 100 warm-up + 2000 timed, incl. auto-resets)"
             line["steady_state"] = st
-    if args.workload == "c2" and not args.no_side:
+    if args.full and args.workload == "c2" and not args.no_side:
         run_side_windows(torch, dist, device, rank, world, args.rng, line, args.launch)
     if rank == 0:
-        if not args.no_cpu_baseline and world == 1 and args.workload == "c2":
+        if args.full and not args.no_cpu_baseline and world == 1 and args.workload == "c2":
             line["cpu_baseline"] = cpu_baseline(N, args.cpu_budget)
         print(json.dumps(line), flush=True)
     if dist is not None:

@@ -1,7 +1,7 @@
 #!/bin/bash
 # rocprofv3 collection for a bench workload (run on the GPU box via gpurun from the repo root):
 #   bash profiles/run_profile.sh <tag> [bench.py args...]
-# Default args = the driver's own invocation (bench.py --gpus 1 --steps 20 --warmup 5), whose line carries
+# Default args = the driver's window with every other measurement (bench.py --gpus 1 --steps 20 --warmup 5 --full), whose line carries
 # the main window (launches 6-25 after cn_reset) and the steady_state window (launches 126-2125);
 # summarize.py splits every figure by those windows. The counter passes add --no-cpu-baseline (the CPU leg
 # runs after all GPU work and launches nothing), the kernel-trace pass runs the command unchanged.
@@ -17,7 +17,7 @@
 set -e
 TAG=${1:-r02}
 shift || true
-ARGS="${*:---gpus 1 --steps 20 --warmup 5}"
+ARGS="${*:---gpus 1 --steps 20 --warmup 5 --full}"
 PARGS="$ARGS --no-cpu-baseline"
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/prof_$TAG

@@ -6,6 +6,7 @@ import os
 import sys
 
 import numpy as np
+import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench  # noqa: E402
@@ -90,8 +91,78 @@ def test_window_object_arithmetic_and_fields():
     assert abs(r["achieved"] - 5274 * 4096 / 0.0005 / 1e9) < 1e-3 and r["peak"] == 8000.0
 
 
+def test_dump_outputs_dtypes_names_and_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: one <name>.npy per array, float64 kept and every other dtype as float32 with the same
+    values; an array over its share of the byte budget is cut to the same seeded sample in every run; ranks past
+    0 write <name>.rank<r>.npy."""
+    arrays = {"reward": np.arange(12, dtype=np.float32).reshape(3, 4) / 7, "done": np.array([0, 1, 1], np.uint8),
+              "ep_return": np.arange(3, dtype=np.float64) / 3, "ep_len": np.array([5, 70000, 2], np.int32)}
+    bench.dump_outputs(str(tmp_path / "a"), arrays)
+    assert sorted(os.listdir(tmp_path / "a")) == ["done.npy", "ep_len.npy", "ep_return.npy", "reward.npy"]
+    for k, v in arrays.items():
+        got = np.load(tmp_path / "a" / (k + ".npy"))
+        assert got.dtype == (np.float64 if v.dtype == np.float64 else np.float32) and got.shape == v.shape
+        np.testing.assert_array_equal(got, v)
+    bench.dump_outputs(str(tmp_path / "a"), {"reward": arrays["reward"]}, rank=1, world=2)
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "reward.rank1.npy"), arrays["reward"])
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 64)   # 2 arrays -> 32 bytes each: 8 float32 / 4 float64 elements
+    big = {"x": np.arange(100, dtype=np.float32), "y": np.arange(100, dtype=np.float64)}
+    bench.dump_outputs(str(tmp_path / "b"), big)
+    bench.dump_outputs(str(tmp_path / "c"), big)
+    x, y = np.load(tmp_path / "b" / "x.npy"), np.load(tmp_path / "b" / "y.npy")
+    assert x.shape == (8,) and y.shape == (4,) and x.nbytes + y.nbytes <= 64
+    assert np.all(np.diff(x) > 0) and set(x) <= set(big["x"])
+    np.testing.assert_array_equal(x, np.load(tmp_path / "c" / "x.npy"))
+    np.testing.assert_array_equal(y, np.load(tmp_path / "c" / "y.npy"))
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_asked_steps_and_dumps_its_last_outputs(tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` run measures the main window alone (no steady_state,
+    side windows or CPU baseline: those are --full's), reports K and ms_per_step = the window's wall time / K,
+    and --dump-outputs holds exactly what W + K steps of the same engine on the same seeded actions return
+    (bit for bit: the engine is deterministic, tests/test_envs.py::test_step_seq_equals_single_steps)."""
+    import subprocess
+
+    import torch
+
+    from crowdnav_dsrnn_amd.engine import CrowdNavEngine
+
+    E, K, W = 64, 3, 1
+    out = tmp_path / "dump"
+    p = subprocess.run([sys.executable, os.path.join(os.path.dirname(bench.__file__), "bench.py"), "--gpus", "1",
+                        "--steps", str(K), "--warmup", str(W), "--envs", str(E), "--dump-outputs", str(out)],
+                       capture_output=True, text=True, timeout=240, cwd=str(tmp_path))
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [json.loads(ln) for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, p.stdout
+    line = lines[0]
+    assert line["steps"] == K and line["warmup"] == W and line["config"]["launches"] == [W, K]
+    assert line["unit"] == "env-steps/s" and line["higher_is_better"] is True and line["dtype"] == "f64"
+    assert abs(line["ms_per_step"] - line["config"]["window_ms"]["wall"] / K) < 1e-3
+    assert abs(line["value"] - E * 1e3 / line["ms_per_step"]) <= 1e-3 * line["value"]
+    assert not [k for k in line if k in ("steady_state", "cpu_baseline", "side_wall_s") or k.startswith("side_c")]
+
+    device = torch.device("cuda", 0)
+    eng = CrowdNavEngine(bench.make_config(E, 10, 0, E), device)
+    gen = torch.Generator(device=device)
+    gen.manual_seed(0)
+    a = (torch.rand((K + W, E, 2), generator=gen, device=device) * 0.2 - 0.1).contiguous()
+    eng.reset()
+    eng.step_seq(a[0:W])
+    eng.step_seq(a[W:W + K])
+    torch.cuda.synchronize()
+    want = bench.engine_outputs(eng)
+    eng.close()
+    assert sorted(os.listdir(out)) == sorted(k + ".npy" for k in want)
+    for k, v in want.items():
+        got = np.load(out / (k + ".npy"))
+        assert got.dtype == (np.float64 if v.dtype == np.float64 else np.float32) and got.shape == v.shape
+        np.testing.assert_array_equal(got, v, err_msg=k)
+
+
 def test_side_windows_are_the_survey_shapes():
-    """The default line's side windows: C3 and C5 after 100 warm-up launches over 200 timed ones, C4 one eager
+    """The --full line's side windows: C3 and C5 after 100 warm-up launches over 200 timed ones, C4 one eager
     update + the graph-capturing one, then 2 timed updates, all inside the watchdog's deadline."""
     assert [w[0] for w in bench.SIDE_WINDOWS] == ["c3", "c5", "c4"]
     assert dict((w[0], w[1:]) for w in bench.SIDE_WINDOWS) == {"c3": (100, 200), "c5": (100, 200), "c4": (2, 2)}
