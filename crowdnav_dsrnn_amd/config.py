@@ -97,6 +97,11 @@ class Config(object):
     lidar = BaseConfig()
     lidar.enable = False
     lidar.viz = False
+    # live = True (this project's opt-in, not a reference option): with robot.policy = 'convgru' and
+    # lidar.enable the observation carries the scan of the CURRENT state at every reset and step — all humans
+    # and the walls, heading along the robot's velocity (cn_lidar_scan) — instead of the reference's held
+    # per-episode scan of the last human
+    lidar.live = False
     lidar.cfg = {"max_range": 5, "num_beams": 180, "robot_radius": robot.radius}
 
     action_space = BaseConfig()
@@ -183,7 +188,8 @@ def make_cn_config(config, num_envs, env_offset=0, nenv=None, phase=None, seed=N
     if getattr(config.noise, "add_noise", False):
         bad.append("noise.add_noise")
     # lidar.enable: the LiDAR scan only feeds the 'convgru' observation, built outside the step kernel by
-    # cn_lidar_obs (CrowdNavVecEnv); with the srnn policy it changes nothing the reference returns
+    # cn_lidar_obs (or, with lidar.live, cn_lidar_scan) in CrowdNavVecEnv; with the srnn policy it changes
+    # nothing the reference returns
     if not config.reward.potential_based or getattr(config.reward, "exponential", False):
         bad.append("reward.exponential")
     if config.humans.policy not in ("orca", "social_force"):

@@ -163,6 +163,18 @@ class CrowdNavEngine:
                                                lidar.data_ptr(), out.data_ptr()))
         return out
 
+    def lidar_scan(self, out, beams=180, max_range=5.0, robot_radius=0.3):
+        """The live ConvGRU observation (cn_lidar_scan) into out (E,1,7+beams) f32: the scan of the engine's
+        current state — all humans and the walls, heading along the robot's velocity. No host sync."""
+        t = self.torch
+        if (out.dtype != t.float32 or out.device != self.device or not out.is_contiguous()
+                or out.numel() != self.E * (7 + int(beams))):
+            raise ValueError("lidar_scan: out must be a contiguous float32 (E, 1, 7 + beams) tensor on %s" % self.device)
+        with t.cuda.device(self.device):
+            _lib.check(_lib.lib().cn_lidar_scan(self._h, self._stream(), int(beams), float(max_range),
+                                                float(robot_radius), out.data_ptr()))
+        return out
+
     def get_state(self):
         """abi.StateView of the engine; a mixed engine: [(rows, StateView of the group)] in group order."""
         buf = np.zeros(self.state_bytes, np.uint8)

@@ -218,12 +218,16 @@ class CrowdNavVecEnv:
         if engine_device is None and self.device.type == "cuda":
             engine_device = self.device
         self.engine = CrowdNavEngine(self.cn_cfg, engine_device)
-        # 'convgru' observation (crowd_sim_dict.py:57-62, 96-101): robot state + the episode's LiDAR scan
+        # 'convgru' observation (crowd_sim_dict.py:57-62, 96-101): robot state + the episode's LiDAR scan (or the
+        # live one)
         self.obs_mode = "convgru" if getattr(config.robot, "policy", "srnn") == "convgru" else "srnn"
         if self.obs_mode == "convgru":
             lc = dict(config.lidar.cfg)
             self._lidar_cfg = dict(enable=bool(config.lidar.enable), beams=int(lc["num_beams"]),
                                    max_range=float(lc["max_range"]), robot_radius=float(lc["robot_radius"]))
+            # lidar.live: the scan of the current state at every reset / step (cn_lidar_scan) instead of the
+            # reference's held per-episode scan; only with lidar.enable
+            self._lidar_live = bool(getattr(config.lidar, "live", False)) and self._lidar_cfg["enable"]
             B = self._lidar_cfg["beams"]
             self.observation_space = spaces.lidar_observation_space(B)
             self._lidar = torch.zeros((self.num_envs, B), dtype=torch.float32, device=self.engine.device)
@@ -255,6 +259,9 @@ class CrowdNavVecEnv:
         return o.to(self.device, copy=True)
 
     def _convgru_obs(self, reset_mask):
+        if self._lidar_live:
+            c = self._lidar_cfg
+            return self.engine.lidar_scan(self._lidar_obs, c["beams"], c["max_range"], c["robot_radius"])
         return self.engine.lidar_obs(self._lidar_obs, self._lidar, reset_mask, **self._lidar_cfg)
 
     def reset(self):

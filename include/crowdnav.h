@@ -33,6 +33,8 @@
  *                   policy_factory[name](config).predict(JointState) (crowd_nav/policy/policy_factory.py:1-17)
  *   cn_lidar_obs     ⟵ CrowdSimDict.generate_ob's 'convgru' observation (crowd_sim_dict.py:96-101) with
  *                   LidarSensor.sensor_spin (crowd_sim/envs/utils/lidarv2.py:398-427) evaluated at reset
+ *   cn_lidar_scan    ⟵ the scan CrowdSimDict.step() takes every step and discards (crowd_sim_dict.py:224-251):
+ *                   all humans and the walls, heading along the robot's velocity (opt-in live mode)
  *   cn_wgrad       ⟵ the weight / bias gradient of the Linear layers with a tiny side (autograd's dy^T x)
  *   cn_attn_pool_fwd / cn_attn_pool_bwd ⟵ EdgeAttention's weighted sum of the spatial edge states
  *                   (srnn_model.py:320-333, torch.bmm(h_spatials^T, attn)) and its gradient
@@ -171,7 +173,7 @@ void cn_destroy(cn_engine *eng);
  * [num_envs]-row buffers; spatial_edges rows beyond an env's own human count are padding (a never-seen
  * human: belief (15, 15) relative to the robot). cn_step launches one step kernel per group.
  * cn_get_state / cn_set_state: the groups' blobs concatenated in group order; cn_state_device_ptr: NULL;
- * cn_lidar_obs: CN_EUNSUPPORTED. */
+ * cn_lidar_obs / cn_lidar_scan: CN_EUNSUPPORTED. */
 int cn_create_mixed(const cn_config *groups, int num_groups, const int32_t *env_group, int64_t num_envs, int device,
                     cn_engine **out);
 /* per-env human count, into host memory [E] (a plain engine: N everywhere) */
@@ -394,6 +396,20 @@ int cn_gru_bwd_seq(void *stream, int T, int H, int nseg, const cn_gru_seq_bwd *s
  * Call after cn_reset / cn_step on the same stream. */
 int cn_lidar_obs(cn_engine *eng, void *stream, const uint8_t *reset_mask, int enable, int beams, double max_range,
                  double robot_radius, float *lidar, float *obs);
+
+/* The live ConvGRU observation row of every env, obs [E][7 + beams] float32, same layout as cn_lidar_obs:
+ *   [clip(robot (px, py, radius, gx, gy, v_pref, theta) / max_range, 0, 1), |1 - clip(dist / max_range, 0, 1)|]
+ * with the scan of the engine's CURRENT state: the one CrowdSimDict.step() computes every step and discards
+ * (crowd_sim_dict.py:224-251) — the sensor at the robot's position, heading atan2(vy, vx) (0 right after a
+ * reset), all N
+ * humans in index order and the walls of the square world, lidarv2.py's semantics in float64: per-obstacle
+ * angular windows with their in-place flip, only the obstacle with the nearest centre among those whose
+ * window holds the beam is sampled (every 0.01 m, first sample strictly inside), else the first wall crossed
+ * within range, never inside robot_radius. Nothing is held between calls: call it after cn_reset / cn_step /
+ * cn_set_state on the same stream; envs that auto-reset in that step show their new episode. One launch,
+ * no synchronisation and no allocation (graph-capturable). beams in [2, 4096], max_range in (0, 1e4].
+ * A mixed engine: CN_EUNSUPPORTED. */
+int cn_lidar_scan(cn_engine *eng, void *stream, int beams, double max_range, double robot_radius, float *obs);
 
 /* Test hook: the norm-zone predicate of the step kernel, robot 64-gon (GEOS Point.buffer(r)) vs convex quad
  * (crowd_sim.py norm-zone penalty), for n cases on the device: px, py, r [n], qx, qy [n][4],
