@@ -186,7 +186,8 @@ class BoxSpace:
 BoxSpace.__name__ = "Box"
 
 
-def make_policy(N, E=4, T=8, device="cpu"):
+def make_policy(N, E=4, T=8, device="cpu", **srnn_sizes):
+    """srnn_sizes: overrides of config.SRNN fields (e.g. human_node_rnn_size=96)."""
     from crowdnav_dsrnn_amd.policy import Policy
 
     c = clone_config(Config())
@@ -194,6 +195,9 @@ def make_policy(N, E=4, T=8, device="cpu"):
     c.training.num_processes = E
     c.ppo.num_steps = T
     c.ppo.num_mini_batch = 1
+    for k, v in srnn_sizes.items():
+        assert hasattr(c.SRNN, k), k
+        setattr(c.SRNN, k, v)
     pol = Policy({}, BoxSpace((2,)), base="srnn", base_kwargs=c)
     pol.load_state_dict(procedural_state_dict(pol))
     return pol.to(device).eval()
@@ -242,3 +246,63 @@ def attention_pool_ref(hs, attn):
     import torch
 
     return torch.bmm(hs.transpose(1, 2), attn).squeeze(-1)
+
+
+def gru_step_fwd_ref(gi, gh, hm, m_next=None):
+    """One GRU step after the two GEMMs as include/crowdnav.h states it for cn_gru_fwd_step (gate order
+    r | z | n), in the operands' dtype (float64 in the tests): returns h, hm_next = h * m_next (h itself with
+    m_next None) and the record save = r | z | n | gh_n."""
+    import torch
+
+    H = hm.shape[1]
+    r = torch.sigmoid(gh[:, :H] + gi[:, :H])
+    z = torch.sigmoid(gh[:, H:2 * H] + gi[:, H:2 * H])
+    ghn = gh[:, 2 * H:]
+    n = torch.tanh(gi[:, 2 * H:] + r * ghn)
+    h = (hm - n) * z + n
+    hm_next = h if m_next is None else h * m_next.unsqueeze(-1)
+    return h, hm_next, torch.cat((r, z, n, ghn), 1)
+
+
+def gru_step_bwd_ref(acc, m_next, dout, save, hm):
+    """Gradient of one step as include/crowdnav.h states it for cn_gru_bwd_step: g = acc * m_next + dout is
+    dL/dh_t; returns the new acc = g * z, dgi = dr | dz | dn and dgh = dr | dz | dhn ([B][3H] each)."""
+    import torch
+
+    H = hm.shape[1]
+    r, z, n, ghn = (save[:, k * H:(k + 1) * H] for k in range(4))
+    g = acc if m_next is None else acc * m_next.unsqueeze(-1)
+    if dout is not None:
+        g = g + dout
+    dn = g * (1 - z) * (1 - n * n)
+    dz = g * (hm - n) * z * (1 - z)
+    dr = dn * ghn * r * (1 - r)
+    dhn = dn * r
+    return g * z, torch.cat((dr, dz, dn), 1), torch.cat((dr, dz, dhn), 1)
+
+
+def gru_row_tile(Bs, H):
+    """Row tile (128, or 32 = split-K) the sequence / fused-step GRU kernels pick on the current device for
+    one launch over GRUs of Bs rows: cn_gru_bwd_seq_work_elems(1, H, ...) is 64 x 4H floats for the bias
+    reduction plus 4H per row tile of every GRU. Needs row counts at which the two tilings differ."""
+    from crowdnav_dsrnn_amd import _lib
+
+    Bs = tuple(int(b) for b in ((Bs,) if isinstance(Bs, int) else Bs))
+    segs = (_lib.GruSeqBwd * len(Bs))()
+    for s, b in zip(segs, Bs):
+        s.B = b
+    tiles = (_lib.lib().cn_gru_bwd_seq_work_elems(1, H, len(Bs), segs) - 64 * 4 * H) // (4 * H)
+    n128, n32 = (sum((b + t - 1) // t for b in Bs) for t in (128, 32))
+    assert n128 != n32, "row counts %s do not tell the tilings apart" % (Bs,)
+    assert tiles in (n128, n32), (tiles, n128, n32)
+    return 128 if tiles == n128 else 32
+
+
+def gru_form_rows(H, cus):
+    """(B_hi, B_lo): total row counts on either side of the sequence kernels' threshold on a device with
+    `cus` compute units. 128-row tiles run when ceil(rows / 128) * (H / 32) >= cus, so the smallest such
+    row count is Rmin = 128 * (ceil(cus / (H / 32)) - 1) + 1; B_hi = Rmin + 40 has a ragged last 128-row
+    tile and B_lo = Rmin - 20 is split-K with a ragged last 32-row tile."""
+    ut = H // 32
+    rmin = 128 * ((cus + ut - 1) // ut - 1) + 1
+    return rmin + 40, rmin - 20

@@ -78,6 +78,45 @@ def test_gru_seq_rejects_bad_arguments_without_launching(L):
     assert L.cn_gru_fwd_seq(None, 4, 256, 1, seg) != 0 and b"nh == T" in L.cn_last_error()
 
 
+def test_gru_step_entry_points_reject_bad_arguments_without_launching(L):
+    """cn_gru_fwd_fused, cn_gru_fwd_step_group, cn_gru_bwd_step_bias / _gates and cn_gru_bias_reduce turn down
+    sizes, layouts and alignments their kernels do not serve before any launch (non-null dummy addresses, 16-byte
+    aligned unless the case says otherwise, are never dereferenced), each naming itself in cn_last_error()."""
+    def rejected(rc, who):
+        return rc != 0 and who in L.cn_last_error()
+
+    # cn_gru_fwd_fused(stream, B, H, gi, hm, w_hh, b_hh, m_next, h_out, hm_next, save, h_out2, g2, ld2)
+    fused = b"cn_gru_fwd_fused"
+    assert rejected(L.cn_gru_fwd_fused(None, 64, 48, 16, 32, 48, 64, None, 80, None, None, None, 1, 0), fused)    # H % 32
+    assert rejected(L.cn_gru_fwd_fused(None, 64, 64, 16, 36, 48, 64, None, 80, None, None, None, 1, 0), fused)    # hm + 4
+    assert b"16-byte aligned" in L.cn_last_error()
+    assert rejected(L.cn_gru_fwd_fused(None, 64, 64, 16, 32, 48, 64, None, 80, None, None, 96, 0, 640), fused)    # g2 = 0
+    assert rejected(L.cn_gru_fwd_fused(None, 64, 64, 16, 32, 48, 64, None, 80, None, None, 96, 5, 319), fused)    # ld2 < g2 H
+    assert b"ld2 >= g2 * H" in L.cn_last_error()
+
+    # cn_gru_step_seg: B, gi, x, w_ih, b_ih, F, hm, w_hh, b_hh, h_out, h_out2, g2, ld2
+    group = b"cn_gru_fwd_step_group"
+    with_gi = _lib.GruStepSeg(64, 16, None, None, None, 0, 32, 48, 64, 80, None, 1, 0)
+    with_x = _lib.GruStepSeg(64, None, 16, 96, 112, 64, 32, 48, 64, 80, None, 1, 0)
+    segs = (_lib.GruStepSeg * 3)(with_gi, with_x, with_gi)
+    assert rejected(L.cn_gru_fwd_step_group(None, 256, 2, segs), group)                    # one GRU gi, the other x
+    assert b"every GRU" in L.cn_last_error()
+    assert rejected(L.cn_gru_fwd_step_group(None, 256, 3, segs), group)                    # nseg = 3
+    one = (_lib.GruStepSeg * 1)(with_x)
+    one[0].F = 48
+    assert rejected(L.cn_gru_fwd_step_group(None, 256, 1, one), group)                     # x with F % 32 != 0
+    assert b"F % 32" in L.cn_last_error()
+    one[0] = with_gi
+    one[0].w_hh = 52
+    assert rejected(L.cn_gru_fwd_step_group(None, 256, 1, one), group)                     # a misaligned array
+    assert b"16-byte aligned" in L.cn_last_error()
+
+    # the bias-folding step kernels serve H in {64, 128, 256} only; the reduction needs rows
+    assert rejected(L.cn_gru_bwd_step_bias(None, 16, 96, 16, None, None, 32, 48, 64, 80, 96), b"cn_gru_bwd_step_bias")
+    assert rejected(L.cn_gru_bwd_step_gates(None, 16, 96, 16, None, None, 32, 48, 64, 80), b"cn_gru_bwd_step_gates")
+    assert rejected(L.cn_gru_bias_reduce(None, 0, 64, 16, 32, 48, 64), b"cn_gru_bias_reduce")
+
+
 def test_step_seq_and_graph_census_reject_bad_arguments(L):
     """cn_step_seq / cn_graph_node_counts validate their arguments before touching the GPU."""
     assert L.cn_step_seq(None, None, 4, None, 0, *([None] * 9)) != 0

@@ -1,0 +1,549 @@
+"""The GRU kernels of csrc/cn_gru.hip in every dispatch form and at every accepted size vs float64.
+
+Each recurrent launch picks the 128-row kernels (cn_gru_fused_kernel / cn_gru_bwd_fused_kernel) when
+ceil(rows / 128) * (H / 32) >= the device's CU count and the 32-row split-K kernels (cn_gru_fused_sk_kernel /
+cn_gru_bwd_sk_kernel) otherwise; the forward ones project x themselves (XM, F % 32 == 0) or take gi from a
+library GEMM. The row counts here are derived from the CU count so both forms run on whatever device the suite
+is on, and every test asserts the form it ran through helpers.gru_row_tile (cn_gru_bwd_seq_work_elems reveals
+the tile), so a CU-count or threshold change fails here instead of moving coverage.
+
+References: plain torch in float64 on the CPU (helpers.masked_gru_ref, gru_infer_step_ref and the one-step
+restatements gru_step_fwd_ref / gru_step_bwd_ref of include/crowdnav.h's formulas); none shares code with ops.py.
+Tolerances (the project's): sequences 2e-5 abs on outputs / states, 1e-4 * max(1, max|ref|) on gradients
+(tests/test_policy.py::test_masked_gru_kernels_vs_fp64; the float32 run of masked_gru_ref itself is >= 20x
+inside them at these sizes); step kernels 2e-6 * max(1, |ref|) elementwise and 2e-6 * sum|terms| on column
+sums (test_wgrad_kernel_vs_fp64's bound)."""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+from tests.helpers import (gru_form_rows, gru_infer_step_ref, gru_row_tile, gru_step_bwd_ref, gru_step_fwd_ref,
+                           masked_gru_ref)
+
+DEV = "cuda:0"
+NAMES = ["out", "hT", "dx", "dh0", "dW_ih", "dW_hh", "db_ih", "db_hh"]
+
+
+def _form_B(form, H):
+    """Total rows that run `form` ('hi': 128-row tiles, 'lo': split-K) at hidden size H on this device."""
+    hi, lo = gru_form_rows(H, torch.cuda.get_device_properties(0).multi_processor_count)
+    return hi if form == "hi" else lo
+
+
+def _case(g, T, B, F, H, masks=None):
+    x = torch.randn(T, B, F, generator=g)
+    h0 = torch.randn(B, H, generator=g) * 0.5
+    if masks is None:
+        masks = (torch.rand(T, B, generator=g) > 0.2).float()
+        masks[:, 0] = 0.0
+    ws = [(torch.rand(3 * H, F, generator=g) * 2 - 1) / H ** 0.5, (torch.rand(3 * H, H, generator=g) * 2 - 1) / H ** 0.5,
+          torch.randn(3 * H, generator=g) * 0.1, torch.randn(3 * H, generator=g) * 0.1]
+    return x, h0, masks, ws, torch.randn(T, B, H, generator=g), torch.randn(B, H, generator=g)
+
+
+def _run_group(group, cases, dev, dt, use=("out", "hT")):
+    """Forward + backward of one or two GRUs; per GRU the eight NAMES tensors as float64 on the CPU."""
+    leaves, grus, loss = [], [], 0
+    for x, h0, masks, ws, _, _ in cases:
+        lv = [t.to(dev, dt).detach().clone().requires_grad_(True) for t in (x, h0, *ws)]
+        leaves.append(lv)
+        grus.append((lv[0], lv[1], masks.to(dev, dt), *lv[2:]))
+    res = group(*grus)
+    for (out, hT), (_, _, _, _, dout, dhT) in zip(res, cases):
+        if "out" in use:
+            loss = loss + (out * dout.to(dev, dt)).sum()
+        if "hT" in use:
+            loss = loss + (hT * dhT.to(dev, dt)).sum()
+    loss.backward()
+    return [[out.detach().cpu().double(), hT.detach().cpu().double()] + [l.grad.cpu().double() for l in lv]
+            for (out, hT), lv in zip(res, leaves)]
+
+
+def _check_vs_fp64(cases, use=("out", "hT")):
+    from crowdnav_dsrnn_amd import ops
+
+    got = _run_group(ops.masked_gru_group, cases, DEV, torch.float32, use)
+    want = _run_group(lambda *grus: [masked_gru_ref(*gr) for gr in grus], cases, "cpu", torch.float64, use)
+    for k in range(len(cases)):
+        for n, a, b in zip(NAMES, got[k], want[k]):
+            tol = 2e-5 if n in ("out", "hT") else 1e-4 * max(1.0, float(b.abs().max()))
+            assert torch.isfinite(a).all(), "gru %d %s" % (k, n)
+            np.testing.assert_allclose(a.numpy(), b.numpy(), atol=tol, rtol=0, err_msg="gru %d %s" % (k, n))
+
+
+def _split(B, split):
+    return (B,) if split is None else (B - split, split)
+
+
+# ---- 1. sequence kernels, every form ----------------------------------------------------------------------
+@pytest.mark.gpu
+@pytest.mark.parametrize("split", [None, 77, 1, 50])
+@pytest.mark.parametrize("F", [64, 48])
+@pytest.mark.parametrize("form", ["hi", "lo"])
+def test_seq_every_form_vs_fp64(form, F, split):
+    """ops.masked_gru_group at H = 256, T = 3 vs float64 over {128-row, split-K} x {XM (F 64), gi (F 48)} x
+    {one GRU, two GRUs}: with two GRUs the total rows decide the form and the boundary (B - 77 | 77, B - 1 | 1,
+    B - 50 | 50) falls inside the tiling with B0 no tile multiple. B is 41 (hi) or -19 (lo) modulo 128 on any
+    device, so B_lo - 77 alone is a whole number of 32-row tiles (a boundary on a tile edge); 50 gives split-K
+    its second ragged boundary. All eight tensors of every GRU."""
+    H, T = 256, 3
+    Bs = _split(_form_B(form, H), split)
+    tile = gru_row_tile(Bs, H)
+    print("seq form=%s F=%d Bs=%s row tile %d" % (form, F, Bs, tile))
+    assert tile == (128 if form == "hi" else 32)
+    assert Bs[0] % tile or (form, split) == ("lo", 77)
+    g = torch.Generator().manual_seed(1000 + F + (split or 0))
+    _check_vs_fp64([_case(g, T, B, F, H) for B in Bs])
+
+
+# ---- 2. size sweep ----------------------------------------------------------------------------------------
+@pytest.mark.gpu
+@pytest.mark.parametrize("F", [32, 128, 16])
+@pytest.mark.parametrize("H", [32, 96, 160, 512])
+def test_seq_sizes_split_k_vs_fp64(H, F):
+    """Every accepted kind of H (one K chunk: three of the four split-K waves contribute zero; three and five
+    unit tiles: a non-power-of-two k % unit_tiles; sixteen) x F (XM 32 / 128, gi 16) in split-K at B = 70."""
+    T, B = 3, 70
+    tile = gru_row_tile(B, H)
+    print("sizes H=%d F=%d B=%d row tile %d" % (H, F, B, tile))
+    assert tile == 32
+    _check_vs_fp64([_case(torch.Generator().manual_seed(H + F), T, B, F, H)])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("F", [32, 128, 16])
+@pytest.mark.parametrize("H", [32, 96, 512])
+def test_seq_sizes_128_row_vs_fp64(H, F):
+    """The same sizes on 128-row tiles: the smallest row count that selects them, + 40 (ragged last tile), T = 2."""
+    T, B = 2, _form_B("hi", H)
+    tile = gru_row_tile(B, H)
+    print("sizes H=%d F=%d B=%d row tile %d" % (H, F, B, tile))
+    assert tile == 128
+    _check_vs_fp64([_case(torch.Generator().manual_seed(H + F + 1), T, B, F, H)])
+
+
+# ---- 3. mask and length edges -----------------------------------------------------------------------------
+def _mask(kind, T, B):
+    m = torch.ones(T, B)
+    if kind == "zeros":
+        m.zero_()
+    elif kind == "first":
+        m[0] = 0.0
+    elif kind == "last":
+        m[T - 1] = 0.0
+    elif kind == "alternating":
+        m = ((torch.arange(T).unsqueeze(1) + torch.arange(B).unsqueeze(0)) % 2).float()
+    return m
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("use", ["out", "hT"])
+@pytest.mark.parametrize("kind", ["ones", "zeros", "first", "last", "alternating"])
+@pytest.mark.parametrize("T", [1, 2, 5])
+def test_seq_mask_and_length_edges_vs_fp64(T, kind, use):
+    """B = 70, H = 64: sequences of one, two and five steps under every edge mask, with only `out` or only
+    `hT` in the loss (the other gradient arrives as zeros)."""
+    B, F, H = 70, 32, 64
+    assert gru_row_tile(B, H) == 32
+    g = torch.Generator().manual_seed(T * 10 + len(kind))
+    _check_vs_fp64([_case(g, T, B, F, H, masks=_mask(kind, T, B))], use=(use,))
+
+
+# ---- 4. the no-grad masked-state ring ---------------------------------------------------------------------
+@pytest.mark.gpu
+@pytest.mark.parametrize("F", [64, 48])
+@pytest.mark.parametrize("form", ["hi", "lo"])
+def test_seq_no_grad_ring_is_bit_identical(form, F):
+    """T = 5 under torch.no_grad() (masked-state ring nh = 2) vs the grad-enabled run (nh = T): the same kernel
+    and arithmetic per row, only the hm buffers differ, so out / hT are equal bit for bit."""
+    from crowdnav_dsrnn_amd import ops
+
+    H, T = 256, 5
+    B = _form_B(form, H)
+    assert gru_row_tile(B, H) == (128 if form == "hi" else 32)
+    x, h0, masks, ws, _, _ = _case(torch.Generator().manual_seed(77 + F), T, B, F, H)
+    args = [t.to(DEV) for t in (x, h0, masks, *ws)]
+    with torch.no_grad():
+        out_n, hT_n = ops.masked_gru(*args)
+    lv = [a.clone().requires_grad_(True) for a in args]
+    out_g, hT_g = ops.masked_gru(lv[0], lv[1], args[2], *lv[3:])
+    assert out_g.requires_grad and not out_n.requires_grad
+    np.testing.assert_array_equal(out_n.cpu().numpy(), out_g.detach().cpu().numpy())
+    np.testing.assert_array_equal(hT_n.cpu().numpy(), hT_g.detach().cpu().numpy())
+    ref, _ = masked_gru_ref(*[a.cpu().double() for a in args])
+    np.testing.assert_allclose(out_n.cpu().double().numpy(), ref.numpy(), atol=2e-5, rtol=0)
+
+
+# ---- 5. cn_gru_fwd_step_group vs float64 ------------------------------------------------------------------
+@pytest.mark.gpu
+@pytest.mark.parametrize("G", [1, 5])
+@pytest.mark.parametrize("F", [64, 48])
+@pytest.mark.parametrize("form", ["hi", "lo"])
+@pytest.mark.parametrize("nseg", [1, 2])
+def test_infer_group_vs_fp64(nseg, form, F, G):
+    """ops.gru_infer_group (cn_gru_fwd_step_group) vs gru_infer_step_ref in float64, one and two GRUs, both
+    forms, XM (F 64) and gi (F 48). dest is a slice of a (R', G + 2, H) state tensor aliasing h0 (ld2 > g2 * H):
+    GRU 0 owns [:, 1:G+1], GRU 1 [:, 0:1]; [:, G+1] (NaN) and, with one GRU, [:, 0] must stay bit for bit."""
+    from crowdnav_dsrnn_amd import ops
+
+    H = 256
+    per = G + 1 if nseg == 2 else G
+    Rg = -(-_form_B("hi", H) // per) if form == "hi" else _form_B("lo", H) // per
+    Bs = (Rg * G, Rg)[:nseg]
+    tile = gru_row_tile(Bs, H)
+    print("infer nseg=%d form=%s F=%d G=%d Bs=%s row tile %d" % (nseg, form, F, G, Bs, tile))
+    assert tile == (128 if form == "hi" else 32)
+    g = torch.Generator().manual_seed(nseg * 100 + F + G)
+    state = torch.randn(Rg, G + 2, H, generator=g) * 0.5
+    state[:, G + 1] = float("nan")
+    m = (torch.rand(Rg, generator=g) > 0.2).float()
+    xs = [torch.randn(Rg * G, F, generator=g), torch.randn(Rg, F, generator=g)]
+    ws = [[(torch.rand(3 * H, F, generator=g) * 2 - 1) / H ** 0.5, (torch.rand(3 * H, H, generator=g) * 2 - 1) / H ** 0.5,
+           torch.randn(3 * H, generator=g) * 0.1, torch.randn(3 * H, generator=g) * 0.1] for _ in range(2)]
+
+    def args(st, i, dev, dt):
+        sl = st[:, 1:G + 1, :] if i == 0 else st[:, 0:1, :]
+        return (xs[i].to(dev, dt), sl, m.to(dev, dt), *[w.to(dev, dt) for w in ws[i]], sl)
+
+    st_ref = state.double()
+    ref = [gru_infer_step_ref(*args(st_ref, i, "cpu", torch.float64)) for i in range(nseg)]
+    st_got = state.to(DEV)
+    got = ops.gru_infer_group(*[args(st_got, i, DEV, torch.float32) for i in range(nseg)])
+    torch.cuda.synchronize()
+    st_got = st_got.cpu()
+    written = torch.zeros(Rg, G + 2, dtype=torch.bool)
+    written[:, 1:G + 1] = True
+    written[:, 0] = nseg == 2
+    for a, b in zip(got, ref):
+        assert torch.isfinite(a).all()
+        np.testing.assert_allclose(a.cpu().double().numpy(), b.numpy(), atol=2e-5, rtol=0)
+    np.testing.assert_allclose(st_got[written].double().numpy(), st_ref[written].numpy(), atol=2e-5, rtol=0)
+    np.testing.assert_array_equal(st_got[~written].view(torch.int32).numpy(), state[~written].view(torch.int32).numpy())
+
+
+# ---- 6. step-level entry points through ctypes ------------------------------------------------------------
+def _lib_stream():
+    from crowdnav_dsrnn_amd import _lib
+
+    return _lib, _lib.lib(), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _nan(*shape):
+    return torch.full(shape, float("nan"), device=DEV)
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def _close(got, ref, name):
+    """Elementwise outputs of unit-scale gates: 2e-6 * max(1, |ref|)."""
+    got = got.cpu().double()
+    assert torch.isfinite(got).all(), name
+    bound = 2e-6 * torch.clamp(ref.abs(), min=1.0)
+    bad = (got - ref).abs() > bound
+    assert not bad.any(), "%s: %d of %d out of bound, max err %g" % (name, int(bad.sum()), bad.numel(),
+                                                                    float((got - ref).abs().max()))
+
+
+def _step_operands(g, B, H):
+    gi = torch.randn(B, 3 * H, generator=g)
+    gh = torch.randn(B, 3 * H, generator=g)
+    hm = torch.randn(B, H, generator=g) * 0.5
+    m = (torch.rand(B, generator=g) > 0.3).float()
+    return gi, gh, hm, m
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("with_hmn", [False, True])
+@pytest.mark.parametrize("with_save", [False, True])
+@pytest.mark.parametrize("mask", [False, True])
+@pytest.mark.parametrize("H", [4, 36, 100, 256])
+def test_fwd_step_and_scatter_vs_fp64(H, mask, with_save, with_hmn):
+    """cn_gru_fwd_step and cn_gru_fwd_step_scatter (grouped second copy, ragged last group) vs the float64
+    restatement: h_out, hm_next = h * m_next, save = r | z | n | gh_n; m_next null / given (mask), save and
+    hm_next each null / given. B = 300: more than one block at every H. Every output is prefilled with NaN; the
+    grouped copy's unwritten elements (the last group's missing rows and the (G + 1)-th slot of every group)
+    must keep their bits."""
+    _lib, L, st = _lib_stream()
+    B, G = 300, 7
+    Rg = (B + G - 1) // G
+    gi, gh, hm, m = _step_operands(torch.Generator().manual_seed(H + 4 * mask + 2 * with_save + with_hmn), B, H)
+    h, hmn, save = gru_step_fwd_ref(gi.double(), gh.double(), hm.double(), m.double() if mask else None)
+    dgi, dgh, dhm, dm = (t.to(DEV) for t in (gi, gh, hm, m))
+    written = torch.zeros(Rg, G + 1, dtype=torch.bool)
+    written[:, :G] = True
+    written.view(-1)[[(b // G) * (G + 1) + b % G for b in range(B, Rg * G)]] = False
+    assert int(written.sum()) == B
+    for scatter in (False, True):
+        o_h, o_hmn, o_save = _nan(B, H), (_nan(B, H) if with_hmn else None), (_nan(B, 4 * H) if with_save else None)
+        o_h2 = _nan(Rg, G + 1, H) if scatter else None
+        common = (st, B, H, dgi.data_ptr(), dgh.data_ptr(), dhm.data_ptr(), dm.data_ptr() if mask else None,
+                  o_h.data_ptr(), _ptr(o_hmn), _ptr(o_save))
+        if scatter:
+            guard = o_h2.cpu().view(torch.int32)[~written].clone()
+            _lib.check(L.cn_gru_fwd_step_scatter(*common, o_h2.data_ptr(), G, (G + 1) * H))
+        else:
+            _lib.check(L.cn_gru_fwd_step(*common))
+        torch.cuda.synchronize()
+        _close(o_h, h, "h_out")
+        if with_hmn:
+            _close(o_hmn, hmn, "hm_next")
+        if with_save:
+            _close(o_save, save, "save")
+        if scatter:
+            o_h2 = o_h2.cpu()
+            _close(o_h2[written], h, "h_out2")                       # rows in order: b -> (b // G, b % G)
+            np.testing.assert_array_equal(o_h2[written].numpy(), o_h.cpu().numpy())
+            np.testing.assert_array_equal(o_h2.view(torch.int32)[~written].numpy(), guard.numpy())
+
+
+def _bwd_operands(g, B, H):
+    gi, gh, hm, m = _step_operands(g, B, H)
+    _, _, save = gru_step_fwd_ref(gi.double(), gh.double(), hm.double())
+    return (torch.randn(B, H, generator=g), m, torch.randn(B, H, generator=g), save.float(), hm)
+
+
+def _bwd_ref(acc, m, dout, save, hm, mask, use_dout):
+    return gru_step_bwd_ref(acc.double(), m.double() if mask else None, dout.double() if use_dout else None,
+                            save.double(), hm.double())
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("use_dout", [False, True])
+@pytest.mark.parametrize("mask", [False, True])
+@pytest.mark.parametrize("H", [4, 36, 100, 256])
+def test_bwd_step_vs_fp64(H, mask, use_dout):
+    """cn_gru_bwd_step vs the float64 restatement: dgi, dgh and the updated acc, every row."""
+    _lib, L, st = _lib_stream()
+    B = 300
+    acc, m, dout, save, hm = _bwd_operands(torch.Generator().manual_seed(H + 2 * mask + use_dout), B, H)
+    r_acc, r_dgi, r_dgh = _bwd_ref(acc, m, dout, save, hm, mask, use_dout)
+    d_acc, d_m, d_dout, d_save, d_hm = (t.clone().to(DEV) for t in (acc, m, dout, save, hm))
+    o_dgi, o_dgh = _nan(B, 3 * H), _nan(B, 3 * H)
+    _lib.check(L.cn_gru_bwd_step(st, B, H, d_acc.data_ptr(), d_m.data_ptr() if mask else None,
+                                 d_dout.data_ptr() if use_dout else None, d_save.data_ptr(), d_hm.data_ptr(),
+                                 o_dgi.data_ptr(), o_dgh.data_ptr()))
+    torch.cuda.synchronize()
+    _close(d_acc, r_acc, "acc")
+    _close(o_dgi, r_dgi, "dgi")
+    _close(o_dgh, r_dgh, "dgh")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("use_dout", [False, True])
+@pytest.mark.parametrize("mask", [False, True])
+@pytest.mark.parametrize("B", [1, 16, 17, 250])
+@pytest.mark.parametrize("H", [64, 128, 256])
+def test_bwd_step_bias_and_gates_vs_fp64(H, B, mask, use_dout):
+    """cn_gru_bwd_step_bias and cn_gru_bwd_step_gates (ragged 16-row blocks at B 1 / 17 / 250; m_next and dout
+    each null / given) vs float64: dgi / dgh or g = dn | dr | dz | dhn and the updated acc elementwise, and
+    every row of part (column sums of dr | dz | dn | dhn per 16-row block) against the float64 sums of the
+    float64 terms; the two kernels agree exactly on acc, part and the shared columns.
+
+    part's bound is 2e-6 * sum|terms| per entry wherever plain float32 meets it. It cannot everywhere: the
+    terms are computed, not given, and 1 - n * n (ATen's operation order, kept) cancels for |n| near 1, so a
+    block of few rows inherits the relative error of single gate gradients (B = 1: part is dgi's row, which is
+    within its own 2e-6 * max(1, |ref|)). The test therefore measures, per case and with no kernel involved,
+    the float32 run of gru_step_bwd_ref on the CPU with float32 block sums against the same float64 reference,
+    as a multiple f32 of 2e-6 * sum|terms|, and asserts part within max(1, 4 * f32) x 2e-6 * sum|terms| (the
+    factor 4 covers another summation order). Measured as that multiple, kernel / float32 restatement, worst
+    of each (H, B) over mask and dout: H 64: B 1 2.41 / 2.41, B 16 0.116 / 0.116, B 17 2.66 / 2.66, B 250
+    0.129 / 0.129; H 128: 12.9 / 12.9, 0.117 / 0.091, 1.96 / 1.96, 0.142 / 0.122; H 256: 6.66 / 6.66,
+    0.077 / 0.095, 2.68 / 2.68, 0.112 / 0.135 (blocks of up to 16 rows sum in another order; a one-row tail block
+    is the restatement bit for bit). Both figures are printed for every case. In addition part must
+    equal, within the plain 2e-6 * sum|terms|, the float64 sums of the float32 rows the launch itself wrote."""
+    _lib, L, st = _lib_stream()
+    acc, m, dout, save, hm = _bwd_operands(torch.Generator().manual_seed(H + B + 2 * mask + use_dout), B, H)
+    r_acc, r_dgi, r_dgh = _bwd_ref(acc, m, dout, save, hm, mask, use_dout)
+    nblk = int(L.cn_gru_bias_blocks(B))
+    assert nblk == (B + 15) // 16
+    cols = torch.cat((r_dgi, r_dgh[:, 2 * H:]), 1)                     # dr | dz | dn | dhn
+    pad = torch.zeros(nblk * 16 - B, 4 * H, dtype=torch.float64)
+    blocks = torch.cat((cols, pad), 0).view(nblk, 16, 4 * H)
+    r_part, r_abs = blocks.sum(1), blocks.abs().sum(1)
+    # the float32 restatement's own deviation from float64 on this case (CPU, no kernel)
+    _, f_dgi, f_dgh = gru_step_bwd_ref(acc, m if mask else None, dout if use_dout else None, save, hm)
+    f_cols = torch.cat((f_dgi, f_dgh[:, 2 * H:], ), 1)
+    f_part = torch.cat((f_cols, pad.float()), 0).view(nblk, 16, 4 * H).sum(1)
+    assert f_part.dtype == torch.float32
+    f32 = float(((f_part.double() - r_part).abs() / (2e-6 * r_abs + 1e-30)).max())
+    factor = max(1.0, 4.0 * f32)
+    d_m, d_dout, d_save, d_hm = (t.to(DEV) for t in (m, dout, save, hm))
+    ptrs = (d_m.data_ptr() if mask else None, d_dout.data_ptr() if use_dout else None, d_save.data_ptr(),
+            d_hm.data_ptr())
+
+    acc_b, dgi, dgh, part_b = acc.clone().to(DEV), _nan(B, 3 * H), _nan(B, 3 * H), _nan(nblk, 4 * H)
+    _lib.check(L.cn_gru_bwd_step_bias(st, B, H, acc_b.data_ptr(), *ptrs, dgi.data_ptr(), dgh.data_ptr(),
+                                      part_b.data_ptr()))
+    acc_g, gg, part_g = acc.clone().to(DEV), _nan(B, 4 * H), _nan(nblk, 4 * H)
+    _lib.check(L.cn_gru_bwd_step_gates(st, B, H, acc_g.data_ptr(), *ptrs, gg.data_ptr(), part_g.data_ptr()))
+    torch.cuda.synchronize()
+    _close(acc_b, r_acc, "acc")
+    _close(dgi, r_dgi, "dgi")
+    _close(dgh, r_dgh, "dgh")
+    _close(gg, torch.cat((r_dgi[:, 2 * H:], r_dgi[:, :2 * H], r_dgh[:, 2 * H:]), 1), "g")
+    terms = torch.cat((dgi.cpu().double(), dgh.cpu().double()[:, 2 * H:]), 1)
+    terms = torch.cat((terms, pad), 0).view(nblk, 16, 4 * H)
+    for name, p in (("part (bias)", part_b), ("part (gates)", part_g)):
+        p = p.cpu().double()
+        assert torch.isfinite(p).all(), name
+        print("%s H=%d B=%d mask=%d dout=%d: max |part - float64| / (2e-6 sum|terms|) = %.3g, float32 restatement %.3g" % (
+            name, H, B, mask, use_dout, float(((p - r_part).abs() / (2e-6 * r_abs + 1e-30)).max()), f32))
+        np.testing.assert_array_less((p - r_part).abs().numpy(), (factor * 2e-6 * r_abs + 1e-30).numpy(), err_msg=name)
+        np.testing.assert_array_less((p - terms.sum(1)).abs().numpy(), (2e-6 * r_abs + 1e-30).numpy(), err_msg=name)
+    np.testing.assert_array_equal(acc_b.cpu().numpy(), acc_g.cpu().numpy())
+    np.testing.assert_array_equal(part_b.cpu().numpy(), part_g.cpu().numpy())
+    gg = gg.cpu()
+    np.testing.assert_array_equal(gg[:, H:3 * H].numpy(), dgi.cpu()[:, :2 * H].numpy())    # dr | dz
+    np.testing.assert_array_equal(gg[:, :H].numpy(), dgi.cpu()[:, 2 * H:].numpy())         # dn
+    np.testing.assert_array_equal(gg[:, H:].numpy(), dgh.cpu().numpy())                    # dr | dz | dhn
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("H", [64, 100, 256])
+@pytest.mark.parametrize("rows", [1, 63, 64, 65, 1000])
+def test_bias_reduce_vs_fp64(rows, H):
+    """cn_gru_bias_reduce on random partials vs the float64 column sums mapped to db_ih = (dr, dz, dn) and
+    db_hh = (dr, dz, dhn): rows below, at and above its 64 row chunks; 2e-6 * sum|terms| per entry."""
+    _lib, L, st = _lib_stream()
+    part = torch.randn(rows, 4 * H, generator=torch.Generator().manual_seed(rows + H))
+    s, a = part.double().sum(0), part.double().abs().sum(0)
+    d_part, db_ih, db_hh = part.to(DEV), _nan(3 * H), _nan(3 * H)
+    work = _nan(int(L.cn_gru_bias_work_elems(H)))
+    _lib.check(L.cn_gru_bias_reduce(st, rows, H, d_part.data_ptr(), db_ih.data_ptr(), db_hh.data_ptr(),
+                                    work.data_ptr()))
+    torch.cuda.synchronize()
+    for name, got, sel in (("db_ih", db_ih, slice(0, 3 * H)),
+                           ("db_hh", db_hh, np.r_[0:2 * H, 3 * H:4 * H])):
+        got = got.cpu().double()
+        assert torch.isfinite(got).all(), name
+        np.testing.assert_array_less((got - s[sel]).abs().numpy(), (2e-6 * a[sel] + 1e-30).numpy(), err_msg=name)
+
+
+# ---- 7. the policy at non-default sizes -------------------------------------------------------------------
+SIZES = dict(human_node_rnn_size=96, human_human_edge_rnn_size=128)
+
+
+def _sized_policy_results(d, dev, N=5):
+    """act (no-grad, then the autograd T = 1 path) and evaluate_actions of a policy with SIZES on the dsrnn.npz
+    observations / masks / actions and seeded random states of the new widths: 13 arrays."""
+    from tests import helpers
+    from tests.test_policy import _obs
+
+    def hxs(p):
+        out = {}
+        for k, hs in (("human_node_rnn", 96), ("human_human_edge_rnn", 128)):
+            shape = d[p + "hxs_" + k].shape[:-1] + (hs,)
+            out[k] = (torch.randn(shape, generator=torch.Generator().manual_seed(hs + len(p))) * 0.5).to(dev)
+        return out
+
+    pol = helpers.make_policy(N, device=dev, **SIZES)
+    assert pol.base.humanNodeRNN.gru.weight_hh_l0.shape == (3 * 96, 96)
+    assert pol.base.humanhumanEdgeRNN_spatial.gru.weight_hh_l0.shape == (3 * 128, 128)
+    res = []
+    p = "N%d_act_" % N
+    masks = torch.from_numpy(d[p + "masks"]).to(dev)
+    for grad in (False, True):
+        with torch.set_grad_enabled(grad):
+            v, a, lp, nh = pol.act(_obs(d, p + "obs_", dev), hxs(p), masks, deterministic=True)
+        res += [v, a, lp, nh["human_node_rnn"], nh["human_human_edge_rnn"]]
+    p = "N%d_ev_" % N
+    with torch.no_grad():
+        v, lp, ent, _ = pol.evaluate_actions(_obs(d, p + "obs_", dev), hxs(p),
+                                             torch.from_numpy(d[p + "masks"]).to(dev),
+                                             torch.from_numpy(d[p + "actions"]).to(dev))
+    res += [v, lp, ent.reshape(1)]
+    return [t.detach().cpu().numpy() for t in res]
+
+
+def _patch_ops_with_restatements(mp):
+    from crowdnav_dsrnn_amd import ops
+    from tests import helpers
+
+    mp.setattr(ops, "edge_features", helpers.edge_features_fp32)
+    mp.setattr(ops, "masked_gru", helpers.masked_gru_ref)
+    mp.setattr(ops, "gru_infer_step", helpers.gru_infer_step_ref)
+    mp.setattr(ops, "attention_pool", helpers.attention_pool_ref)
+
+
+def test_sized_policy_cpu_restatement_paths_agree(monkeypatch):
+    """The CPU side of the comparison below, on its own: with the restatements in place the no-grad act() step
+    and the autograd T = 1 path of the resized policy give the same values, actions and states."""
+    from tests import helpers
+    from tests.test_policy import ATOL, RTOL
+
+    _patch_ops_with_restatements(monkeypatch)
+    res = _sized_policy_results(helpers.load("dsrnn.npz"), "cpu")
+    assert len(res) == 13 and all(np.isfinite(r).all() for r in res)
+    assert res[3].shape[-1] == 96 and res[4].shape[-1] == 128
+    for a, b in zip(res[:5], res[5:10]):
+        np.testing.assert_allclose(a, b, atol=ATOL, rtol=RTOL)
+
+
+@pytest.mark.gpu
+def test_policy_at_non_default_sizes_gpu_vs_cpu(monkeypatch):
+    """act (no-grad and autograd T = 1 paths) and evaluate_actions with human_node_rnn_size = 96 and
+    human_human_edge_rnn_size = 128 on the GPU vs the same module on the CPU with ops replaced by the plain
+    restatements (as test_policy_graph_cpu_with_fp32_input_layers does); ATOL, RTOL of test_policy.py."""
+    from tests import helpers
+    from tests.test_policy import ATOL, RTOL
+
+    d = helpers.load("dsrnn.npz")
+    with monkeypatch.context() as mp:
+        _patch_ops_with_restatements(mp)
+        want = _sized_policy_results(d, "cpu")
+    got = _sized_policy_results(d, DEV)
+    assert len(got) == len(want) == 13
+    for k, (a, b) in enumerate(zip(got, want)):
+        assert a.shape == b.shape
+        np.testing.assert_allclose(a, b, atol=ATOL, rtol=RTOL, err_msg="result %d" % k)
+
+
+# ---- CPU: the references themselves, and ops.wgrad's split-K branch ---------------------------------------
+def test_step_restatements_agree_with_autograd_and_gru_cell():
+    """The one-step float64 restatements the GPU tests compare against are themselves right: the forward equals
+    torch.gru_cell and the backward equals autograd through it."""
+    g = torch.Generator().manual_seed(3)
+    B, F, H = 9, 5, 12
+    x = torch.randn(B, F, generator=g, dtype=torch.float64)
+    hm = torch.randn(B, H, generator=g, dtype=torch.float64).requires_grad_(True)
+    w_ih, w_hh = torch.randn(3 * H, F, generator=g, dtype=torch.float64), torch.randn(3 * H, H, generator=g, dtype=torch.float64)
+    b_ih, b_hh = torch.randn(3 * H, generator=g, dtype=torch.float64), torch.randn(3 * H, generator=g, dtype=torch.float64)
+    m = (torch.rand(B, generator=g) > 0.5).double()
+    acc, dout = torch.randn(B, H, generator=g, dtype=torch.float64), torch.randn(B, H, generator=g, dtype=torch.float64)
+    gi = (x @ w_ih.t() + b_ih).requires_grad_(True)
+    gh = hm @ w_hh.t() + b_hh
+    gh.retain_grad()
+    h, hmn, save = gru_step_fwd_ref(gi, gh, hm, m)
+    np.testing.assert_allclose(h.detach().numpy(), torch.gru_cell(x, hm, w_ih, w_hh, b_ih, b_hh).detach().numpy(),
+                               atol=1e-14, rtol=0)
+    np.testing.assert_array_equal(hmn.detach().numpy(), (h * m.unsqueeze(-1)).detach().numpy())
+    ((hmn * acc).sum() + (h * dout).sum()).backward()
+    a, dgi, dgh = gru_step_bwd_ref(acc, m, dout, save.detach(), hm.detach())
+    np.testing.assert_allclose(dgi.numpy(), gi.grad.numpy(), atol=1e-13, rtol=0)
+    np.testing.assert_allclose(dgh.numpy(), gh.grad.numpy(), atol=1e-13, rtol=0)
+    np.testing.assert_allclose((a + dgh @ w_hh).numpy(), hm.grad.numpy(), atol=1e-13, rtol=0)   # dL/dhm
+
+
+@pytest.mark.parametrize("K", [255, 256, 300, 333, 1000])
+def test_wgrad_split_k_branch_on_cpu(K):
+    """ops.wgrad with chunk = 64 on CPU tensors: the plain branch (K 255: S < 4), exact chunks (256, 300) and a
+    remainder (333, 1000), on the row-strided column slices g2[:, :3H] / g2[:, H:] of one (K, 4H) buffer that the
+    GRU backward passes; vs the float64 dy^T x with test_wgrad_kernel_vs_fp64's bound 2e-6 * |dy|^T |x|."""
+    from crowdnav_dsrnn_amd import ops
+
+    H, F, chunk = 8, 5, 64
+    S = K // chunk
+    assert (S < 4) == (K == 255) and (S >= 4 and S * (K // S) < K) == (K in (333, 1000))
+    g = torch.Generator().manual_seed(K)
+    g2 = torch.randn(K, 4 * H, generator=g)
+    x, hm = torch.randn(K, F, generator=g), torch.randn(K, H, generator=g)
+    for dy, xx in ((g2[:, :3 * H], x), (g2[:, H:], hm)):
+        assert not dy.is_contiguous()
+        got = ops.wgrad(dy, xx, chunk=chunk).double()
+        ref, bound = dy.double().t() @ xx.double(), dy.double().abs().t() @ xx.double().abs()
+        assert got.shape == ref.shape
+        np.testing.assert_array_less((got - ref).abs().numpy(), (2e-6 * bound + 1e-30).numpy())

@@ -10,8 +10,8 @@ import numpy as np
 import pytest
 import torch
 
-from tests.helpers import (attention_pool_ref, edge_features_fp32, gru_infer_step_ref, masked_gru_ref, load,
-                           make_policy)
+from tests.helpers import (attention_pool_ref, edge_features_fp32, gru_form_rows, gru_infer_step_ref, gru_row_tile,
+                           masked_gru_ref, load, make_policy)
 
 ATOL, RTOL = 2e-5, 1e-4
 
@@ -157,18 +157,39 @@ def test_edge_features_backward_vs_fp32():
         np.testing.assert_allclose(y.grad.cpu().numpy(), x.grad.numpy(), atol=1e-4, rtol=1e-4)
 
 
+def _B_hi(H):
+    """The smallest total row count that runs the 128-row kernels at H on this device, + 40 (ragged last tile)."""
+    return gru_form_rows(H, torch.cuda.get_device_properties(0).multi_processor_count)[0]
+
+
+# the row tile each (total rows, H) of the tests below runs on the MI355X's 256 CUs: 128-row tiles need
+# ceil(rows / 128) * (H / 32) >= 256 workgroups. Asserted, so a CU-count or threshold change fails instead of
+# silently moving what these shapes cover: on a device with another CU count this table has to be edited (and the
+# docstrings below with it); the "hi" cases and tests/test_gru_forms.py derive their rows from the device.
+_TILE = {(45, 256): 32, (33, 256): 32, (70, 128): 32, (1000, 64): 32, (3000, 256): 32, (40, 64): 32, (9000, 256): 128,
+         (345, 256): 32, (130, 128): 32, (22528, 256): 128, (384, 64): 32}
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("T,B,F,H", [(1, 45, 64, 256), (9, 33, 64, 256), (16, 70, 128, 128), (3, 1000, 32, 64),
-                                     (4, 50, 16, 36), (5, 3000, 48, 256), (3, 40, 16, 64), (4, 9000, 64, 256)])
+                                     (4, 50, 16, 36), (5, 3000, 48, 256), (3, 40, 16, 64), (4, 9000, 64, 256),
+                                     (5, "hi", 48, 256)])
 def test_masked_gru_kernels_vs_fp64(T, B, F, H):
     """ops.masked_gru vs the plain torch restatement of the mask-segmented GRU (srnn_model.py:52-104) in
     float64: outputs, final state and every input / weight gradient, with episode starts at step 0 and
-    mid-sequence. Covers the sequence kernels' four forms -- 128-row tiles (>= 256 workgroups: B 3000 / 9000
-    at H 256) and split-K 32-row tiles, each with the input projection in the kernel (F % 32 == 0) or a gi
-    GEMM first (F 48 / 16) -- and the per-step path (H 36). fp32 GEMM/transcendental rounding: atol 2e-5
-    (outputs), 1e-4 x scale (gradients)."""
+    mid-sequence. Forms these shapes run on 256 CUs (asserted): split-K 32-row tiles with the input projection
+    in the kernel (F % 32 == 0: B 45 / 33 / 70 / 1000) or a gi GEMM first (B 3000 at F 48 -- 24 x 8 = 192
+    workgroups of 128 rows, below 256 -- and B 40 at F 16); 128-row tiles with the projection in the kernel
+    (B 9000) and with a gi GEMM (B "hi": the smallest row count on 128-row tiles + 40, 4009 at 256 CUs); and the
+    per-step path (H 36). tests/test_gru_forms.py covers the forms x sizes systematically. fp32
+    GEMM/transcendental rounding: atol 2e-5 (outputs), 1e-4 x scale (gradients)."""
     from crowdnav_dsrnn_amd import ops
 
+    if B == "hi":
+        B = _B_hi(H)
+        assert gru_row_tile(B, H) == 128
+    elif H % 32 == 0:
+        assert gru_row_tile(B, H) == _TILE[(B, H)]
     g = torch.Generator().manual_seed(T * 1000 + B)
     x = torch.randn(T, B, F, generator=g)
     h0 = torch.randn(B, H, generator=g) * 0.5
@@ -207,14 +228,21 @@ def _gru_case(g, T, B, F, H):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("T,Bs,F,H", [(9, (300, 45), 64, 256), (3, (1, 129), 64, 128), (17, (2048 * 10, 2048), 64, 256),
-                                      (2, (128, 256), 32, 64)])
+                                      (2, (128, 256), 32, 64), (3, ("hi", 77), 48, 256)])
 def test_masked_gru_group_vs_fp64(T, Bs, F, H):
     """ops.masked_gru_group (two GRUs in shared cn_gru_fwd_seq / cn_gru_bwd_seq launches: the spatial and
     temporal edge RNNs) vs the float64 restatement of each GRU on its own: outputs, final states and every
-    gradient of both. Ragged row tiles on either side of the boundary (1, 129, 45) and C4's minibatch shape
-    (20,480 + 2,048 rows). Tolerances as test_masked_gru_kernels_vs_fp64."""
+    gradient of both. Ragged row tiles on either side of the boundary (1, 129, 45), all split-K on 256 CUs
+    (the total rows decide), and on 128-row tiles C4's minibatch shape (20,480 + 2,048 rows, projection in the
+    kernel) and ("hi", 77): the smallest total on 128-row tiles + 40, split (B - 77, 77), with a gi GEMM
+    (F 48). The form of each is asserted. Tolerances as test_masked_gru_kernels_vs_fp64."""
     from crowdnav_dsrnn_amd import ops
 
+    if Bs[0] == "hi":
+        Bs = (_B_hi(H) - Bs[1], Bs[1])
+        assert gru_row_tile(Bs, H) == 128
+    else:
+        assert gru_row_tile(Bs, H) == _TILE[(sum(Bs), H)]
     g = torch.Generator().manual_seed(T * 7 + Bs[0])
     cases = [_gru_case(g, T, B, F, H) for B in Bs]
 
@@ -278,26 +306,30 @@ def test_masked_gru_seq_matches_per_step_path():
     (hipBLASLt gi = x W_ih^T + b_ih, then cn_gru_fwd_fused per step; cn_gru_bwd_step_gates + a library GEMM
     per step) on the same fp32 operands. The sequence forward accumulates x W_ih^T with hm W_hh^T in the
     step kernel and the backward's recurrent GEMM sums in another order: only the summation order differs
-    (atol 2e-6 on the outputs, 2e-5 x scale on the gradients)."""
+    (atol 2e-6 on the outputs, 2e-5 x scale on the gradients). B = 3000 is split-K on 256 CUs (192 workgroups
+    of 128 rows); the derived row count (4009 at 256 CUs) runs the 128-row kernels, with the projection in the
+    kernel (F 64) and with a gi GEMM (F 48). Forms asserted."""
     from crowdnav_dsrnn_amd import ops
 
-    g = torch.Generator().manual_seed(5)
-    T, B, F, H = 12, 3000, 64, 256
-    x, h0, masks, ws, dout, dhT = _gru_case(g, T, B, F, H)
+    H = 256
+    for T, B, F, tile in ((12, 3000, 64, _TILE[(3000, 256)]), (12, _B_hi(H), 64, 128), (5, _B_hi(H), 48, 128)):
+        assert gru_row_tile(B, H) == tile
+        g = torch.Generator().manual_seed(5)
+        x, h0, masks, ws, dout, dhT = _gru_case(g, T, B, F, H)
 
-    def run(fn):
-        lv = [t.cuda().requires_grad_(True) for t in (x, h0, *ws)]
-        out, hT = fn(lv[0], lv[1], masks.cuda(), *lv[2:])
-        ((out * dout.cuda()).sum() + (hT * dhT.cuda()).sum()).backward()
-        return [out.detach(), hT.detach()] + [l.grad for l in lv]
+        def run(fn):
+            lv = [t.cuda().requires_grad_(True) for t in (x, h0, *ws)]
+            out, hT = fn(lv[0], lv[1], masks.cuda(), *lv[2:])
+            ((out * dout.cuda()).sum() + (hT * dhT.cuda()).sum()).backward()
+            return [out.detach(), hT.detach()] + [l.grad for l in lv]
 
-    got = run(ops.masked_gru)
-    ref = run(ops._MaskedGRU.apply)
-    for n, a, b in zip(["out", "hT"], got[:2], ref[:2]):
-        np.testing.assert_allclose(a.cpu().numpy(), b.cpu().numpy(), atol=2e-6, rtol=0, err_msg=n)
-    for n, a, b in zip(["dx", "dh0", "dW_ih", "dW_hh", "db_ih", "db_hh"], got[2:], ref[2:]):
-        np.testing.assert_allclose(a.cpu().numpy(), b.cpu().numpy(), atol=2e-5 * max(1.0, float(b.abs().max())),
-                                   rtol=0, err_msg=n)
+        got = run(ops.masked_gru)
+        ref = run(ops._MaskedGRU.apply)
+        for n, a, b in zip(["out", "hT"], got[:2], ref[:2]):
+            np.testing.assert_allclose(a.cpu().numpy(), b.cpu().numpy(), atol=2e-6, rtol=0, err_msg="%s B=%d F=%d" % (n, B, F))
+        for n, a, b in zip(["dx", "dh0", "dW_ih", "dW_hh", "db_ih", "db_hh"], got[2:], ref[2:]):
+            np.testing.assert_allclose(a.cpu().numpy(), b.cpu().numpy(), atol=2e-5 * max(1.0, float(b.abs().max())),
+                                       rtol=0, err_msg="%s B=%d F=%d" % (n, B, F))
 
 
 @pytest.mark.gpu
