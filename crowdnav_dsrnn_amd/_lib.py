@@ -110,6 +110,9 @@ def lib():
                                      vp]
     L.cn_debug_set_spawn_budget.argtypes = [vp, ctypes.c_longlong]
     L.cn_debug_spawn_stats.argtypes = [vp, vp]
+    if hasattr(L, "cn_debug_set_seq_chunk") or not os.environ.get("CN_LIB_PATH"):   # (an older A/B library lacks it)
+        L.cn_debug_set_seq_chunk.argtypes = [vp, ctypes.c_int]
+        L.cn_debug_set_seq_chunk.restype = i32
     L.cn_social_force_predict.argtypes = [vp, i64, ctypes.c_int, vp, vp] + [ctypes.c_double] * 4 + [vp]
     L.cn_gru_bwd_step.argtypes = [vp, i64, ctypes.c_int] + [vp] * 7
     L.cn_lidar_obs.argtypes = [vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, vp, vp]
@@ -195,4 +198,4 @@ EXPORTED = ["cn_last_error", "cn_version", "cn_config_validate", "cn_create", "c
             "cn_gru_bwd_seq_work_elems", "cn_gru_fwd_step_group", "cn_gru_fwd_seq", "cn_gru_bwd_seq", "cn_gaussian_act", "cn_gae",
             "cn_set_graph_mode", "cn_graph_node_counts", "cn_lidar_obs", "cn_lidar_scan", "cn_debug_disc_quad",
             "cn_debug_orca", "cn_debug_copy64", "cn_orca_predict", "cn_orca_predict_kd", "cn_social_force_predict",
-            "cn_debug_set_spawn_budget", "cn_debug_spawn_stats"]
+            "cn_debug_set_spawn_budget", "cn_debug_spawn_stats", "cn_debug_set_seq_chunk"]

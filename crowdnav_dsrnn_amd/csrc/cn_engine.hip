@@ -87,7 +87,7 @@ struct StepPlan {
     int kd;      // A > 10: RVO2's KdTree order decides ties between equally distant neighbours
     // LDS byte offsets
     int o_renv, o_racts, o_rflag, o_rvr, o_hum, o_lane, o_orad, o_vis, o_nv, o_eg, o_lines, o_proj, o_nd, o_ns, o_perm,
-        o_hvr, o_hst, o_l3b, o_l3r, o_l3k,
+        o_hvr, o_hst, o_l3b, o_l3r, o_l3k, o_app,
         total;
     int rng_waves;   // phase-5 RNG regions (rng_stride bytes each), laid over o_lines
     int rng_stride;  // CN_PEND_LDS, + CN_GRID_LDS when the plan has room for the spawn's DiscGrid
@@ -123,6 +123,12 @@ struct StepPlan {
 #endif
 #ifndef CN_RNG_PRIO_ALL
 #define CN_RNG_PRIO_ALL 0   // diagnostic: raise the RNG waves' priority on the quad path too
+#endif
+#ifndef CN_SEQ_CHUNK
+// steps per launch of cn_step_seq (cn_debug_set_seq_chunk; 1: one cn_step launch per step). C2 sweep, us per step
+// of the steady window: 1: 38.7, 4: 33.9, 8: 32.0, 16: 30.9, 32: 29.9, 64: 29.6 but with resets that no longer
+// find their spawn drawn (a spawn queued in one launch is drawn by the next: > 1 inline draw per step at 64)
+#define CN_SEQ_CHUNK 32
 #endif
 #define CN_GRID 16
 #define CN_GRID_LDS (96 * 8 + CN_GRID * CN_GRID * 4 + 4 * 8 + 4 * 8)   // + spawn DiscGrid: agent table, masks, cover, box
@@ -188,6 +194,10 @@ __host__ __device__ inline StepPlan cn_step_plan(int N, int robot_visible)
     p.rng_stride = p.o_lines + p.rng_waves * (CN_PEND_LDS + CN_GRID_LDS) <= o ? CN_PEND_LDS + CN_GRID_LDS : CN_PEND_LDS;
     const int rng_end = p.o_lines + p.rng_waves * p.rng_stride;
     p.total = o > rng_end ? o : rng_end;
+    // multi-step launches: the spawn-list entries a workgroup holds for its envs (SL::app), kept across the steps,
+    // so behind everything a step lays out (no other offset moves)
+    p.o_app = p.total;
+    p.total = cn_align16(p.total + 2 * p.EPB * 4);
     return p;
 }
 
@@ -197,6 +207,7 @@ struct SL {
     double *r;        // [CN_RENV_F][EPB]
     float *act;       // [2][EPB] clipped action (holonomic vx,vy / unicycle v,r)
     uint32_t *rflag;  // [EPB] flags ; [EPB] aux ; [EPB] humans the reward loop visited (first collision + 1)
+    uint32_t *app;    // [EPB][2] multi-step launches: the env's spawn-list entry of each key parity (index + 1; 0: none)
     double *rvr;      // [8][EPB] robot VelocityRectangle corners
     double *hvr;      // [8][H] human VelocityRectangle corners (x0..x3, y0..y3)
     double *hst;      // [7][H] human_post's results (vx, vy, belief px, py, vx, vy, r), stored after phase 2
@@ -2248,6 +2259,16 @@ __device__ __forceinline__ void reset_env(const ResetOut &o, const PendPtrs &P2,
     // FOR THIS KEY is consumed, and no wave of this launch writes such a slot (a slot is rewritten for key rc + 2
     // only after this reset; a spawn of key rc that is written for the first time in this very launch shows the
     // key in its ok word only with id 0 or this launch's), so the payload read after it needs no fence.
+    // Multi-step launches (an env may reset several times in one launch, at keys rc, rc + 1, rc + 2, ...): the same
+    // holds. The spawn waves of launch L write, per env and slot parity, at most one item: the one entry the env's
+    // workgroup kept in launch L - 1's list (cn_step_kernel, phase 5) or a spawn parked by L - 1, never both live
+    // (a parked spawn of key K is dropped once reset_count > K, and an entry of its parity queued in L - 1 comes
+    // from a reset at a key >= K, after which reset_count > K). An item written in L has a key K' <= rc for a
+    // reset at key rc of L itself (it was queued by a reset at K' - 2 of an earlier launch, and keys only grow);
+    // K' == rc shows this launch's id or 0, K' < rc another key: neither is consumed, and an entry that IS
+    // consumed (key rc, completed by an earlier launch) has no writer in L, because the one item of its parity
+    // alive in L would have to carry a key > rc. So no two waves of a launch write one slot, a slot consumed in L
+    // is rewritten in L + 1 at the earliest, and a reset consumes only what an earlier launch completed for its key.
     const uint64_t okw = P.ok[e];
     const uint32_t ok = (uint32_t)okw;
     if (FENCE) __threadfence();
@@ -2309,7 +2330,11 @@ struct PendLaunch {
 // is spent (stream, robot and humans so far go to the pending slot, the item to rlist_w) and parks the
 // items it has not started; a later launch resumes them. The pending slot of a spawn is written only by
 // the wave that owns the item, and a reset consumes an entry only if an EARLIER launch completed it.
-template <bool PHX, bool GRID, bool PARK = GRID>
+// RESUME_FIRST (multi-step launches): the parked spawns come before the new items. A multi-step launch reads the
+// entries of a whole chunk of steps, many more than there are spawning waves; with the new items first, every
+// wave's first item (the one it works on whatever the budget) would be a new one, and under a small budget the
+// parked spawns, which are the older ones and needed sooner, would be parked again in every launch until stale.
+template <bool PHX, bool GRID, bool PARK = GRID, bool RESUME_FIRST = false>
 __device__ __forceinline__ void pend_waves(const PendLaunch &pl, const cn_state_ptrs &S, const cn_config &c, int E, char *smem)
 {
     const int nw = pl.waves, w = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -2328,7 +2353,13 @@ __device__ __forceinline__ void pend_waves(const PendLaunch &pl, const cn_state_
     const int pb = pl.first ? (int)blockIdx.x : (int)blockIdx.x - pl.step_blocks;
     const long long deadline = (PARK && pl.budget) ? (long long)clock64() + pl.budget : 0;
     bool worked = false;   // a wave always works on its first item of the launch (progress for any budget)
-    for (uint32_t it = (uint32_t)(pb * nw + w); it < nnew + nres; it += (uint32_t)(pl.pend_blocks * nw)) {
+    for (uint32_t it0 = (uint32_t)(pb * nw + w); it0 < nnew + nres; it0 += (uint32_t)(pl.pend_blocks * nw)) {
+        uint32_t it = it0;   // item: [0, nnew) the new ones, [nnew, nnew + nres) the parked ones
+        if constexpr (RESUME_FIRST) {   // the same list, rotated to start at the parked spawns
+            it = it0 + nnew;
+            if (it >= nnew + nres) it -= nnew + nres;
+            it = (uint32_t)__builtin_amdgcn_readfirstlane((int)it);   // wave-uniform: the entries stay scalar loads
+        }
         int64_t e, cc;
         int32_t rc;
         bool started = false;
@@ -2353,7 +2384,9 @@ __device__ __forceinline__ void pend_waves(const PendLaunch &pl, const cn_state_
             // its reset has come and gone (drawn inline). reset_count may be advanced by a reset of this same
             // launch while it is read; either value is safe: such a reset draws inline (the parked entry is not
             // complete), so the item only turns stale, and the next writer of its slot (key rc + 2, queued by
-            // that reset) belongs to the next launch, stream-ordered after this item's stores
+            // that reset) belongs to the next launch, stream-ordered after this item's stores.
+            // (multi-step launches: several resets of the env may follow in this launch; they queue one entry per
+            // slot parity, for the next launch, and reset_count only grows, so the item stays stale)
             if (rc < S.reset_count[e]) continue;
         }
         if (deadline && worked && (long long)clock64() > deadline) {   // out of budget: park the item unstarted / as is
@@ -2442,19 +2475,28 @@ struct StepArgs {
     // spawn, [CN_CTL_DONE] finished workgroups; the last workgroup of a launch advances them), so a launch
     // has no per-call arguments and a sequence of cn_step calls can be captured in a hipGraph and replayed;
     // the pointers below are then derived at the top of the kernel. Otherwise the host passes them.
-    uint32_t *ctl;
-    uint32_t *plist_base;   // [3][E + 64][4] spawn lists: {env, reset_count, case_counter lo, hi} after the reset
+    // Multi-step launches (the SEQ kernels, cn_step_seq; never in graph mode) keep their two arguments where the
+    // struct has room, so that its size and every other member's place in the kernarg segment stay what the
+    // single-step kernels were tuned with: the stride shares ctl's slot, nsteps fills the padding behind E.
+    union {
+        uint32_t *ctl;
+        int64_t action_stride;   // SEQ: step t takes the actions at actions + t * action_stride
+    };
+    uint32_t *plist_base;  // [3][E + 64][4] spawn lists: {env, reset_count, case_counter lo, hi} after the reset
     uint32_t *rlist_base;   // [3][2E + 64][4] parked-spawn lists
-    uint32_t *plist_w;      // envs reset by this launch (their next spawn is drawn by the next launch)
+    uint32_t *plist_w;      // envs reset by this launch (their next spawn is drawn by the next launch); a multi-step
+                            // launch keeps one entry per env and slot parity, the first E of them
     uint32_t *pcount_w;
     uint32_t *pcount_zero;  // the counter the NEXT launch appends to (triple-buffered), zeroed here
     uint32_t *rcount_zero;  // likewise for the parked-spawn list
     PendLaunch pend;        // spawn waves: the first or the last pend_blocks workgroups (pend.first)
     int64_t case_size;
     int E;
+    int nsteps;             // SEQ: steps a step workgroup runs in this launch
     OutView ov;             // output rows / human stride (mixed engines); also pend.ov
     double cth_h, cth_r;    // cos(human_fov / 2), cos(robot_fov / 2): in_fov's thresholds
 };
+static_assert(sizeof(StepArgs) == 720, "StepArgs: the kernarg layout of the single-step kernels");
 
 // phase 5 reads cn_config from the kernarg segment right after StepArgs (cn_step_kernel's RNG loop): the
 // by-value arguments are laid out in order at their natural alignment (AMDHSA metadata: 0 / 720 today)
@@ -2497,7 +2539,14 @@ __device__ inline float bbox_dist(float x, float y, float mnx, float mxx, float 
 // MIX: a group of a mixed engine (outputs through g.ov); a plain engine's identity view is then a
 // compile-time constant and costs no registers
 // DEVSEQ: graph mode (StepArgs::devseq), a variant of its own so the default launches carry none of it
-template <bool KD, bool PHX, bool MIX, bool DEVSEQ = false>
+// SEQ: a multi-step launch (cn_step_seq's chunks): the step workgroups run g.nsteps steps of their own envs
+// back to back (phases 0-5 in a loop, a workgroup barrier between steps), the spare workgroups draw spawns once
+// per launch as ever. Envs are independent and belong to one workgroup for the whole launch, so no workgroup
+// waits for another one: a slow step (a random-goal rejection, a reset next to goal changes on one wave) delays
+// its own workgroup only, and over a chunk the workgroups' totals even out. Every step reads the state the
+// previous one wrote through global memory (written by other waves of the same workgroup: visible after the
+// barrier) and re-initialises every LDS word and register it uses, exactly as a launch of its own would.
+template <bool KD, bool PHX, bool MIX, bool DEVSEQ = false, bool SEQ = false>
 __global__ void __launch_bounds__(CN_BLK, 3) cn_step_kernel(StepArgs g, cn_config c)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -2548,7 +2597,7 @@ __global__ void __launch_bounds__(CN_BLK, 3) cn_step_kernel(StepArgs g, cn_confi
     if (sb < 0 || sb >= g.pend.step_blocks) {  // spare workgroups: draw upcoming episodes' spawns
         PendLaunch pl = g.pend;
         pl.ov = ov;
-        pend_waves<PHX, KD, KD || CN_QUAD_PARK>(pl, g.s, c, g.E, smem);
+        pend_waves<PHX, KD, KD || CN_QUAD_PARK, SEQ>(pl, g.s, c, g.E, smem);
         finish();
         return;
     }
@@ -2560,6 +2609,7 @@ __global__ void __launch_bounds__(CN_BLK, 3) cn_step_kernel(StepArgs g, cn_confi
     sl.r = (double *)(smem + P.o_renv);
     sl.act = (float *)(smem + P.o_racts);
     sl.rflag = (uint32_t *)(smem + P.o_rflag);
+    sl.app = (uint32_t *)(smem + P.o_app);
     sl.rvr = (double *)(smem + P.o_rvr);
     sl.hvr = (double *)(smem + P.o_hvr);
     sl.hst = (double *)(smem + P.o_hst);
@@ -2588,14 +2638,24 @@ __global__ void __launch_bounds__(CN_BLK, 3) cn_step_kernel(StepArgs g, cn_confi
         return KD ? ((double *)(sl.proj + hh * M))[f] : sl.hst[f * 64 + hh];
     };
 
-    const int tid = threadIdx.x;
+    // SEQ: the spawn-list entry (index + 1; 0: none yet) this launch holds for each env and key parity (phase 5)
+    if constexpr (SEQ) { if ((int)threadIdx.x < 2 * EPB) sl.app[threadIdx.x] = 0u; }
+    int step = 0;
+    do {   // one pass without SEQ: the condition folds and the single-step kernels compile as without the loop
+           // (the body keeps the single step's indentation)
+    int tid = threadIdx.x, sbk = sb;
+    // SEQ: the lane and workgroup indices are opaque in every step, so that nothing derived from them (the ~40
+    // per-lane state addresses above all) is step-invariant: hoisted out of the loop they stayed live across
+    // the whole step (292 VGPRs spilled to scratch); now every step computes them at their uses, as a launch of
+    // its own does
+    if constexpr (SEQ) { asm volatile("" : "+v"(tid)); asm volatile("" : "+s"(sbk)); }
     // XCD-aware env placement: workgroup i runs on XCD i % 8 (round-robin dispatch; for speed only), so
     // give each XCD a contiguous run of env blocks. Neighbouring workgroups share the 128-B lines at the
     // ends of their SoA segments (a per-env field of one workgroup is only 48 B); on one XCD the second
     // reader hits in that XCD's L2 instead of fetching the line again.
     // (a leading pend_blocks is a multiple of 8, so step workgroup sb runs on XCD sb % 8 as well)
-    const int nbk = g.pend.step_blocks, xq = nbk >> 3, xr = nbk & 7, xi = sb & 7;
-    const int blk = xi * xq + min(xi, xr) + (sb >> 3);
+    const int nbk = g.pend.step_blocks, xq = nbk >> 3, xr = nbk & 7, xi = sbk & 7;
+    const int blk = xi * xq + min(xi, xr) + (sbk >> 3);
     const int e0 = blk * EPB;
     const int nenv_here = min(EPB, g.E - e0);
     const int el = tid / N, i = tid - el * N;
@@ -2609,6 +2669,8 @@ __global__ void __launch_bounds__(CN_BLK, 3) cn_step_kernel(StepArgs g, cn_confi
     const bool holo = c.kinematics == CN_HOLONOMIC;
     const double dt = c.time_step;
 
+    const float *actions = g.actions;
+    if constexpr (SEQ) actions += (int64_t)step * g.action_stride;
     STAMP_A(0);
     // ---- phase 0: load state into LDS -----------------------------------------------------------
     // values needed in later phases are loaded here, so their latency overlaps phase 0 (doubles parked
@@ -2649,7 +2711,7 @@ __global__ void __launch_bounds__(CN_BLK, 3) cn_step_kernel(StepArgs g, cn_confi
         const uint32_t fl = S.flags[ge];
         pre_epl = S.ep_len[ge]; pre_sc = S.scenario[ge]; pre_ovf = S.overflow[ge];
         const int64_t oa = orow(ov, ge);   // the env's row in the caller's buffers
-        float a0 = g.actions[oa * 2], a1 = g.actions[oa * 2 + 1];
+        float a0 = actions[oa * 2], a1 = actions[oa * 2 + 1];
         asm volatile("" ::: "memory");
         RF(sl, R_PX, re, EPB) = rv[R_PX]; RF(sl, R_PY, re, EPB) = rv[R_PY];
         RF(sl, R_GX, re, EPB) = rv[R_GX]; RF(sl, R_GY, re, EPB) = rv[R_GY];
@@ -3499,13 +3561,30 @@ __global__ void __launch_bounds__(CN_BLK, 3) cn_step_kernel(StepArgs g, cn_confi
                 const bool may = g.pend.all != PEND_BOTH;   // ready unless this launch redraws both
                 reset_env<KD, (KD || CN_QUAD_PARK) && CN_SLOT_FENCE>(o, G.pend.P, C, G.E, e, G.pend.counter_offset, may,
                                                                      g.pend.launch_id, m, en, G.pend.stats + 7);
-                if (lane == 0) {   // each env resets at most once per launch: k < E (guarded all the same)
+                if (lane == 0) {
                     // the entry carries the counters this reset just wrote (its own stores, read back), so the
                     // next launch's spawn wave keys the spawn after next from them, never from a state that a
-                    // later reset of the same env may be rewriting while it reads
+                    // later reset of the same env may be rewriting while it reads.
+                    // A single-step launch resets an env at most once: at most E entries (k < E guarded all the
+                    // same). A multi-step launch may reset an env several times, at keys rc, rc + 1, rc + 2, ...;
+                    // their entries (spawns rc + 2, rc + 3, rc + 4, ...) would have spawns two keys apart share
+                    // a pending slot and be written by two waves of the next launch. So the launch holds ONE
+                    // entry per env and slot parity: a later reset of the same parity overwrites the entry its
+                    // workgroup appended (sl.app: its index, kept across the steps; the list is read by the next
+                    // launch only), which also keeps the key most likely to be needed. An entry that did not fit
+                    // the list (k >= E: up to 2 E are attempted) is dropped for the launch; a dropped entry only
+                    // costs an inline draw later.
                     const int64_t ccn = G.s.case_counter[e];
                     const int32_t rcn = G.s.reset_count[e];
-                    const uint32_t k = atomicAdd(g.pcount_w, 1u);
+                    uint32_t k;
+                    if constexpr (SEQ) {
+                        uint32_t *const aw = sl.app + 2 * q + (rcn & 1);
+                        k = *aw;
+                        if (k == 0u) {
+                            k = atomicAdd(g.pcount_w, 1u);
+                            *aw = k + 1u;
+                        } else k -= 1u;
+                    } else k = atomicAdd(g.pcount_w, 1u);
                     if (k < (uint32_t)G.E) {
                         uint32_t *q = g.plist_w + 4 * k;
                         q[0] = (uint32_t)e; q[1] = (uint32_t)rcn;
@@ -3529,6 +3608,10 @@ __global__ void __launch_bounds__(CN_BLK, 3) cn_step_kernel(StepArgs g, cn_confi
         // back to normal priority for the epilogue (graph mode's finish barrier, stamps)
         if ((KD || CN_RNG_PRIO_ALL) && w < nw) __builtin_amdgcn_s_setprio(0);
     }
+    // the next step's phase 0 reads the state (and the RNG streams) this step's resets and goal changes wrote
+    // through other waves, and rewrites the LDS their RNG regions and agent tables use
+    if constexpr (SEQ) __syncthreads();
+    } while (SEQ && ++step < g.nsteps);
 #ifdef CN_STAMPS
     __syncthreads();
     STAMP_A(6);
@@ -3970,7 +4053,8 @@ struct cn_engine {
     uint32_t ctl_host[4];
     int pend_all;         // next kernel A's pending mode: PEND_BOTH (after cn_set_state) or PEND_FRESH (after cn_reset)
     uint64_t nstep;
-    long long spawn_budget;   // clock cycles a spawning wave works per launch before parking (0: never)
+    long long spawn_budget;   // clock cycles a spawning wave works per step of a launch before parking (0: never)
+    int seq_chunk;        // steps per launch of cn_step_seq (1: a cn_step launch per step)
     void *pend_mem;       // pending next-episode spawns (PendPtrs)
     PendPtrs pend;
     int pend_blocks;      // spare workgroups of kernel A running spawn waves
@@ -4460,6 +4544,7 @@ int cn_create(const cn_config *cfg, int device, cn_engine **out)
         // launch queued again: two writers of one pending slot, one of them resuming from it -- 5 of 149 C3 runs
         // departed; 0 of 149 with keyed entries). The quad path parks after CN_QUAD_BUDGET cycles (round 6).
         g->spawn_budget = g->plan.kd ? 600000 : (CN_QUAD_PARK ? CN_QUAD_BUDGET : 0);
+        g->seq_chunk = CN_SEQ_CHUNK;
     }
     cn_state_bind(&g->s, g->state, g->E, g->N, cfg->robot_visible);
     if (circ_table_init() != hipSuccess) {
@@ -4468,7 +4553,9 @@ int cn_create(const cn_config *cfg, int device, cn_engine **out)
     }
     if (g->a_lds > 160 * 1024) { cn_destroy(g); return set_err(CN_EUNSUPPORTED, "LDS plan exceeds 160 KiB"); }
     if (g->a_lds > 64 * 1024) {
-        const void *ks[8] = {(const void *)cn_step_kernel<true, false, false>, (const void *)cn_step_kernel<false, false, false>,
+        const void *ks[10] = {(const void *)cn_step_kernel<false, false, false, false, true>,
+                              (const void *)cn_step_kernel<false, true, false, false, true>,
+                             (const void *)cn_step_kernel<true, false, false>, (const void *)cn_step_kernel<false, false, false>,
                              (const void *)cn_step_kernel<true, true, false>, (const void *)cn_step_kernel<false, true, false>,
                              (const void *)cn_step_kernel<true, false, true>, (const void *)cn_step_kernel<false, false, true>,
                              (const void *)cn_step_kernel<true, true, true>, (const void *)cn_step_kernel<false, true, true>};
@@ -4678,8 +4765,13 @@ int cn_reset(cn_engine *g, void *stream, float *robot_node, float *temporal, flo
     return CN_OK;
 }
 
-int cn_step(cn_engine *g, void *stream, const float *actions, float *robot_node, float *temporal, float *spatial,
-            float *reward, uint8_t *done, int8_t *event, float *info, double *ep_return, int32_t *ep_len)
+// One step launch. nsteps == 1: cn_step's launch (every engine, graph mode). nsteps > 1: a multi-step launch of
+// cn_step_seq (a plain quad-path engine outside graph mode, pend_all == 0: seq_fusable), whose step workgroups
+// run nsteps steps with the actions at actions + t * action_stride. g->nstep counts LAUNCHES (the triple-buffer
+// index of the spawn lists, the launch id, graph mode's hand-over); cn_profile's window counts STEPS.
+static int step_launch(cn_engine *g, void *stream, const float *actions, int nsteps, int64_t action_stride,
+                       float *robot_node, float *temporal, float *spatial, float *reward, uint8_t *done, int8_t *event,
+                       float *info, double *ep_return, int32_t *ep_len)
 {
     if (!g || !actions || !robot_node || !temporal || !spatial) return set_err(CN_EINVAL, "null argument");
     hipStream_t st = (hipStream_t)stream;
@@ -4687,6 +4779,8 @@ int cn_step(cn_engine *g, void *stream, const float *actions, float *robot_node,
     // graph mode keeps it on the device, StepArgs::devseq)
     const int kw = (int)(g->nstep % 3), kr = (int)((g->nstep + 2) % 3), kz = (int)((g->nstep + 1) % 3);
     ++g->nstep;
+    // the window's events: before the launch of its first step, after the launch that completes the count
+    // (cn_step_seq splits a chunk that would straddle the end of the window)
     const bool prof = g->prof_on && g->prof_n < g->prof_cap;
     if (prof && g->prof_n == 0) HIPCHK(hipEventRecord(g->ev[0], st));
     if (g->ngroups) {   // one step launch per group, concurrently (fork / join around the caller's stream)
@@ -4718,7 +4812,13 @@ int cn_step(cn_engine *g, void *stream, const float *actions, float *robot_node,
     a.rcount_zero = g->work_count + 5 + kz;
     a.pend.rlist = g->rlist + (int64_t)kr * 4 * (2 * (int64_t)g->E + 64); a.pend.rcount = g->work_count + 5 + kr;
     a.pend.rlist_w = g->rlist + (int64_t)kw * 4 * (2 * (int64_t)g->E + 64); a.pend.rcount_w = g->work_count + 5 + kw;
-    a.pend.budget = g->spawn_budget;
+    // the budget is clock cycles per STEP: a multi-step launch lasts nsteps times as long and draws the spawns its
+    // predecessor queued over as many steps, so its spawning waves get nsteps times the budget, the default one
+    // and one set through cn_debug_set_spawn_budget alike. (Taken per launch, a small test budget left a run of
+    // 300 steps with ~10 launches of one or two humans' progress each: no parked spawn ever completed.)
+    a.pend.budget = g->spawn_budget * nsteps;
+    a.nsteps = nsteps;
+    if (nsteps > 1) a.action_stride = action_stride;   // (shares ctl's slot: the SEQ kernels are never graph mode's)
     a.pend.stats = g->work_count + 8;
     a.pend.launch_id = (uint32_t)(g->nstep % 0x7ffffffeu) + 1u;   // nonzero, differs from the neighbours'
     const int blocks = (g->E + g->plan.EPB - 1) / g->plan.EPB;
@@ -4743,16 +4843,34 @@ int cn_step(cn_engine *g, void *stream, const float *actions, float *robot_node,
     void (*const kern_dev[4])(StepArgs, cn_config) = {   // graph mode (plain engines)
         cn_step_kernel<false, false, false, true>, cn_step_kernel<false, true, false, true>,
         cn_step_kernel<true, false, false, true>, cn_step_kernel<true, true, false, true>};
+    void (*const kern_seq[2])(StepArgs, cn_config) = {   // multi-step launches (plain quad-path engines)
+        cn_step_kernel<false, false, false, false, true>, cn_step_kernel<false, true, false, false, true>};
     (void)hipGetLastError();   // a stale error of an earlier call (any library) is not this launch's
-    if (g->devseq)
+    if (nsteps > 1) {
+        if (g->devseq || g->rows || g->plan.kd || a.pend.all)
+            return set_err(CN_EINVAL, "multi-step launch: plain quad-path engine outside graph mode required");
+        hipLaunchKernelGGL(kern_seq[phx ? 1 : 0], dim3(grid), dim3(g->plan.T), g->a_lds, st, a, g->c);
+    } else if (g->devseq)
         hipLaunchKernelGGL(kern_dev[variant >> 1], dim3(grid), dim3(g->plan.T), g->a_lds, st, a, g->c);
     else
         hipLaunchKernelGGL(kern[variant], dim3(grid), dim3(g->plan.T), g->a_lds, st, a, g->c);
     HIPCHK(hipGetLastError());
-    if (prof && ++g->prof_n == g->prof_cap) HIPCHK(hipEventRecord(g->ev[1], st));
+    if (prof && (g->prof_n += nsteps) >= g->prof_cap) HIPCHK(hipEventRecord(g->ev[1], st));
     return CN_OK;
 }
 
+int cn_step(cn_engine *g, void *stream, const float *actions, float *robot_node, float *temporal, float *spatial,
+            float *reward, uint8_t *done, int8_t *event, float *info, double *ep_return, int32_t *ep_len)
+{
+    return step_launch(g, stream, actions, 1, 0, robot_node, temporal, spatial, reward, done, event, info, ep_return,
+                       ep_len);
+}
+
+// T steps as ceil(T / C) multi-step launches of up to C = seq_chunk steps (the last one of the remainder), with
+// the results of T cn_step launches bit for bit. A launch per step where the multi-step kernels do not apply:
+// C == 1, mixed engines, graph mode, the kd-tree path (> 10 agents per simulator), and the first launch after
+// cn_reset / cn_set_state (pend_all != 0: its spawn waves redraw or ignore the pending lists; the chunks start
+// after it).
 int cn_step_seq(cn_engine *g, void *stream, int T, const float *actions, int64_t action_stride, float *robot_node,
                 float *temporal, float *spatial, float *reward, uint8_t *done, int8_t *event, float *info,
                 double *ep_return, int32_t *ep_len)
@@ -4760,10 +4878,19 @@ int cn_step_seq(cn_engine *g, void *stream, int T, const float *actions, int64_t
     if (!g || !actions) return set_err(CN_EINVAL, "null argument");
     if (T < 0 || (T > 1 && action_stride < 2 * g->E))
         return set_err(CN_EINVAL, "cn_step_seq: T >= 0 and action_stride >= 2 * E required");
-    for (int t = 0; t < T; ++t) {
-        const int rc = cn_step(g, stream, actions + (int64_t)t * action_stride, robot_node, temporal, spatial, reward,
-                               done, event, info, ep_return, ep_len);
+    const bool fusable = g->seq_chunk > 1 && !g->ngroups && !g->rows && !g->devseq && !g->plan.kd;
+    for (int t = 0; t < T;) {
+        int n = 1;
+        if (fusable && !g->pend_all) {
+            n = T - t < g->seq_chunk ? T - t : g->seq_chunk;
+            // a chunk never straddles the end of cn_profile's window: its last event follows the launch that
+            // completes the count
+            if (g->prof_on && g->prof_n < g->prof_cap && n > g->prof_cap - g->prof_n) n = g->prof_cap - g->prof_n;
+        }
+        const int rc = step_launch(g, stream, actions + (int64_t)t * action_stride, n, action_stride, robot_node,
+                                   temporal, spatial, reward, done, event, info, ep_return, ep_len);
         if (rc) return rc;
+        t += n;
     }
     return CN_OK;
 }
@@ -4880,6 +5007,14 @@ int cn_debug_set_spawn_budget(cn_engine *g, long long cycles)
     if (!g || cycles < 0) return set_err(CN_EINVAL, "cn_debug_set_spawn_budget: engine and cycles >= 0 required");
     for (int k = 0; k < g->ngroups; ++k) cn_debug_set_spawn_budget(g->grp[k], cycles);
     if (!g->ngroups && (g->plan.kd || CN_QUAD_PARK)) g->spawn_budget = cycles;   // (parking paths only)
+    return CN_OK;
+}
+
+int cn_debug_set_seq_chunk(cn_engine *g, int n)
+{
+    if (!g || n < 1) return set_err(CN_EINVAL, "cn_debug_set_seq_chunk: engine and n >= 1 required");
+    for (int k = 0; k < g->ngroups; ++k) cn_debug_set_seq_chunk(g->grp[k], n);   // (mixed engines step per launch)
+    g->seq_chunk = n;
     return CN_OK;
 }
 

@@ -206,6 +206,11 @@ class CrowdNavEngine:
         case where they did: DESIGN.md)."""
         _lib.check(_lib.lib().cn_debug_set_spawn_budget(self._h, int(cycles)))
 
+    def set_seq_chunk(self, n):
+        """Steps per launch of step_seq's multi-step launches (cn_debug_set_seq_chunk); 1 = one step launch per
+        step through the single-step kernels. Results do not depend on it."""
+        _lib.check(_lib.lib().cn_debug_set_seq_chunk(self._h, int(n)))
+
     def spawn_stats(self):
         """Cumulative spawn counters (cn_debug_spawn_stats; synchronises): kd-tree path spawns parked before
         starting, parked mid-way, resumed, completed by a resume; auto-resets drawn inline (no pending spawn)."""

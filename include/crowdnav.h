@@ -194,11 +194,14 @@ int cn_step(cn_engine *eng, void *stream, const float *actions,
             float *reward, uint8_t *done, int8_t *event, float *info,
             double *ep_return, int32_t *ep_len);
 
-/* T consecutive cn_step calls issued from native code: step t takes actions + t * action_stride
+/* T consecutive steps issued from native code: step t takes actions + t * action_stride
  * (floats; >= 2 * E, e.g. a [T][E][2] tensor), the outputs are those of the last step (each step
  * overwrites them, as T cn_step calls would). For open-loop action sequences (scripted or pre-drawn
- * actions, bench.py's synthetic windows): the launches go back to back without a host round trip per
- * step. Same kernels, same results as the T single calls. */
+ * actions, bench.py's synthetic windows). A plain engine with at most 10 agents per simulator runs them
+ * as multi-step launches: ceil(T / C) launches whose workgroups each step their own envs up to C times
+ * (cn_debug_set_seq_chunk), so no workgroup waits for the grid's slowest one after every step; every
+ * other engine (mixed, graph mode, > 10 agents) and the first launch after cn_reset / cn_set_state get
+ * one cn_step launch per step. Either way the results are those of the T single calls, bit for bit. */
 int cn_step_seq(cn_engine *eng, void *stream, int T, const float *actions, int64_t action_stride,
                 float *robot_node, float *temporal_edges, float *spatial_edges,
                 float *reward, uint8_t *done, int8_t *event, float *info,
@@ -230,11 +233,12 @@ int cn_set_state(cn_engine *eng, void *stream, const void *src, int src_on_host)
 const void *cn_state_device_ptr(const cn_engine *eng);
 
 /* Kernel timing (measurement hook for bench.py's roofline): while enabled, cn_step records one HIP event
- * on its stream before the first and one after the `max_steps`-th step launch of the window (per-launch
- * event pairs would cost ~12 us of stream time per step). cn_profile_read synchronises on the closing
+ * on its stream before the launch of the window's first step and one after the launch that completes its
+ * `max_steps`-th step (per-launch event pairs would cost ~12 us of stream time per step; cn_step_seq splits
+ * a multi-step launch at the end of the window). cn_profile_read synchronises on the closing
  * event and returns the window's span in step_kernel_ms (back-to-back launches: the summed launch
- * durations) and the launch count; rng_kernel_ms is always 0 (the RNG work is fused into the step
- * kernel). Reading an incomplete window is CN_EINVAL. */
+ * durations) and the number of STEPS in `launches`; rng_kernel_ms is always 0 (the RNG work is fused into
+ * the step kernel). Reading an incomplete window is CN_EINVAL. */
 int cn_profile(cn_engine *eng, int enable, int max_steps);
 int cn_profile_read(cn_engine *eng, double *step_kernel_ms, double *rng_kernel_ms, int64_t *launches);
 
@@ -459,9 +463,15 @@ int cn_social_force_predict(void *stream, int64_t n, int M, const double *self, 
  * cn_debug_spawn_stats: cumulative counts since cn_create [5] = spawns parked before they started, parked
  * mid-way, resumed, completed by a resume (kd-tree path), and auto-resets whose spawn the step kernel drew
  * inline because no pending spawn was ready (every path; synchronises the device). Results do not depend on the budget:
- * tests/test_gpu_parity.py forces parking after every human and compares with the oracle. */
+ * tests/test_gpu_parity.py forces parking after every human and compares with the oracle. The budget is per step:
+ * a multi-step launch of cn_step_seq gives its spawn waves `cycles` times its number of steps. */
 int cn_debug_set_spawn_budget(cn_engine *eng, long long cycles);
 int cn_debug_spawn_stats(cn_engine *eng, uint32_t *out);
+
+/* Steps per launch of cn_step_seq's multi-step launches (default: the library's CN_SEQ_CHUNK). n = 1 issues one
+ * cn_step launch per step through the single-step kernels: the in-library A/B and the reference of
+ * tests/test_step_seq_fused.py. Results do not depend on n. */
+int cn_debug_set_seq_chunk(cn_engine *eng, int n);
 
 /* Profiler calibration hook (MI355X_MICROARCH.md § HBM: FETCH_SIZE / WRITE_SIZE are calibrated only for
  * 16-B-per-lane streams): dst[k] = src[k] over n doubles with the step kernel's access shape, one 8-B load
