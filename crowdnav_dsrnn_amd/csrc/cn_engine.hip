@@ -53,12 +53,23 @@ __device__ unsigned long long cn_stamp_r[8192 * 2];   // every workgroup: start 
 __device__ unsigned long long cn_lp3_cnt[2 + 12];   // lp3 sub-problems solved / visited by the replay (all launches)
 __device__ unsigned long long cn_stamp_s[8192 * 16];   // spawn_env: start, seeded, robot, after human i (3 + i)
 #define STAMP_S(e, k) do { if (lane == 0 && (e) >= 0 && (e) < 8192) cn_stamp_s[(e) * 16 + (k)] = clock64(); } while (0)
-#define STAMP_R(k) do { if (threadIdx.x == 0 && blockIdx.x < 8192) cn_stamp_r[blockIdx.x * 2 + (k)] = __builtin_amdgcn_s_memrealtime(); } while (0)
+// every workgroup: where it ran (HW_REG_XCC_ID, HW_REG_HW_ID: CU / SE fields) and its start / end on its XCD's
+// shader clock, so that its in-kernel clock is (x[3] - x[2]) / (r[1] - r[0]) x 100 MHz (tools/probe_stamps.py xcd)
+__device__ unsigned long long cn_stamp_x[8192 * 4];
+#ifndef CN_LABEL_ROT
+#define CN_LABEL_ROT 0
+#endif
+#define CN_GETREG32(id) ((unsigned)__builtin_amdgcn_s_getreg((id) | (31 << 11)))
+#define STAMP_R(k) do { if (threadIdx.x == 0 && blockIdx.x < 8192) { \
+        if ((k) == 0) { cn_stamp_x[blockIdx.x * 4] = CN_GETREG32(20); cn_stamp_x[blockIdx.x * 4 + 1] = CN_GETREG32(4); } \
+        cn_stamp_x[blockIdx.x * 4 + 2 + (k)] = __builtin_amdgcn_s_memtime(); \
+        cn_stamp_r[blockIdx.x * 2 + (k)] = __builtin_amdgcn_s_memrealtime(); } } while (0)
 #define STAMP_A(k) do { const unsigned sb_ = (unsigned)sb; if (threadIdx.x == 0 && sb_ < 4096) cn_stamp_a[sb_ * CN_NSTAMP + (k)] = clock64(); } while (0)
 #define STAMP_B(w, k) do { if ((threadIdx.x & 63) == 0 && (w) < 8192) cn_stamp_b[(w) * CN_NSTAMP + (k)] = clock64(); } while (0)
 // stamp k by thread t (a lane of another wave than thread 0's)
 #define STAMP_T(k, t) do { const unsigned sb_ = (unsigned)sb; if (threadIdx.x == (t) && sb_ < 4096) cn_stamp_a[sb_ * CN_NSTAMP + (k)] = clock64(); } while (0)
 #else
+#define CN_LABEL_ROT 0
 #define STAMP_T(k, t) do { } while (0)
 #define STAMP_A(k) do { } while (0)
 #define STAMP_B(w, k) do { } while (0)
@@ -129,6 +140,13 @@ struct StepPlan {
 // of the steady window: 1: 38.7, 4: 33.9, 8: 32.0, 16: 30.9, 32: 29.9, 64: 29.6 but with resets that no longer
 // find their spawn drawn (a spawn queued in one launch is drawn by the next: > 1 inline draw per step at 64)
 #define CN_SEQ_CHUNK 32
+#endif
+#ifndef CN_SEQ_PRIO_ROT
+#define CN_SEQ_PRIO_ROT 1   // multi-step launches rotate their waves' issue priority with the step (cn_step_kernel)
+#endif
+#ifndef CN_SEQ_EMIT_LAST
+// multi-step launches store the caller's outputs in their last step only (0: in every step; the A/B of DESIGN.md §4)
+#define CN_SEQ_EMIT_LAST 1
 #endif
 #define CN_GRID 16
 #define CN_GRID_LDS (96 * 8 + CN_GRID * CN_GRID * 4 + 4 * 8 + 4 * 8)   // + spawn DiscGrid: agent table, masks, cover, box
@@ -1961,15 +1979,19 @@ __device__ __forceinline__ void write_pending(const PendPtrs &P2, const cn_confi
 
 // The deterministic rest of CrowdSimDict.reset (crowd_sim_dict.py:136-203): state of the new episode,
 // case_counter advance, first observation. `mt_src` = key words after the spawn (LDS or pending buffer).
+// OBS_OPT (the SEQ kernels): g.robot_node == nullptr means the first observation is not wanted (a later step of the
+// same launch overwrites it)
+template <bool OBS_OPT = false>
 __device__ __forceinline__ void write_reset(const ResetOut &g, const cn_config &c, int64_t e, const Env1 &en, double rth, int sc,
                             uint32_t ovf, const uint32_t *mt_src, int pos, int lane)
 {
+    const bool obs = !OBS_OPT || g.robot_node != nullptr;
     const cn_state_ptrs &S = g.s;
     const int N = c.human_num;
     const int64_t hb = e * N;
     const double rpx = en.rpx, rpy = en.rpy;
     const int64_t orw = orow(g.ov, e);
-    if (lane >= N && lane < g.ov.NS) {
+    if (obs && lane >= N && lane < g.ov.NS) {
         g.spatial[(orw * g.ov.NS + lane) * 2] = (float)(CN_PAD_POS - rpx);
         g.spatial[(orw * g.ov.NS + lane) * 2 + 1] = (float)(CN_PAD_POS - rpy);
     }
@@ -1988,8 +2010,10 @@ __device__ __forceinline__ void write_reset(const ResetOut &g, const cn_config &
         if (v) { bpx = px; bpy = py; bvx = 0; bvy = 0; br = en.hr[lane]; }
         else { bpx = 15.0; bpy = 15.0; bvx = 0.0; bvy = 0.0; br = 0.3; }
         S.b_px[h] = bpx; S.b_py[h] = bpy; S.b_vx[h] = bvx; S.b_vy[h] = bvy; S.b_r[h] = br;
-        g.spatial[(orw * g.ov.NS + lane) * 2] = (float)(bpx - rpx);
-        g.spatial[(orw * g.ov.NS + lane) * 2 + 1] = (float)(bpy - rpy);
+        if (obs) {
+            g.spatial[(orw * g.ov.NS + lane) * 2] = (float)(bpx - rpx);
+            g.spatial[(orw * g.ov.NS + lane) * 2 + 1] = (float)(bpy - rpy);
+        }
     }
     const int A = N + (c.robot_visible ? 1 : 0);
     if (A > 10) for (int k = lane; k < N * A; k += 64) S.o_perm[e * N * A + k] = 0;
@@ -2011,10 +2035,12 @@ __device__ __forceinline__ void write_reset(const ResetOut &g, const cn_config &
         S.reset_count[e] += 1;
         S.ep_return[e] = 0.0; S.ep_len[e] = 0;
         S.flags[e] = 0; S.overflow[e] = ovf; S.mt_pos[e] = pos;
-        float *rn = g.robot_node + orw * 7;
-        rn[0] = (float)rpx; rn[1] = (float)rpy; rn[2] = (float)c.robot_radius;
-        rn[3] = (float)en.rgx; rn[4] = (float)en.rgy; rn[5] = (float)c.robot_vpref; rn[6] = (float)rth;
-        g.temporal[orw * 2] = 0.0f; g.temporal[orw * 2 + 1] = 0.0f;
+        if (obs) {
+            float *rn = g.robot_node + orw * 7;
+            rn[0] = (float)rpx; rn[1] = (float)rpy; rn[2] = (float)c.robot_radius;
+            rn[3] = (float)en.rgx; rn[4] = (float)en.rgy; rn[5] = (float)c.robot_vpref; rn[6] = (float)rth;
+            g.temporal[orw * 2] = 0.0f; g.temporal[orw * 2 + 1] = 0.0f;
+        }
     }
 }
 
@@ -2242,7 +2268,7 @@ __device__ __forceinline__ void goal_changes(const cn_config &c, const cn_state_
 
 // Auto-reset of env e (VecEnv worker, shmem_vec_env.py:164-168 -> CrowdSimDict.reset): copy the pending
 // spawn when `may_consume` and it is valid for the current key, else draw it here. One wave.
-template <bool GRID, bool FENCE = GRID>
+template <bool GRID, bool FENCE = GRID, bool OBS_OPT = false>
 __device__ __forceinline__ void reset_env(const ResetOut &o, const PendPtrs &P2, const cn_config &c, int64_t E, int64_t e,
                           int64_t counter_offset, bool may_consume, uint32_t launch_id, WRng &m, Env1 &en,
                           uint32_t *inline_count = nullptr)
@@ -2286,7 +2312,7 @@ __device__ __forceinline__ void reset_env(const ResetOut &o, const PendPtrs &P2,
         en.rpx = P.r[e]; en.rpy = P.r[E + e]; en.rgx = P.r[2 * E + e]; en.rgy = P.r[3 * E + e];
         const double rth = P.r[4 * E + e];
         wsync();
-        write_reset(o, c, e, en, rth, P.sc[e], P.ovf[e], P.mt + e * CN_MT_N, P.pos[e], lane);
+        write_reset<OBS_OPT>(o, c, e, en, rth, P.sc[e], P.ovf[e], P.mt + e * CN_MT_N, P.pos[e], lane);
     } else {
         double rth;
         uint32_t ovf;
@@ -2294,7 +2320,7 @@ __device__ __forceinline__ void reset_env(const ResetOut &o, const PendPtrs &P2,
         if (inline_count && lane == 0) atomicAdd(inline_count, 1u);
         spawn_env<GRID>(c, c.env_offset + orow(o.ov, e), cc, rc, counter_offset, m, en, rth, ovf, sc);
         const bool in1 = !m.phx && m.p > CN_MT_N;
-        write_reset(o, c, e, en, rth, sc, ovf, m.blk(in1 ? 1 : 0), in1 ? m.p - CN_MT_N : m.p, lane);
+        write_reset<OBS_OPT>(o, c, e, en, rth, sc, ovf, m.blk(in1 ? 1 : 0), in1 ? m.p - CN_MT_N : m.p, lane);
     }
     wsync();
 }
@@ -2649,13 +2675,37 @@ __global__ void __launch_bounds__(CN_BLK, 3) cn_step_kernel(StepArgs g, cn_confi
     // the whole step (292 VGPRs spilled to scratch); now every step computes them at their uses, as a launch of
     // its own does
     if constexpr (SEQ) { asm volatile("" : "+v"(tid)); asm volatile("" : "+s"(sbk)); }
+#if CN_SEQ_PRIO_ROT
+    // SEQ: the issue priority of the workgroup's waves rotates with the step. A CU's resident workgroups sit in
+    // wave slots 0, 1, 2 of its SIMDs in the order they arrived (HW_REG_HW_ID's wave id), and at equal priority
+    // the SIMD issues its oldest wave first: the first workgroup of a CU ran 32 steps in ~790 us, the second in
+    // ~860, the third in ~940, launch after launch, and the launch ends with the third ("Where the
+    // persistent groups come from"). With priority (slot + step) % 3 every workgroup spends a third of its steps
+    // at each rank. For speed only: results do not depend on it.
+    if constexpr (SEQ) {
+        const unsigned ws = (unsigned)__builtin_amdgcn_s_getreg(4 | (3 << 11));   // HW_ID bits 3:0: the wave slot
+        switch ((ws + (unsigned)step) % 3u) {
+        case 0: __builtin_amdgcn_s_setprio(0); break;
+        case 1: __builtin_amdgcn_s_setprio(1); break;
+        default: __builtin_amdgcn_s_setprio(2); break;
+        }
+    }
+#endif
     // XCD-aware env placement: workgroup i runs on XCD i % 8 (round-robin dispatch; for speed only), so
     // give each XCD a contiguous run of env blocks. Neighbouring workgroups share the 128-B lines at the
     // ends of their SoA segments (a per-env field of one workgroup is only 48 B); on one XCD the second
     // reader hits in that XCD's L2 instead of fetching the line again.
     // (a leading pend_blocks is a multiple of 8, so step workgroup sb runs on XCD sb % 8 as well)
     const int nbk = g.pend.step_blocks, xq = nbk >> 3, xr = nbk & 7, xi = sbk & 7;
+#if CN_LABEL_ROT
+    // diagnostic (-DCN_STAMPS -DCN_LABEL_ROT=r, tools/probe_stamps.py xcd): the labels' runs of env blocks in the
+    // order of (label + r) & 7, so that a slowness bound to the label can be told from one bound to the env range
+    int blk = sbk >> 3;
+    for (int y = 0; y < 8; ++y)
+        if (((y + CN_LABEL_ROT) & 7) < ((xi + CN_LABEL_ROT) & 7)) blk += xq + (y < xr ? 1 : 0);
+#else
     const int blk = xi * xq + min(xi, xr) + (sbk >> 3);
+#endif
     const int e0 = blk * EPB;
     const int nenv_here = min(EPB, g.E - e0);
     const int el = tid / N, i = tid - el * N;
@@ -2671,6 +2721,13 @@ __global__ void __launch_bounds__(CN_BLK, 3) cn_step_kernel(StepArgs g, cn_confi
 
     const float *actions = g.actions;
     if constexpr (SEQ) actions += (int64_t)step * g.action_stride;
+    // SEQ: the caller reads the outputs of the launch's last step only (every step would overwrite them), so the
+    // earlier steps neither convert nor store them (wave-uniform; state writes are not outputs and stay)
+#if CN_SEQ_EMIT_LAST
+    const bool emit = !SEQ || step == g.nsteps - 1;
+#else
+    const bool emit = true;
+#endif
     STAMP_A(0);
     // ---- phase 0: load state into LDS -----------------------------------------------------------
     // values needed in later phases are loaded here, so their latency overlaps phase 0 (doubles parked
@@ -2949,7 +3006,7 @@ __global__ void __launch_bounds__(CN_BLK, 3) cn_step_kernel(StepArgs g, cn_confi
             if (event == CN_EV_DANGER || event == CN_EV_NOTHING) reward = reward + (double)r_spin + (double)r_back;
             else reward = (double)(((float)reward + r_spin) + r_back);
         }
-        if (g.info) {
+        if (emit && g.info) {
             float *info = g.info + orow(ov, ge) * CN_INFO_K;
             info[CN_INFO_AGG_NAV_TIME] = (float)agg;
             info[CN_INFO_PERSONAL_VIOLATION] = dmin < c.min_personal_space ? 1.0f : 0.0f;
@@ -2967,12 +3024,14 @@ __global__ void __launch_bounds__(CN_BLK, 3) cn_step_kernel(StepArgs g, cn_confi
         const double epr = RF(sl, R_EPR, re, EPB) + reward;
         const int32_t epl = pre_epl + 1;
         S.ep_return[ge] = epr; S.ep_len[ge] = epl;
-        const int64_t oe = orow(ov, ge);
-        if (g.reward) g.reward[oe] = (float)reward;
-        if (g.done) g.done[oe] = (uint8_t)done;
-        if (g.event) g.event[oe] = (int8_t)event;
-        if (g.ep_return) g.ep_return[oe] = epr;
-        if (g.ep_len) g.ep_len[oe] = epl;
+        if (emit) {
+            const int64_t oe = orow(ov, ge);
+            if (g.reward) g.reward[oe] = (float)reward;
+            if (g.done) g.done[oe] = (uint8_t)done;
+            if (g.event) g.event[oe] = (int8_t)event;
+            if (g.ep_return) g.ep_return[oe] = epr;
+            if (g.ep_len) g.ep_len[oe] = epl;
+        }
         sl.rflag[EPB + re] = (uint32_t)done;   // aux word: done
     };
     // human kinematics, robot-FOV belief, observation and goal-reached detection of human hh from its new
@@ -3437,9 +3496,11 @@ __global__ void __launch_bounds__(CN_BLK, 3) cn_step_kernel(StepArgs g, cn_confi
         const double bpx = hst_ref(tid, 2), bpy = hst_ref(tid, 3);
         S.b_px[gh] = bpx; S.b_py[gh] = bpy; S.b_vx[gh] = hst_ref(tid, 4); S.b_vy[gh] = hst_ref(tid, 5);
         S.b_r[gh] = hst_ref(tid, 6);
-        const int64_t oh = orow(ov, e0 + el) * ov.NS + i;
-        g.spatial[oh * 2] = (float)(bpx - RF(sl, R_NX, el, EPB));
-        g.spatial[oh * 2 + 1] = (float)(bpy - RF(sl, R_NY, el, EPB));
+        if (emit) {
+            const int64_t oh = orow(ov, e0 + el) * ov.NS + i;
+            g.spatial[oh * 2] = (float)(bpx - RF(sl, R_NX, el, EPB));
+            g.spatial[oh * 2 + 1] = (float)(bpy - RF(sl, R_NY, el, EPB));
+        }
     }
     if (rl) {
         // robot kinematics (agent.py:198-212): the post-move state computed in phase 1
@@ -3470,19 +3531,21 @@ __global__ void __launch_bounds__(CN_BLK, 3) cn_step_kernel(StepArgs g, cn_confi
             nan |= (f & 0x80000000u) != 0;
             vr_viol += (k < kv && (f & LF_VR)) ? 1 : 0;
         }
-        if (g.info) g.info[orow(ov, ge) * CN_INFO_K + CN_INFO_PATH_VIOLATION] = (float)vr_viol;
+        if (emit && g.info) g.info[orow(ov, ge) * CN_INFO_K + CN_INFO_PATH_VIOLATION] = (float)vr_viol;
         if (nan) flags2 |= CN_FLAG_NAN;
         S.flags[ge] = flags2;
-        const int64_t oe = orow(ov, ge);
-        float *rn = g.robot_node + oe * 7;
-        rn[0] = (float)nx; rn[1] = (float)ny; rn[2] = (float)RF(sl, R_RAD, re, EPB);
-        rn[3] = (float)RF(sl, R_GX, re, EPB); rn[4] = (float)RF(sl, R_GY, re, EPB);
-        rn[5] = (float)RF(sl, R_VP, re, EPB); rn[6] = (float)RF(sl, R_TH, re, EPB);
-        g.temporal[oe * 2] = (float)RF(sl, R_VX, re, EPB);
-        g.temporal[oe * 2 + 1] = (float)RF(sl, R_VY, re, EPB);
-        for (int k = N; k < ov.NS; ++k) {   // padding slots of a mixed engine (never-seen humans)
-            g.spatial[(oe * ov.NS + k) * 2] = (float)(CN_PAD_POS - nx);
-            g.spatial[(oe * ov.NS + k) * 2 + 1] = (float)(CN_PAD_POS - ny);
+        if (emit) {
+            const int64_t oe = orow(ov, ge);
+            float *rn = g.robot_node + oe * 7;
+            rn[0] = (float)nx; rn[1] = (float)ny; rn[2] = (float)RF(sl, R_RAD, re, EPB);
+            rn[3] = (float)RF(sl, R_GX, re, EPB); rn[4] = (float)RF(sl, R_GY, re, EPB);
+            rn[5] = (float)RF(sl, R_VP, re, EPB); rn[6] = (float)RF(sl, R_TH, re, EPB);
+            g.temporal[oe * 2] = (float)RF(sl, R_VX, re, EPB);
+            g.temporal[oe * 2 + 1] = (float)RF(sl, R_VY, re, EPB);
+            for (int k = N; k < ov.NS; ++k) {   // padding slots of a mixed engine (never-seen humans)
+                g.spatial[(oe * ov.NS + k) * 2] = (float)(CN_PAD_POS - nx);
+                g.spatial[(oe * ov.NS + k) * 2 + 1] = (float)(CN_PAD_POS - ny);
+            }
         }
         // random numbers needed? (crowd_sim_dict.py:260-269, shmem_vec_env.py:166-167)
         const bool done = sl.rflag[EPB + re] != 0;
@@ -3548,6 +3611,7 @@ __global__ void __launch_bounds__(CN_BLK, 3) cn_step_kernel(StepArgs g, cn_confi
             ResetOut o;
             o.s = G.s; o.robot_node = G.robot_node; o.temporal = G.temporal; o.spatial = G.spatial;
             o.case_size = G.case_size; o.ov = ov;
+            if (SEQ && !emit) o.robot_node = nullptr;   // (write_reset<OBS_OPT>: no first observation)
             const uint32_t need = sl.rflag[EPB + q] & 7u;
             const int64_t e = e0 + q;
             STAMP_B(e, 0);
@@ -3559,7 +3623,7 @@ __global__ void __launch_bounds__(CN_BLK, 3) cn_step_kernel(StepArgs g, cn_confi
                 // rewrote them at the top from the device-side step counter; the kernarg segment holds the values of
                 // the captured launch)
                 const bool may = g.pend.all != PEND_BOTH;   // ready unless this launch redraws both
-                reset_env<KD, (KD || CN_QUAD_PARK) && CN_SLOT_FENCE>(o, G.pend.P, C, G.E, e, G.pend.counter_offset, may,
+                reset_env<KD, (KD || CN_QUAD_PARK) && CN_SLOT_FENCE, SEQ>(o, G.pend.P, C, G.E, e, G.pend.counter_offset, may,
                                                                      g.pend.launch_id, m, en, G.pend.stats + 7);
                 if (lane == 0) {
                     // the entry carries the counters this reset just wrote (its own stores, read back), so the
@@ -4990,6 +5054,14 @@ int cn_debug_stamps_r(unsigned long long *r, unsigned long long *sp)
     unsigned long long l3[14];
     HIPCHK(hipMemcpyFromSymbol(l3, HIP_SYMBOL(cn_lp3_cnt), sizeof(l3)));
     for (int k = 0; k < 14; ++k) r[8192 * 2 - 14 + k] = l3[k];   // (the last workgroup slots: never a real grid here)
+    return CN_OK;
+}
+
+// per workgroup [8192][4]: HW_REG_XCC_ID, HW_REG_HW_ID, start / end on the XCD's shader clock
+int cn_debug_stamps_x(unsigned long long *x)
+{
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpyFromSymbol(x, HIP_SYMBOL(cn_stamp_x), sizeof(unsigned long long) * 8192 * 4));
     return CN_OK;
 }
 

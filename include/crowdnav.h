@@ -199,7 +199,9 @@ int cn_step(cn_engine *eng, void *stream, const float *actions,
  * overwrites them, as T cn_step calls would). For open-loop action sequences (scripted or pre-drawn
  * actions, bench.py's synthetic windows). A plain engine with at most 10 agents per simulator runs them
  * as multi-step launches: ceil(T / C) launches whose workgroups each step their own envs up to C times
- * (cn_debug_set_seq_chunk), so no workgroup waits for the grid's slowest one after every step; every
+ * (cn_debug_set_seq_chunk), so no workgroup waits for the grid's slowest one after every step. Such a launch
+ * stores the outputs in its last step only (the earlier steps' values would be overwritten unread), and its
+ * waves rotate their issue priority from step to step, so that the workgroups sharing a CU advance alike; every
  * other engine (mixed, graph mode, > 10 agents) and the first launch after cn_reset / cn_set_state get
  * one cn_step launch per step. Either way the results are those of the T single calls, bit for bit. */
 int cn_step_seq(cn_engine *eng, void *stream, int T, const float *actions, int64_t action_stride,

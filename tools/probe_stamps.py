@@ -216,6 +216,121 @@ def run(variant, E=4096, N=10, steps=300):
     eng.close()
 
 
+def run_xcd(rot=0, launches=60, warm=130, chunk=32, E=4096, N=10):
+    """Where the step workgroups of C2's multi-step launches run and how long they take: per workgroup label
+    (step workgroup index & 7: the workgroups that share an XCD under round-robin dispatch), per XCC id, and per
+    place in their CU's residency order.
+
+        CN_LIB_PATH=<stamps build> python tools/probe_stamps.py xcd [rot]
+
+    rot: the CN_LABEL_ROT the library was built with (the labels' env ranges in the order of (label + rot) & 7), so
+    that a slowness that stays with the label can be told from one that moves with the env range.
+    Durations on the device-wide 100 MHz clock (s_memrealtime); a workgroup's clock is its shader-clock span
+    (s_memtime) over that."""
+    c = clone_config(Config())
+    c.humans.policy = "orca"
+    c.sim.human_num = N
+    c.sim.train_val_sim = c.sim.test_sim = ["circle_crossing"]
+    c.action_space.kinematics = "unicycle"
+    eng = CrowdNavEngine(make_cn_config(c, num_envs=E), "cuda:0")
+    eng.reset()
+    eng.set_seq_chunk(chunk)
+    L = _lib.lib()
+    L.cn_debug_stamps_r.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+    L.cn_debug_stamps_x.argtypes = [ctypes.c_void_p]
+    g = torch.Generator(device="cuda:0")
+    g.manual_seed(0)
+    acts = torch.rand((warm + chunk * launches, E, 2), generator=g, device="cuda:0") * 0.2 - 0.1
+    eng.step_seq(acts[:warm])
+    epb = min(64 // N, 16)
+    nstep = (E + epb - 1) // epb
+    r = np.zeros(8192 * 2, np.uint64)
+    x = np.zeros(8192 * 4, np.uint64)
+    ta, tb, nn = ctypes.c_double(), ctypes.c_double(), ctypes.c_int64()
+    lab = np.arange(nstep) & 7
+    dur = np.zeros((launches, nstep))
+    clk = np.zeros((launches, nstep))
+    xcc = np.zeros((launches, nstep), int)
+    order = np.zeros((launches, nstep), int)     # place in the CU's residency order: 0 = the first to start there
+    share = np.zeros((launches, nstep), int)     # step workgroups on the same CU
+    wslot = np.zeros((launches, nstep), int)     # HW_ID wave slot of the workgroup's wave 0
+    kern, last_end = [], []
+    st0 = eng.spawn_stats()
+    for k in range(launches):
+        _lib.check(L.cn_profile(eng._h, 1, chunk))
+        eng.step_seq(acts[warm + k * chunk:warm + (k + 1) * chunk])
+        _lib.check(L.cn_profile_read(eng._h, ctypes.byref(ta), ctypes.byref(tb), ctypes.byref(nn)))
+        L.cn_debug_stamps_r(r.ctypes.data_as(ctypes.c_void_p), None)
+        L.cn_debug_stamps_x(x.ctypes.data_as(ctypes.c_void_p))
+        R = r.reshape(-1, 2).astype(np.int64)[:nstep]
+        X = x.reshape(-1, 4).astype(np.int64)[:nstep]
+        dur[k] = (R[:, 1] - R[:, 0]) / 100.0                                            # us
+        clk[k] = (X[:, 3] - X[:, 2]) / np.maximum(R[:, 1] - R[:, 0], 1) * 100.0          # MHz
+        xcc[k] = X[:, 0] & 0xf
+        wslot[k] = X[:, 1] & 0xf
+        key = xcc[k] * 256 + (X[:, 1] >> 8 & 0xff)     # XCC id, then HW_ID's CU / SH / SE fields (bits 8-15)
+        for kk in np.unique(key):
+            m = np.nonzero(key == kk)[0]
+            share[k, m] = len(m)
+            order[k, m[np.argsort(R[m, 0], kind="stable")]] = np.arange(len(m))
+        kern.append(ta.value * 1e3)
+        last_end.append((R[:, 1].max() - R[:, 0].min()) / 100.0)
+    _lib.check(L.cn_profile(eng._h, 0, 0))
+    st1 = eng.spawn_stats()
+    kern = np.asarray(kern)
+    print("[xcd rot %d] chunk %d, %d launches after %d warm-up steps (us; stamps build), %d step workgroups"
+          % (rot, chunk, launches, warm, nstep))
+    wg_mean = dur.mean(axis=0)
+    allm = dur.mean()
+    print("  kernel %.2f  step-WG mean %.2f  max %.2f  last step-WG end %.2f  -> kernel / mean step-WG %.3f, max / mean %.3f"
+          % (kern.mean(), allm, dur.max(axis=1).mean(), np.mean(last_end), kern.mean() / allm,
+             dur.max(axis=1).mean() / allm))
+    h, edges = np.histogram(wg_mean, bins=12)
+    print("  histogram of per-workgroup means: " + " ".join("%.1f:%d" % (edges[i], h[i]) for i in range(len(h))))
+    print("  (a) by label: label | env range | WGs | XCC ids seen | per-WG means: mean  std  min  max | clock MHz")
+    lm, ls = [], []
+    for b in range(8):
+        v = wg_mean[lab == b]
+        lm.append(v.mean())
+        ls.append(v.std())
+        print("      %5d | %9d | %3d | %-12s | %8.2f %8.2f %8.2f %8.2f | %8.1f" % (
+            b, (b + rot) & 7, len(v), ",".join(map(str, np.unique(xcc[:, lab == b]))), v.mean(), v.std(), v.min(), v.max(),
+            clk[:, lab == b].mean()))
+    print("      spread between the labels' means: std %.2f, max - min %.2f; within a label (std of its workgroups' means): %.2f"
+          % (np.std(lm), np.max(lm) - np.min(lm), np.mean(ls)))
+    print("  (b) by dispatch order (step workgroup index // 256: one workgroup per CU and round): "
+          + "; ".join("%d: %d WGs mean %.2f std %.2f" % (q, (np.arange(nstep) // 256 == q).sum(),
+                                                          wg_mean[np.arange(nstep) // 256 == q].mean(),
+                                                          wg_mean[np.arange(nstep) // 256 == q].std())
+                      for q in range((nstep + 255) // 256)))
+    print("  (c) by place in the CU's residency order (per launch: rank of the workgroup's start among the step "
+          "workgroups of its XCC / SE / SH / CU), all launches:")
+    for q in range(order.max() + 1):
+        m = order == q
+        print("      place %d: %6d samples  duration mean %.2f std %.2f  clock %.1f MHz" % (
+            q, m.sum(), dur[m].mean(), dur[m].std(), clk[m].mean()))
+    for sh in np.unique(share):
+        print("      CUs with %d step workgroups: " % sh + "; ".join(
+            "place %d mean %.2f" % (q, dur[(share == sh) & (order == q)].mean()) for q in range(sh)))
+    stable = (order == order[0]).all(axis=0)
+    print("      workgroups with the same place in every launch: %d of %d; their per-WG means by place: %s" % (
+        stable.sum(), nstep, "; ".join("%d: %d WGs mean %.2f std %.2f" % (
+            q, (stable & (order[0] == q)).sum(), wg_mean[stable & (order[0] == q)].mean(),
+            wg_mean[stable & (order[0] == q)].std()) for q in range(order.max() + 1) if (stable & (order[0] == q)).any())))
+    print("      HW_ID wave slot of wave 0 by place (last launch): " + "; ".join(
+        "place %d: %s" % (q, dict(zip(*[a.tolist() for a in np.unique(wslot[-1][order[-1] == q], return_counts=True)])))
+        for q in range(order.max() + 1)))
+    resid = dur - np.choose(order, [dur[order == q].mean() for q in range(order.max() + 1)])
+    print("  (d) left after the place's mean is taken out: std of per-WG means %.2f (raw %.2f); per label means %s"
+          % (resid.mean(axis=0).std(), wg_mean.std(), " ".join("%.2f" % resid[:, lab == b].mean() for b in range(8))))
+    print("  spawn stats delta: %s" % {k: st1[k] - st0[k] for k in st1})
+    print("  per step: kernel %.2f us" % (kern.mean() / chunk))
+    eng.close()
+
+
 if __name__ == "__main__":
+    if sys.argv[1:2] == ["xcd"]:
+        run_xcd(int(sys.argv[2]) if len(sys.argv) > 2 else 0)
+        sys.exit(0)
     for v in (sys.argv[1:] or ["c2", "nogoal", "sf"]):
         run(v)
