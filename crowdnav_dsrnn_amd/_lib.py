@@ -117,6 +117,9 @@ def lib():
     L.cn_gru_bwd_step.argtypes = [vp, i64, ctypes.c_int] + [vp] * 7
     L.cn_lidar_obs.argtypes = [vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, vp, vp]
     L.cn_lidar_scan.argtypes = [vp, vp, ctypes.c_int, ctypes.c_double, ctypes.c_double, vp]
+    if hasattr(L, "cn_robot_act") or not os.environ.get("CN_LIB_PATH"):   # (an older A/B library lacks it)
+        L.cn_robot_act.argtypes = [vp, vp, ctypes.c_int, vp]
+        L.cn_robot_act.restype = i32
     L.cn_attn_pool_fwd.argtypes = [vp, i64, ctypes.c_int, ctypes.c_int] + [vp] * 3
     L.cn_attn_pool_bwd.argtypes = [vp, i64, ctypes.c_int, ctypes.c_int] + [vp] * 5
     try:
@@ -196,6 +199,6 @@ EXPORTED = ["cn_last_error", "cn_version", "cn_config_validate", "cn_create", "c
             "cn_spatial_attn_bwd", "cn_wgrad_work_elems", "cn_wgrad",
             "cn_gru_bias_blocks", "cn_gru_bwd_step_bias", "cn_gru_bwd_step_gates", "cn_gru_bias_work_elems", "cn_gru_bias_reduce",
             "cn_gru_bwd_seq_work_elems", "cn_gru_fwd_step_group", "cn_gru_fwd_seq", "cn_gru_bwd_seq", "cn_gaussian_act", "cn_gae",
-            "cn_set_graph_mode", "cn_graph_node_counts", "cn_lidar_obs", "cn_lidar_scan", "cn_debug_disc_quad",
+            "cn_set_graph_mode", "cn_graph_node_counts", "cn_lidar_obs", "cn_lidar_scan", "cn_robot_act", "cn_debug_disc_quad",
             "cn_debug_orca", "cn_debug_copy64", "cn_orca_predict", "cn_orca_predict_kd", "cn_social_force_predict",
             "cn_debug_set_spawn_budget", "cn_debug_spawn_stats", "cn_debug_set_seq_chunk"]

@@ -4403,6 +4403,148 @@ __global__ void __launch_bounds__(64) cn_sf_predict_kernel(int64_t n, int M, con
     else { out[2 * i] = nx; out[2 * i + 1] = ny; }
 }
 
+// ------------------------------------------------------------------------------------------------
+// cn_robot_act: the scripted robot (ORCA / social force) on the engine's CURRENT state, read straight from
+// the blob: policy_factory[name](config).predict(JointState(robot FullState, [ObservableState(b_px, b_py,
+// b_vx, b_vy, b_r) of the N humans in index order])) of a fresh policy object per env, rounded to float32.
+// Pure functions of the state (nothing held between calls), one launch each.
+// ------------------------------------------------------------------------------------------------
+// Agent j of the robot's RVO2 simulator in float32 as ORCA._frame casts it (orca.py:91-115): j = 0 the robot,
+// j >= 1 the belief of human j - 1; radius (float)((radius + 0.01) + safety_space).
+__device__ __forceinline__ void robot_sim_agent(const cn_state_ptrs &S, double safety, int64_t e, int N, int j,
+                                                float &x, float &y, float &vx, float &vy, float &r)
+{
+    if (j == 0) {
+        x = (float)S.r_px[e]; y = (float)S.r_py[e]; vx = (float)S.r_vx[e]; vy = (float)S.r_vy[e];
+        r = (float)((S.r_radius[e] + 0.01) + safety);
+    } else {
+        const int64_t h = e * N + (j - 1);
+        x = (float)S.b_px[h]; y = (float)S.b_py[h]; vx = (float)S.b_vx[h]; vy = (float)S.b_vy[h];
+        r = (float)((S.b_r[h] + 0.01) + safety);
+    }
+}
+
+// maxSpeed and the preferred velocity (orca.py:118-122): float64 towards the goal, normalised only above
+// speed 1 (np.linalg.norm), then float32
+__device__ __forceinline__ void robot_pref_velocity(const cn_state_ptrs &S, int64_t e, float &vmax, float &ox, float &oy)
+{
+    const double vx = S.r_gx[e] - S.r_px[e], vy = S.r_gy[e] - S.r_py[e];
+    const double speed = np_norm2(vx, vy);
+    vmax = (float)S.r_vpref[e];
+    if (speed > 1) { ox = (float)ddiv(vx, speed); oy = (float)ddiv(vy, speed); }
+    else { ox = (float)vx; oy = (float)vy; }
+}
+
+// ORCA, N + 1 <= 10 agents: cn_orca_kernel's quad path (one quad per env, 16 envs per 64-lane workgroup).
+// `act` depends on the quad alone, so a quad is whole or absent and its control flow uniform (DESIGN.md §4,
+// "Cross-lane reads"): the quad's 4 lanes read the same state words.
+__global__ void __launch_bounds__(64) cn_robot_orca_kernel(cn_state_ptrs S, int E, int N, double safety, float nd,
+                                                           float th, float ts, float *__restrict__ actions)
+{
+    __shared__ float4 Ls[16][9];
+    const int q = threadIdx.x >> 2, sq = threadIdx.x & 3;
+    const int64_t e = (int64_t)blockIdx.x * 16 + q;
+    const bool act = e < E;
+    int cnt = 0;
+    if (act) {
+        float X0, Y0, VX0, VY0, R0;
+        robot_sim_agent(S, safety, e, N, 0, X0, Y0, VX0, VY0, R0);
+        cnt = orca_lines_quad(
+            [&](int k, float &x, float &y, float &vx, float &vy, float &r) {
+                robot_sim_agent(S, safety, e, N, k + 1, x, y, vx, vy, r);
+            },
+            N, sq, X0, Y0, VX0, VY0, R0, nd * nd, fdiv(1.0f, th), fdiv(1.0f, ts), Ls[q]);
+    }
+    wsync();
+    if (act) {
+        float vmax, ox, oy, rx, ry;
+        robot_pref_velocity(S, e, vmax, ox, oy);
+        float4 R[3];
+#pragma unroll
+        for (int u = 0; u < 3; ++u) R[u] = sq + 4 * u < cnt ? Ls[q][sq + 4 * u] : make_float4(0.f, 0.f, 0.f, 0.f);
+        const int fail_at = lp2_r<3>(R, cnt, vmax, ox, oy, sq, rx, ry);
+        if (fail_at < cnt) lp3_r<3>(R, Ls[q], cnt, fail_at, vmax, sq, rx, ry);
+        if (sq == 0) { actions[2 * e] = rx; actions[2 * e + 1] = ry; }
+    }
+}
+
+// ORCA, N + 1 > 10 agents: cn_orca_kd_kernel's path with a fresh simulator's identity agent order (LDS sized by
+// A = N + 1: orca_kd_lds)
+__global__ void __launch_bounds__(64) cn_robot_orca_kd_kernel(cn_state_ptrs S, int E, int N, double safety, float nd,
+                                                              float th, float ts, float *__restrict__ actions)
+{
+    extern __shared__ __attribute__((aligned(16))) char kd_smem[];
+    const int A = N + 1;
+    const int q = threadIdx.x >> 2, sq = threadIdx.x & 3;
+    float4 *Lq = (float4 *)kd_smem + q * (A - 1);                 // [16][A - 1]
+    float4 *Pq = (float4 *)kd_smem + 16 * (A - 1) + q * (A - 1);  // [16][A - 1]
+    float *Xq = (float *)(kd_smem + 16 * 2 * 16 * (A - 1)) + q * A;
+    float *Yq = (float *)(kd_smem + 16 * 2 * 16 * (A - 1)) + 16 * A + q * A;
+    uint8_t *Pmq = (uint8_t *)(kd_smem + 16 * (2 * 16 * (A - 1) + 2 * 4 * A)) + q * A;
+    uint8_t *Nbq = (uint8_t *)(kd_smem + 16 * (2 * 16 * (A - 1) + 2 * 4 * A)) + 16 * A + q * A;
+    int *Cn = (int *)(kd_smem + orca_kd_lds(A) - 16 * 4);
+    const int64_t e = (int64_t)blockIdx.x * 16 + q;
+    const bool act = e < E;
+    if (act)
+        for (int k = sq; k < A; k += 4) {
+            float x, y, vx, vy, r;
+            robot_sim_agent(S, safety, e, N, k, x, y, vx, vy, r);
+            Xq[k] = x; Yq[k] = y;
+            Pmq[k] = (uint8_t)k;
+        }
+    wsync();
+    if (act && sq == 0) Cn[q] = kd_neighbors_seq(A, Xq, Yq, Pmq, nd * nd, Nbq);
+    wsync();
+    if (act) {
+        const int cnt = Cn[q];
+        const float invTH = fdiv(1.0f, th), invTS = fdiv(1.0f, ts);
+        float X0, Y0, VX0, VY0, R0;
+        robot_sim_agent(S, safety, e, N, 0, X0, Y0, VX0, VY0, R0);
+        for (int k = sq; k < cnt; k += 4) {
+            float x, y, vx, vy, r;
+            robot_sim_agent(S, safety, e, N, Nbq[k], x, y, vx, vy, r);
+            Lq[k] = orca_line(X0, Y0, VX0, VY0, R0, x, y, vx, vy, r, invTH, invTS);
+        }
+    }
+    wsync();
+    if (act) {
+        const int cnt = Cn[q];
+        float vmax, ox, oy, rx, ry;
+        robot_pref_velocity(S, e, vmax, ox, oy);
+        const int fail_at = lp2_q<uint64_t>(Lq, cnt, vmax, ox, oy, sq, rx, ry);
+        if (fail_at < cnt) lp3_q<uint64_t>(Lq, Pq, cnt, fail_at, vmax, sq, rx, ry);
+        if (sq == 0) { actions[2 * e] = rx; actions[2 * e + 1] = ry; }
+    }
+}
+
+// Social force: cn_sf_predict_kernel's float64 arithmetic on the robot's FullState and the N belief humans,
+// one lane per env; the ActionXY rounded to float32
+__global__ void __launch_bounds__(64) cn_robot_sf_kernel(cn_state_ptrs S, int E, int N, double A, double B, double KI,
+                                                         double dt, float *__restrict__ actions)
+{
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= E) return;
+    const double px = S.r_px[e], py = S.r_py[e], vx0 = S.r_vx[e], vy0 = S.r_vy[e], rad = S.r_radius[e];
+    const double vpref = S.r_vpref[e];
+    const double gdx = S.r_gx[e] - px, gdy = S.r_gy[e] - py;
+    const double dg = dsqrt(gdx * gdx + gdy * gdy);
+    const double dvx = ddiv(gdx, dg) * vpref, dvy = ddiv(gdy, dg) * vpref;
+    const double cdx = KI * (dvx - vx0), cdy = KI * (dvy - vy0);
+    double ix = 0.0, iy = 0.0;
+    for (int k = 0; k < N; ++k) {
+        const int64_t h = e * N + k;
+        const double ddx = px - S.b_px[h], ddy = py - S.b_py[h];
+        const double d = dsqrt(ddx * ddx + ddy * ddy);
+        const double ex = exp(ddiv(rad + S.b_r[h] - d, B));
+        ix += A * ex * ddiv(ddx, d);
+        iy += A * ex * ddiv(ddy, d);
+    }
+    const double nx = vx0 + (cdx + ix) * dt, ny = vy0 + (cdy + iy) * dt;
+    const double nn = np_norm2(nx, ny);
+    if (nn > vpref) { actions[2 * e] = (float)(ddiv(nx, nn) * vpref); actions[2 * e + 1] = (float)(ddiv(ny, nn) * vpref); }
+    else { actions[2 * e] = (float)nx; actions[2 * e + 1] = (float)ny; }
+}
+
 // One control word of the engine set from the stream (graph mode's draw-all flag after cn_reset /
 // cn_set_state). A kernel, not hipMemsetAsync: captured into a hipGraph it is a kernel node, and this
 // runtime replays memset nodes with stale bytes (cn_graph_node_counts).
@@ -5145,6 +5287,32 @@ int cn_lidar_scan(cn_engine *g, void *stream, int beams, double max_range, doubl
     (void)hipGetLastError();   // a stale error of an earlier call (any library) is not this launch's
     hipLaunchKernelGGL(cn_lidar_scan_kernel, dim3((unsigned)((g->E + G - 1) / G)), dim3(256), 0, (hipStream_t)stream,
                        g->s, g->E, g->N, G, 0.5 * g->c.square_width, beams, npts, max_range, robot_radius, obs);
+    HIPCHK(hipGetLastError());
+    return CN_OK;
+}
+
+int cn_robot_act(cn_engine *g, void *stream, int policy, float *actions)
+{
+    if (!g) return set_err(CN_EINVAL, "null engine");
+    if ((policy != CN_ROBOT_ORCA && policy != CN_ROBOT_SOCIAL_FORCE) || !actions)
+        return set_err(CN_EINVAL, "cn_robot_act: policy CN_ROBOT_ORCA / CN_ROBOT_SOCIAL_FORCE and actions required");
+    if (g->ngroups) return set_err(CN_EUNSUPPORTED, "cn_robot_act: not on a mixed engine");
+    if (g->c.kinematics != CN_HOLONOMIC)
+        return set_err(CN_EUNSUPPORTED, "cn_robot_act: the controllers return ActionXY (holonomic engines only)");
+    const cn_config &c = g->c;
+    const hipStream_t st = (hipStream_t)stream;
+    (void)hipGetLastError();   // a stale error of an earlier call (any library) is not this launch's
+    if (policy == CN_ROBOT_SOCIAL_FORCE)
+        hipLaunchKernelGGL(cn_robot_sf_kernel, dim3((unsigned)((g->E + 63) / 64)), dim3(64), 0, st, g->s, g->E, g->N,
+                           c.sf_A, c.sf_B, c.sf_KI, c.time_step, actions);
+    else if (g->N + 1 > 10)
+        hipLaunchKernelGGL(cn_robot_orca_kd_kernel, dim3((unsigned)((g->E + 15) / 16)), dim3(64), orca_kd_lds(g->N + 1),
+                           st, g->s, g->E, g->N, c.orca_safety_space, (float)c.orca_neighbor_dist,
+                           (float)c.orca_time_horizon, (float)c.time_step, actions);
+    else
+        hipLaunchKernelGGL(cn_robot_orca_kernel, dim3((unsigned)((g->E + 15) / 16)), dim3(64), 0, st, g->s, g->E, g->N,
+                           c.orca_safety_space, (float)c.orca_neighbor_dist, (float)c.orca_time_horizon,
+                           (float)c.time_step, actions);
     HIPCHK(hipGetLastError());
     return CN_OK;
 }

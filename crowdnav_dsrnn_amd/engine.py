@@ -68,6 +68,7 @@ class CrowdNavEngine:
         self.info = torch.zeros((E, abi.INFO_K), dtype=torch.float32, device=dev)
         self.ep_return = torch.zeros((E,), dtype=torch.float64, device=dev)
         self.ep_len = torch.zeros((E,), dtype=torch.int32, device=dev)
+        self.robot_actions = torch.zeros((E, 2), dtype=torch.float32, device=dev)   # robot_act()'s own output
         self._step_args = None   # cached output pointers of step() (the buffers above are never reallocated)
         self._seq_fn = None
 
@@ -173,6 +174,25 @@ class CrowdNavEngine:
         with t.cuda.device(self.device):
             _lib.check(_lib.lib().cn_lidar_scan(self._h, self._stream(), int(beams), float(max_range),
                                                 float(robot_radius), out.data_ptr()))
+        return out
+
+    ROBOT_POLICIES = {"orca": 0, "social_force": 1}   # CN_ROBOT_ORCA / CN_ROBOT_SOCIAL_FORCE
+
+    def robot_act(self, policy, out=None):
+        """The scripted robot's action for the engine's current state (cn_robot_act): (E, 2) float32 on the
+        device, what a fresh policy_factory['orca' | 'social_force'] object predicts from the robot's state and
+        its belief of the humans. Into `out` when given, else into a buffer the engine owns (overwritten by the
+        next call). One launch, no host sync."""
+        t = self.torch
+        if policy not in self.ROBOT_POLICIES:
+            raise ValueError("robot_act: policy %r (one of %s)" % (policy, sorted(self.ROBOT_POLICIES)))
+        if out is None:
+            out = self.robot_actions
+        elif (out.dtype != t.float32 or out.device != self.device or not out.is_contiguous()
+                or out.numel() != self.E * 2):
+            raise ValueError("robot_act: out must be a contiguous float32 (E, 2) tensor on %s" % self.device)
+        with t.cuda.device(self.device):
+            _lib.check(_lib.lib().cn_robot_act(self._h, self._stream(), self.ROBOT_POLICIES[policy], out.data_ptr()))
         return out
 
     def get_state(self):

@@ -316,6 +316,11 @@ class CrowdNavVecEnv:
             out = (self._convgru_obs(out[2]),) + tuple(out[1:])
         return out
 
+    def robot_act(self, policy):
+        """The scripted robot's action ('orca' / 'social_force') for the state the last reset / step returned:
+        (E, 2) float32 on the engine's GPU (CrowdNavEngine.robot_act; no host synchronisation)."""
+        return self.engine.robot_act(policy)
+
     def _state(self):
         if self._state_cache is None:
             self._state_cache = self.engine.get_state()

@@ -15,6 +15,10 @@ update positions and velocities. RVO2 works in float32 (positions, velocities, r
 velocity are cast at the boundary) and returns float32 velocities. Simulators of <= 10 agents run on the
 engine's quad path (`cn_orca_predict`); 11 to 64 agents on the kd-tree path (`cn_orca_predict_kd`, RVO2's
 KdTree neighbour order with the persisted agents_ permutation); more than 64 raise UnsupportedConfig.
+
+`ScriptedRobot(venv, name)` is the other direction: an actor stand-in that drives the ROBOT of a
+CrowdNavVecEnv with 'orca' / 'social_force' computed on the device from the engine's state
+(`cn_robot_act`), for baseline rows of `evaluate()` and expert rollouts without a host round trip.
 """
 import collections
 import ctypes
@@ -235,6 +239,43 @@ def predict_batch(policies, states):
         for k, i in enumerate(idx):
             out[i] = ActionXY(float(r[k, 0]), float(r[k, 1]))
     return out
+
+
+class _ScriptedBase:
+    """The one attribute evaluate() reads of an actor's `base` (it sizes the edge RNN state by it)."""
+
+    def __init__(self, human_num):
+        self.human_num = human_num
+
+
+class ScriptedRobot:
+    """Actor stand-in that drives the robot of a CrowdNavVecEnv with a scripted controller on the device
+    (cn_robot_act): the reference's "for orca and sf" robot (crowd_sim.py:1113-1114 -> robot.py:9-15), whose
+    policy predicts from the robot's own state and its belief of the humans. `name`: 'orca' or
+    'social_force'. With it evaluate() and EpisodeRecorder run a baseline unchanged:
+
+        evaluate(ScriptedRobot(venv, 'orca'), None, venv, E, device, config, logging)
+
+    The env's config keeps robot.policy 'srnn' / 'convgru' (that selects the observation); holonomic only,
+    as the controllers return ActionXY."""
+
+    NAMES = ("orca", "social_force")
+
+    def __init__(self, venv, name):
+        if name not in self.NAMES:
+            raise UnsupportedConfig("ScriptedRobot: %r (one of %s)" % (name, ", ".join(self.NAMES)))
+        config = venv.config
+        if config.action_space.kinematics != "holonomic":
+            raise UnsupportedConfig("ScriptedRobot: action_space.kinematics=%r (the controllers return ActionXY: "
+                                    "holonomic only)" % config.action_space.kinematics)
+        self.venv = venv
+        self.name = name
+        self.base = _ScriptedBase(int(config.sim.human_num))
+
+    def act(self, obs, hxs, masks, deterministic=False):
+        """Policy.act's signature and return shape (value, action, log-prob, hidden state). `obs` is not read:
+        the engine's state is the state `obs` came from."""
+        return None, self.venv.robot_act(self.name), None, hxs
 
 
 policy_factory = {"orca": ORCA, "none": none_policy, "social_force": SOCIAL_FORCE, "srnn": SRNN, "convgru": SRNN}

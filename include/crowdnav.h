@@ -31,6 +31,8 @@
  *   cn_gae         ⟵ RolloutStorage.compute_returns with use_gae (storage.py:132-177), one launch per rollout
  *   cn_orca_predict / cn_orca_predict_kd / cn_social_force_predict ⟵ the agent policy plugin
  *                   policy_factory[name](config).predict(JointState) (crowd_nav/policy/policy_factory.py:1-17)
+ *   cn_robot_act     ⟵ Robot.act of a scripted ('orca' / 'social_force') robot on its belief
+ *                   (crowd_sim/envs/utils/robot.py:9-15, crowd_sim.py:1113-1114,1185-1188), every env in one launch
  *   cn_lidar_obs     ⟵ CrowdSimDict.generate_ob's 'convgru' observation (crowd_sim_dict.py:96-101) with
  *                   LidarSensor.sensor_spin (crowd_sim/envs/utils/lidarv2.py:398-427) evaluated at reset
  *   cn_lidar_scan    ⟵ the scan CrowdSimDict.step() takes every step and discards (crowd_sim_dict.py:224-251):
@@ -458,6 +460,33 @@ int cn_orca_predict_kd(void *stream, int64_t n, int A, const float *agents, cons
                        float time_horizon, float time_step, uint8_t *perm, float *out);
 int cn_social_force_predict(void *stream, int64_t n, int M, const double *self, const double *others, double A,
                             double B, double KI, double time_step, double *out);
+
+/* Scripted robot baselines on the device (the "for orca and sf" robot the reference's env anticipates,
+ * crowd_sim.py:1113-1114,1185-1188 -> robot.py:9-15, and then crashes on: those policies have no clip_action).
+ * actions [E][2] float32 = for every env e, rounded to float32, what a FRESH policy object returns for the
+ * engine's current state:
+ *   policy_factory[name](config).predict(JointState(robot FullState (r_px, r_py, r_vx, r_vy, r_radius, r_gx,
+ *       r_gy, r_vpref, r_theta), [ObservableState(b_px, b_py, b_vx, b_vy, b_r) of the N humans in index order]))
+ * i.e. the robot acts on its belief (last_human_states). CN_ROBOT_ORCA: ORCA.predict (orca.py:64-139) as
+ * cn_orca_predict computes it -- positions, velocities and radii (float)((radius + 0.01) + safety_space) cast
+ * to float32, maxSpeed (float)r_vpref, the preferred velocity towards the goal in float64 (normalised only
+ * above speed 1) then float32; neighbor_dist / time_horizon / time_step from the engine's cn_config; N + 1 <= 10
+ * agents on the quad path, more through RVO2's KdTree in a fresh simulator's identity agent order
+ * (cn_orca_predict_kd with perm = NULL). CN_ROBOT_SOCIAL_FORCE: SOCIAL_FORCE.predict (social_force.py:11-66)
+ * in float64 with sf_A / sf_B / sf_KI / time_step from the cn_config, as cn_social_force_predict.
+ * A pure function of the state blob, read in place: nothing is held between calls; one launch, no allocation,
+ * no synchronisation, no memset (graph-capturable next to cn_step). Call it after cn_reset / cn_step /
+ * cn_set_state on the same stream and feed `actions` to cn_step for a closed loop without a host round trip.
+ * Two deliberate deviations from ONE reference ORCA object kept alive over an episode:
+ *   - the simulator is new at every call, so the KdTree agent order does not persist from step to step (it
+ *     only orders equidistant neighbours, and only when N + 1 > 10);
+ *   - the radii follow the current belief instead of being frozen at the object's first predict (identical
+ *     unless humans.random_radii).
+ * CN_EUNSUPPORTED: a unicycle engine (the controllers return ActionXY) or a mixed engine; CN_EINVAL: an
+ * unknown policy or actions = NULL. */
+#define CN_ROBOT_ORCA 0
+#define CN_ROBOT_SOCIAL_FORCE 1
+int cn_robot_act(cn_engine *eng, void *stream, int policy, float *actions);
 
 /* Test hooks of the kd-tree path's resumable spawns (the spawn waves that draw upcoming episodes park a
  * crowded spawn between two humans once a wave has worked `cycles` clock cycles in a launch, and a later

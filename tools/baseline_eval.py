@@ -1,0 +1,70 @@
+#!/usr/bin/env python
+"""The scripted-robot baseline rows: evaluate() with policy_factory.ScriptedRobot ('orca', 'social_force').
+
+The reference's default test configuration (crowd_nav/configs/config.py: 500 test episodes, 5 ORCA humans,
+holonomic robot, circle radius 6, the four default test scenarios -- taken round-robin by env here, where the
+reference draws one per reset with the unseeded `random` module), with the robot invisible to the humans (the
+default) and visible. The robot acts on its belief of the humans, every step computed on the device
+(cn_robot_act); no host round trip except evaluate()'s own end-of-run check every 8 steps.
+Prints one JSON line per (policy, visibility): success / collision / timeout rates, the mean navigation time of
+the successful episodes and the wall time of the run. Needs a GPU.
+
+Usage: python tools/baseline_eval.py [--envs 100] [--test-size 500] [--humans 5] [--out FILE]
+"""
+import argparse
+import json
+import logging
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import torch  # noqa: E402
+
+from crowdnav_dsrnn_amd.config import Config, clone_config  # noqa: E402
+from crowdnav_dsrnn_amd.envs import CrowdNavVecEnv  # noqa: E402
+from crowdnav_dsrnn_amd.evaluation import evaluate  # noqa: E402
+from crowdnav_dsrnn_amd.policy_factory import ScriptedRobot  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--envs", type=int, default=100)
+    ap.add_argument("--test-size", type=int, default=500)
+    ap.add_argument("--humans", type=int, default=5)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("baseline_eval: needs a GPU")
+    log = logging.getLogger("baseline_eval")
+    log.addHandler(logging.NullHandler())
+    log.propagate = False
+    lines = []
+    for visible in (False, True):
+        for name in ScriptedRobot.NAMES:
+            c = clone_config(Config())
+            c.sim.human_num = args.humans
+            c.env.test_size = args.test_size
+            c.robot.visible = visible
+            E = args.envs
+            envs = CrowdNavVecEnv(c, E, c.env.seed, "cuda:0", allow_early_resets=True, nenv=E, phase="test")
+            t0 = time.time()
+            evaluate(ScriptedRobot(envs, name), None, envs, E, "cuda:0", c, log, keep_traces=False, verbose=False)
+            wall = time.time() - t0
+            last = evaluate.last
+            nav = last["metrics"]["navigation time"]
+            rec = {"robot": name, "robot_visible": visible, "humans": args.humans, "episodes": args.test_size,
+                   "envs": E, "success_rate": round(last["success_rate"], 3),
+                   "collision_rate": round(last["collision_rate"], 3), "timeout_rate": round(last["timeout_rate"], 3),
+                   "nav_time_mean_s": round(float(nav[0]), 2), "nav_time_std_s": round(float(nav[1]), 2),
+                   "wall_s": round(wall, 2)}
+            lines.append(json.dumps(rec))
+            print(lines[-1], flush=True)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
