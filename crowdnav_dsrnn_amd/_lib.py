@@ -37,6 +37,17 @@ class GruStepSeg(ctypes.Structure):
                 ("g2", ctypes.c_int64), ("ld2", ctypes.c_int64)]
 
 
+class RolloutOut(ctypes.Structure):
+    """cn_rollout_out (include/crowdnav.h): the per-step records of a cn_rollout call (device pointers)."""
+    _fields_ = [("actions", ctypes.c_void_p), ("robot_node", ctypes.c_void_p), ("temporal_edges", ctypes.c_void_p),
+                ("spatial_edges", ctypes.c_void_p), ("reward", ctypes.c_void_p), ("done", ctypes.c_void_p),
+                ("event", ctypes.c_void_p), ("info", ctypes.c_void_p), ("ep_return", ctypes.c_void_p),
+                ("ep_len", ctypes.c_void_p), ("flags", ctypes.c_int32)]
+
+
+ROLLOUT_OBS_EVERY_STEP = 1   # CN_ROLLOUT_OBS_EVERY_STEP
+
+
 class NativeLibraryMissing(RuntimeError):
     pass
 
@@ -120,6 +131,9 @@ def lib():
     if hasattr(L, "cn_robot_act") or not os.environ.get("CN_LIB_PATH"):   # (an older A/B library lacks it)
         L.cn_robot_act.argtypes = [vp, vp, ctypes.c_int, vp]
         L.cn_robot_act.restype = i32
+    if hasattr(L, "cn_rollout") or not os.environ.get("CN_LIB_PATH"):   # (an older A/B library lacks it)
+        L.cn_rollout.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(RolloutOut), ctypes.POINTER(i32)]
+        L.cn_rollout.restype = i32
     L.cn_attn_pool_fwd.argtypes = [vp, i64, ctypes.c_int, ctypes.c_int] + [vp] * 3
     L.cn_attn_pool_bwd.argtypes = [vp, i64, ctypes.c_int, ctypes.c_int] + [vp] * 5
     try:
@@ -199,6 +213,7 @@ EXPORTED = ["cn_last_error", "cn_version", "cn_config_validate", "cn_create", "c
             "cn_spatial_attn_bwd", "cn_wgrad_work_elems", "cn_wgrad",
             "cn_gru_bias_blocks", "cn_gru_bwd_step_bias", "cn_gru_bwd_step_gates", "cn_gru_bias_work_elems", "cn_gru_bias_reduce",
             "cn_gru_bwd_seq_work_elems", "cn_gru_fwd_step_group", "cn_gru_fwd_seq", "cn_gru_bwd_seq", "cn_gaussian_act", "cn_gae",
-            "cn_set_graph_mode", "cn_graph_node_counts", "cn_lidar_obs", "cn_lidar_scan", "cn_robot_act", "cn_debug_disc_quad",
+            "cn_set_graph_mode", "cn_graph_node_counts", "cn_lidar_obs", "cn_lidar_scan", "cn_robot_act", "cn_rollout",
+            "cn_debug_disc_quad",
             "cn_debug_orca", "cn_debug_copy64", "cn_orca_predict", "cn_orca_predict_kd", "cn_social_force_predict",
             "cn_debug_set_spawn_budget", "cn_debug_spawn_stats", "cn_debug_set_seq_chunk"]

@@ -2484,6 +2484,88 @@ __device__ __forceinline__ void pend_waves(const PendLaunch &pl, const cn_state_
 }
 
 // ------------------------------------------------------------------------------------------------
+// the scripted robot's device functions (cn_robot_act's kernels below; cn_step_kernel's rollout variant)
+// ------------------------------------------------------------------------------------------------
+// Agent j of the robot's RVO2 simulator in float32 as ORCA._frame casts it (orca.py:91-115): j = 0 the robot,
+// j >= 1 the belief of human j - 1; radius (float)((radius + 0.01) + safety_space).
+__device__ __forceinline__ void robot_sim_agent(const cn_state_ptrs &S, double safety, int64_t e, int N, int j,
+                                                float &x, float &y, float &vx, float &vy, float &r)
+{
+    if (j == 0) {
+        x = (float)S.r_px[e]; y = (float)S.r_py[e]; vx = (float)S.r_vx[e]; vy = (float)S.r_vy[e];
+        r = (float)((S.r_radius[e] + 0.01) + safety);
+    } else {
+        const int64_t h = e * N + (j - 1);
+        x = (float)S.b_px[h]; y = (float)S.b_py[h]; vx = (float)S.b_vx[h]; vy = (float)S.b_vy[h];
+        r = (float)((S.b_r[h] + 0.01) + safety);
+    }
+}
+
+// maxSpeed and the preferred velocity (orca.py:118-122): float64 towards the goal, normalised only above
+// speed 1 (np.linalg.norm), then float32
+__device__ __forceinline__ void robot_pref_velocity(const cn_state_ptrs &S, int64_t e, float &vmax, float &ox, float &oy)
+{
+    const double vx = S.r_gx[e] - S.r_px[e], vy = S.r_gy[e] - S.r_py[e];
+    const double speed = np_norm2(vx, vy);
+    vmax = (float)S.r_vpref[e];
+    if (speed > 1) { ox = (float)ddiv(vx, speed); oy = (float)ddiv(vy, speed); }
+    else { ox = (float)vx; oy = (float)vy; }
+}
+
+// The two halves of ORCA.predict on the quad path (N + 1 <= 10 agents), quad-cooperative, with a wave-level LDS
+// ordering point (wsync) between them at the caller: the ORCA lines of env e's robot into Lq [<= 9] (returns
+// their number), then RVO2's linear programs on them. Every lane of the quad gets the new velocity.
+// Shared by cn_robot_orca_kernel and cn_step_kernel's rollout variant: one arithmetic, bit for bit.
+__device__ __forceinline__ int robot_orca_lines(const cn_state_ptrs &S, double safety, int64_t e, int N, int sq, float nd,
+                                                float th, float ts, float4 *Lq)
+{
+    float X0, Y0, VX0, VY0, R0;
+    robot_sim_agent(S, safety, e, N, 0, X0, Y0, VX0, VY0, R0);
+    return orca_lines_quad(
+        [&](int k, float &x, float &y, float &vx, float &vy, float &r) {
+            robot_sim_agent(S, safety, e, N, k + 1, x, y, vx, vy, r);
+        },
+        N, sq, X0, Y0, VX0, VY0, R0, nd * nd, fdiv(1.0f, th), fdiv(1.0f, ts), Lq);
+}
+
+__device__ __forceinline__ void robot_orca_solve(const cn_state_ptrs &S, int64_t e, int cnt, int sq, float4 *Lq, float &rx,
+                                                 float &ry)
+{
+    float vmax, ox, oy;
+    robot_pref_velocity(S, e, vmax, ox, oy);
+    float4 R[3];
+#pragma unroll
+    for (int u = 0; u < 3; ++u) R[u] = sq + 4 * u < cnt ? Lq[sq + 4 * u] : make_float4(0.f, 0.f, 0.f, 0.f);
+    const int fail_at = lp2_r<3>(R, cnt, vmax, ox, oy, sq, rx, ry);
+    if (fail_at < cnt) lp3_r<3>(R, Lq, cnt, fail_at, vmax, sq, rx, ry);
+}
+
+// SOCIAL_FORCE.predict (social_force.py:11-66) of env e's robot on its FullState and the N belief humans:
+// cn_sf_predict_kernel's float64 arithmetic up to the new velocity (nx, ny), its norm nn and the robot's v_pref;
+// the caller clips to v_pref and rounds the ActionXY to float32 (as cn_robot_sf_kernel does). One lane per env.
+__device__ __forceinline__ void robot_sf_velocity(const cn_state_ptrs &S, int64_t e, int N, double A, double B, double KI,
+                                                  double dt, double &nx, double &ny, double &nn, double &vpref)
+{
+    const double px = S.r_px[e], py = S.r_py[e], vx0 = S.r_vx[e], vy0 = S.r_vy[e], rad = S.r_radius[e];
+    vpref = S.r_vpref[e];
+    const double gdx = S.r_gx[e] - px, gdy = S.r_gy[e] - py;
+    const double dg = dsqrt(gdx * gdx + gdy * gdy);
+    const double dvx = ddiv(gdx, dg) * vpref, dvy = ddiv(gdy, dg) * vpref;
+    const double cdx = KI * (dvx - vx0), cdy = KI * (dvy - vy0);
+    double ix = 0.0, iy = 0.0;
+    for (int k = 0; k < N; ++k) {
+        const int64_t h = e * N + k;
+        const double ddx = px - S.b_px[h], ddy = py - S.b_py[h];
+        const double d = dsqrt(ddx * ddx + ddy * ddy);
+        const double ex = exp(ddiv(rad + S.b_r[h] - d, B));
+        ix += A * ex * ddiv(ddx, d);
+        iy += A * ex * ddiv(ddy, d);
+    }
+    nx = vx0 + (cdx + ix) * dt; ny = vy0 + (cdy + iy) * dt;
+    nn = np_norm2(nx, ny);
+}
+
+// ------------------------------------------------------------------------------------------------
 // kernel A
 // ------------------------------------------------------------------------------------------------
 struct StepArgs {
@@ -2507,6 +2589,8 @@ struct StepArgs {
     union {
         uint32_t *ctl;
         int64_t action_stride;   // SEQ: step t takes the actions at actions + t * action_stride
+        // ROBOT (cn_rollout's launches; their action stride is always 2 * E): CN_ROBOT_* | cn_rollout_out::flags << 8
+        int64_t rollout;
     };
     uint32_t *plist_base;  // [3][E + 64][4] spawn lists: {env, reset_count, case_counter lo, hi} after the reset
     uint32_t *rlist_base;   // [3][2E + 64][4] parked-spawn lists
@@ -2572,7 +2656,13 @@ __device__ inline float bbox_dist(float x, float y, float mnx, float mxx, float 
 // its own workgroup only, and over a chunk the workgroups' totals even out. Every step reads the state the
 // previous one wrote through global memory (written by other waves of the same workgroup: visible after the
 // barrier) and re-initialises every LDS word and register it uses, exactly as a launch of its own would.
-template <bool KD, bool PHX, bool MIX, bool DEVSEQ = false, bool SEQ = false>
+// ROBOT: a launch of cn_rollout (a SEQ launch of 1..seq_chunk steps): before phase 0 of every step wave 0 computes
+// the scripted robot's actions of the workgroup's envs from the state the previous step (or launch) left in global
+// memory, with cn_robot_act's device functions (ORCA's quad path: one quad per env, EPB <= 16 envs; social force: one
+// lane per env), stores them to row `step` of g.actions and hands them to phase 0 through LDS. Every step records
+// its outputs at row `step` of [nsteps][E][..] buffers (the observation only with CN_ROLLOUT_OBS_EVERY_STEP;
+// otherwise the launch's last step stores it to a single row, as the SEQ kernels do).
+template <bool KD, bool PHX, bool MIX, bool DEVSEQ = false, bool SEQ = false, bool ROBOT = false>
 __global__ void __launch_bounds__(CN_BLK, 3) cn_step_kernel(StepArgs g, cn_config c)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -2720,14 +2810,60 @@ __global__ void __launch_bounds__(CN_BLK, 3) cn_step_kernel(StepArgs g, cn_confi
     const double dt = c.time_step;
 
     const float *actions = g.actions;
-    if constexpr (SEQ) actions += (int64_t)step * g.action_stride;
+    if constexpr (ROBOT) actions += (int64_t)step * (2 * (int64_t)g.E);
+    else if constexpr (SEQ) actions += (int64_t)step * g.action_stride;
     // SEQ: the caller reads the outputs of the launch's last step only (every step would overwrite them), so the
     // earlier steps neither convert nor store them (wave-uniform; state writes are not outputs and stay)
+    // ROBOT: every step's outputs are recorded, at row `step` (orw_e: its first env row; orw_o: the observation's,
+    // row 0 of a single-row buffer without CN_ROLLOUT_OBS_EVERY_STEP, which then holds the last step's as above)
 #if CN_SEQ_EMIT_LAST
-    const bool emit = !SEQ || step == g.nsteps - 1;
+    const bool emit = !SEQ || ROBOT || step == g.nsteps - 1;
 #else
     const bool emit = true;
 #endif
+    const bool obs_rows = ROBOT && ((g.rollout >> 8) & CN_ROLLOUT_OBS_EVERY_STEP) != 0;
+    const bool emit_obs = ROBOT ? (obs_rows || step == g.nsteps - 1) : emit;
+    const int64_t orw_e = ROBOT ? (int64_t)step * g.E : 0;
+    const int64_t orw_o = obs_rows ? orw_e : 0;
+    if constexpr (ROBOT) {
+        // ---- the scripted robot: wave 0, from the global state (this workgroup's own envs; its previous step's
+        // stores, an auto-reset's included, are visible after that step's closing barrier). The ORCA lines lie over
+        // the step's ORCA scratch (16 envs x 9 float4 = 2304 B at o_lines, idle until phase 2 and smaller than one
+        // RNG region, so SL::app behind the plan is out of reach). A quad is whole or absent (q < nenv_here).
+        if ((tid >> 6) == 0) {
+            float *const arow = const_cast<float *>(actions);
+            if ((int)(g.rollout & 0xff) == CN_ROBOT_SOCIAL_FORCE) {
+                if (tid < nenv_here) {
+                    double nx, ny, nn, vpref;   // (the clip and the rounding of cn_robot_sf_kernel)
+                    robot_sf_velocity(S, e0 + tid, N, c.sf_A, c.sf_B, c.sf_KI, c.time_step, nx, ny, nn, vpref);
+                    float ax, ay;
+                    if (nn > vpref) { ax = (float)(ddiv(nx, nn) * vpref); ay = (float)(ddiv(ny, nn) * vpref); }
+                    else { ax = (float)nx; ay = (float)ny; }
+                    arow[2 * (int64_t)(e0 + tid)] = ax; arow[2 * (int64_t)(e0 + tid) + 1] = ay;
+                    sl.act[tid] = ax; sl.act[EPB + tid] = ay;
+                }
+            } else {
+                const int q = tid >> 2, sq = tid & 3;
+                const bool act = q < nenv_here;
+                const int64_t e = e0 + q;
+                float4 *const Lq = sl.lines + q * 9;
+                int cnt = 0;
+                if (act)
+                    cnt = robot_orca_lines(S, c.orca_safety_space, e, N, sq, (float)c.orca_neighbor_dist,
+                                           (float)c.orca_time_horizon, (float)c.time_step, Lq);
+                wsync();
+                if (act) {
+                    float rx, ry;
+                    robot_orca_solve(S, e, cnt, sq, Lq, rx, ry);
+                    if (sq == 0) {
+                        arow[2 * e] = rx; arow[2 * e + 1] = ry;
+                        sl.act[q] = rx; sl.act[EPB + q] = ry;
+                    }
+                }
+            }
+        }
+        __syncthreads();
+    }
     STAMP_A(0);
     // ---- phase 0: load state into LDS -----------------------------------------------------------
     // values needed in later phases are loaded here, so their latency overlaps phase 0 (doubles parked
@@ -2768,7 +2904,9 @@ __global__ void __launch_bounds__(CN_BLK, 3) cn_step_kernel(StepArgs g, cn_confi
         const uint32_t fl = S.flags[ge];
         pre_epl = S.ep_len[ge]; pre_sc = S.scenario[ge]; pre_ovf = S.overflow[ge];
         const int64_t oa = orow(ov, ge);   // the env's row in the caller's buffers
-        float a0 = actions[oa * 2], a1 = actions[oa * 2 + 1];
+        float a0, a1;
+        if constexpr (ROBOT) { a0 = sl.act[re]; a1 = sl.act[EPB + re]; }   // (wave 0's, before the barrier above)
+        else { a0 = actions[oa * 2]; a1 = actions[oa * 2 + 1]; }
         asm volatile("" ::: "memory");
         RF(sl, R_PX, re, EPB) = rv[R_PX]; RF(sl, R_PY, re, EPB) = rv[R_PY];
         RF(sl, R_GX, re, EPB) = rv[R_GX]; RF(sl, R_GY, re, EPB) = rv[R_GY];
@@ -3007,7 +3145,7 @@ __global__ void __launch_bounds__(CN_BLK, 3) cn_step_kernel(StepArgs g, cn_confi
             else reward = (double)(((float)reward + r_spin) + r_back);
         }
         if (emit && g.info) {
-            float *info = g.info + orow(ov, ge) * CN_INFO_K;
+            float *info = g.info + (orw_e + orow(ov, ge)) * CN_INFO_K;
             info[CN_INFO_AGG_NAV_TIME] = (float)agg;
             info[CN_INFO_PERSONAL_VIOLATION] = dmin < c.min_personal_space ? 1.0f : 0.0f;
             info[CN_INFO_JERK_COST] = (float)RF(sl, R_JERK, re, EPB);
@@ -3025,7 +3163,7 @@ __global__ void __launch_bounds__(CN_BLK, 3) cn_step_kernel(StepArgs g, cn_confi
         const int32_t epl = pre_epl + 1;
         S.ep_return[ge] = epr; S.ep_len[ge] = epl;
         if (emit) {
-            const int64_t oe = orow(ov, ge);
+            const int64_t oe = orw_e + orow(ov, ge);
             if (g.reward) g.reward[oe] = (float)reward;
             if (g.done) g.done[oe] = (uint8_t)done;
             if (g.event) g.event[oe] = (int8_t)event;
@@ -3496,8 +3634,8 @@ __global__ void __launch_bounds__(CN_BLK, 3) cn_step_kernel(StepArgs g, cn_confi
         const double bpx = hst_ref(tid, 2), bpy = hst_ref(tid, 3);
         S.b_px[gh] = bpx; S.b_py[gh] = bpy; S.b_vx[gh] = hst_ref(tid, 4); S.b_vy[gh] = hst_ref(tid, 5);
         S.b_r[gh] = hst_ref(tid, 6);
-        if (emit) {
-            const int64_t oh = orow(ov, e0 + el) * ov.NS + i;
+        if (emit_obs) {
+            const int64_t oh = (orw_o + orow(ov, e0 + el)) * ov.NS + i;
             g.spatial[oh * 2] = (float)(bpx - RF(sl, R_NX, el, EPB));
             g.spatial[oh * 2 + 1] = (float)(bpy - RF(sl, R_NY, el, EPB));
         }
@@ -3531,11 +3669,11 @@ __global__ void __launch_bounds__(CN_BLK, 3) cn_step_kernel(StepArgs g, cn_confi
             nan |= (f & 0x80000000u) != 0;
             vr_viol += (k < kv && (f & LF_VR)) ? 1 : 0;
         }
-        if (emit && g.info) g.info[orow(ov, ge) * CN_INFO_K + CN_INFO_PATH_VIOLATION] = (float)vr_viol;
+        if (emit && g.info) g.info[(orw_e + orow(ov, ge)) * CN_INFO_K + CN_INFO_PATH_VIOLATION] = (float)vr_viol;
         if (nan) flags2 |= CN_FLAG_NAN;
         S.flags[ge] = flags2;
-        if (emit) {
-            const int64_t oe = orow(ov, ge);
+        if (emit_obs) {
+            const int64_t oe = orw_o + orow(ov, ge);
             float *rn = g.robot_node + oe * 7;
             rn[0] = (float)nx; rn[1] = (float)ny; rn[2] = (float)RF(sl, R_RAD, re, EPB);
             rn[3] = (float)RF(sl, R_GX, re, EPB); rn[4] = (float)RF(sl, R_GY, re, EPB);
@@ -3611,7 +3749,10 @@ __global__ void __launch_bounds__(CN_BLK, 3) cn_step_kernel(StepArgs g, cn_confi
             ResetOut o;
             o.s = G.s; o.robot_node = G.robot_node; o.temporal = G.temporal; o.spatial = G.spatial;
             o.case_size = G.case_size; o.ov = ov;
-            if (SEQ && !emit) o.robot_node = nullptr;   // (write_reset<OBS_OPT>: no first observation)
+            if constexpr (ROBOT) {   // the new episode's first observation goes to this step's row as well
+                o.robot_node += orw_o * 7; o.temporal += orw_o * 2; o.spatial += orw_o * ov.NS * 2;
+            }
+            if (SEQ && !emit_obs) o.robot_node = nullptr;   // (write_reset<OBS_OPT>: no first observation)
             const uint32_t need = sl.rflag[EPB + q] & 7u;
             const int64_t e = e0 + q;
             STAMP_B(e, 0);
@@ -4409,32 +4550,8 @@ __global__ void __launch_bounds__(64) cn_sf_predict_kernel(int64_t n, int M, con
 // b_vx, b_vy, b_r) of the N humans in index order])) of a fresh policy object per env, rounded to float32.
 // Pure functions of the state (nothing held between calls), one launch each.
 // ------------------------------------------------------------------------------------------------
-// Agent j of the robot's RVO2 simulator in float32 as ORCA._frame casts it (orca.py:91-115): j = 0 the robot,
-// j >= 1 the belief of human j - 1; radius (float)((radius + 0.01) + safety_space).
-__device__ __forceinline__ void robot_sim_agent(const cn_state_ptrs &S, double safety, int64_t e, int N, int j,
-                                                float &x, float &y, float &vx, float &vy, float &r)
-{
-    if (j == 0) {
-        x = (float)S.r_px[e]; y = (float)S.r_py[e]; vx = (float)S.r_vx[e]; vy = (float)S.r_vy[e];
-        r = (float)((S.r_radius[e] + 0.01) + safety);
-    } else {
-        const int64_t h = e * N + (j - 1);
-        x = (float)S.b_px[h]; y = (float)S.b_py[h]; vx = (float)S.b_vx[h]; vy = (float)S.b_vy[h];
-        r = (float)((S.b_r[h] + 0.01) + safety);
-    }
-}
-
-// maxSpeed and the preferred velocity (orca.py:118-122): float64 towards the goal, normalised only above
-// speed 1 (np.linalg.norm), then float32
-__device__ __forceinline__ void robot_pref_velocity(const cn_state_ptrs &S, int64_t e, float &vmax, float &ox, float &oy)
-{
-    const double vx = S.r_gx[e] - S.r_px[e], vy = S.r_gy[e] - S.r_py[e];
-    const double speed = np_norm2(vx, vy);
-    vmax = (float)S.r_vpref[e];
-    if (speed > 1) { ox = (float)ddiv(vx, speed); oy = (float)ddiv(vy, speed); }
-    else { ox = (float)vx; oy = (float)vy; }
-}
-
+// (robot_sim_agent, robot_pref_velocity, robot_orca_lines / robot_orca_solve and robot_sf_velocity are defined above
+// cn_step_kernel, whose rollout variant computes the same actions inside its multi-step launches)
 // ORCA, N + 1 <= 10 agents: cn_orca_kernel's quad path (one quad per env, 16 envs per 64-lane workgroup).
 // `act` depends on the quad alone, so a quad is whole or absent and its control flow uniform (DESIGN.md §4,
 // "Cross-lane reads"): the quad's 4 lanes read the same state words.
@@ -4446,24 +4563,11 @@ __global__ void __launch_bounds__(64) cn_robot_orca_kernel(cn_state_ptrs S, int 
     const int64_t e = (int64_t)blockIdx.x * 16 + q;
     const bool act = e < E;
     int cnt = 0;
-    if (act) {
-        float X0, Y0, VX0, VY0, R0;
-        robot_sim_agent(S, safety, e, N, 0, X0, Y0, VX0, VY0, R0);
-        cnt = orca_lines_quad(
-            [&](int k, float &x, float &y, float &vx, float &vy, float &r) {
-                robot_sim_agent(S, safety, e, N, k + 1, x, y, vx, vy, r);
-            },
-            N, sq, X0, Y0, VX0, VY0, R0, nd * nd, fdiv(1.0f, th), fdiv(1.0f, ts), Ls[q]);
-    }
+    if (act) cnt = robot_orca_lines(S, safety, e, N, sq, nd, th, ts, Ls[q]);
     wsync();
     if (act) {
-        float vmax, ox, oy, rx, ry;
-        robot_pref_velocity(S, e, vmax, ox, oy);
-        float4 R[3];
-#pragma unroll
-        for (int u = 0; u < 3; ++u) R[u] = sq + 4 * u < cnt ? Ls[q][sq + 4 * u] : make_float4(0.f, 0.f, 0.f, 0.f);
-        const int fail_at = lp2_r<3>(R, cnt, vmax, ox, oy, sq, rx, ry);
-        if (fail_at < cnt) lp3_r<3>(R, Ls[q], cnt, fail_at, vmax, sq, rx, ry);
+        float rx, ry;
+        robot_orca_solve(S, e, cnt, sq, Ls[q], rx, ry);
         if (sq == 0) { actions[2 * e] = rx; actions[2 * e + 1] = ry; }
     }
 }
@@ -4524,23 +4628,8 @@ __global__ void __launch_bounds__(64) cn_robot_sf_kernel(cn_state_ptrs S, int E,
 {
     const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= E) return;
-    const double px = S.r_px[e], py = S.r_py[e], vx0 = S.r_vx[e], vy0 = S.r_vy[e], rad = S.r_radius[e];
-    const double vpref = S.r_vpref[e];
-    const double gdx = S.r_gx[e] - px, gdy = S.r_gy[e] - py;
-    const double dg = dsqrt(gdx * gdx + gdy * gdy);
-    const double dvx = ddiv(gdx, dg) * vpref, dvy = ddiv(gdy, dg) * vpref;
-    const double cdx = KI * (dvx - vx0), cdy = KI * (dvy - vy0);
-    double ix = 0.0, iy = 0.0;
-    for (int k = 0; k < N; ++k) {
-        const int64_t h = e * N + k;
-        const double ddx = px - S.b_px[h], ddy = py - S.b_py[h];
-        const double d = dsqrt(ddx * ddx + ddy * ddy);
-        const double ex = exp(ddiv(rad + S.b_r[h] - d, B));
-        ix += A * ex * ddiv(ddx, d);
-        iy += A * ex * ddiv(ddy, d);
-    }
-    const double nx = vx0 + (cdx + ix) * dt, ny = vy0 + (cdy + iy) * dt;
-    const double nn = np_norm2(nx, ny);
+    double nx, ny, nn, vpref;
+    robot_sf_velocity(S, e, N, A, B, KI, dt, nx, ny, nn, vpref);
     if (nn > vpref) { actions[2 * e] = (float)(ddiv(nx, nn) * vpref); actions[2 * e + 1] = (float)(ddiv(ny, nn) * vpref); }
     else { actions[2 * e] = (float)nx; actions[2 * e + 1] = (float)ny; }
 }
@@ -4975,9 +5064,11 @@ int cn_reset(cn_engine *g, void *stream, float *robot_node, float *temporal, flo
 // cn_step_seq (a plain quad-path engine outside graph mode, pend_all == 0: seq_fusable), whose step workgroups
 // run nsteps steps with the actions at actions + t * action_stride. g->nstep counts LAUNCHES (the triple-buffer
 // index of the spawn lists, the launch id, graph mode's hand-over); cn_profile's window counts STEPS.
+// rollout >= 0 (cn_rollout's fused launches, nsteps >= 1, same engines): StepArgs::rollout of the ROBOT kernels,
+// which compute the actions themselves and record every step at row t of the outputs (`actions` is written).
 static int step_launch(cn_engine *g, void *stream, const float *actions, int nsteps, int64_t action_stride,
                        float *robot_node, float *temporal, float *spatial, float *reward, uint8_t *done, int8_t *event,
-                       float *info, double *ep_return, int32_t *ep_len)
+                       float *info, double *ep_return, int32_t *ep_len, int64_t rollout = -1)
 {
     if (!g || !actions || !robot_node || !temporal || !spatial) return set_err(CN_EINVAL, "null argument");
     hipStream_t st = (hipStream_t)stream;
@@ -5025,6 +5116,7 @@ static int step_launch(cn_engine *g, void *stream, const float *actions, int nst
     a.pend.budget = g->spawn_budget * nsteps;
     a.nsteps = nsteps;
     if (nsteps > 1) a.action_stride = action_stride;   // (shares ctl's slot: the SEQ kernels are never graph mode's)
+    if (rollout >= 0) a.rollout = rollout;
     a.pend.stats = g->work_count + 8;
     a.pend.launch_id = (uint32_t)(g->nstep % 0x7ffffffeu) + 1u;   // nonzero, differs from the neighbours'
     const int blocks = (g->E + g->plan.EPB - 1) / g->plan.EPB;
@@ -5051,11 +5143,14 @@ static int step_launch(cn_engine *g, void *stream, const float *actions, int nst
         cn_step_kernel<true, false, false, true>, cn_step_kernel<true, true, false, true>};
     void (*const kern_seq[2])(StepArgs, cn_config) = {   // multi-step launches (plain quad-path engines)
         cn_step_kernel<false, false, false, false, true>, cn_step_kernel<false, true, false, false, true>};
+    void (*const kern_robot[2])(StepArgs, cn_config) = {   // cn_rollout's launches (the same engines)
+        cn_step_kernel<false, false, false, false, true, true>, cn_step_kernel<false, true, false, false, true, true>};
     (void)hipGetLastError();   // a stale error of an earlier call (any library) is not this launch's
-    if (nsteps > 1) {
+    if (nsteps > 1 || rollout >= 0) {
         if (g->devseq || g->rows || g->plan.kd || a.pend.all)
             return set_err(CN_EINVAL, "multi-step launch: plain quad-path engine outside graph mode required");
-        hipLaunchKernelGGL(kern_seq[phx ? 1 : 0], dim3(grid), dim3(g->plan.T), g->a_lds, st, a, g->c);
+        hipLaunchKernelGGL((rollout >= 0 ? kern_robot : kern_seq)[phx ? 1 : 0], dim3(grid), dim3(g->plan.T), g->a_lds, st,
+                           a, g->c);
     } else if (g->devseq)
         hipLaunchKernelGGL(kern_dev[variant >> 1], dim3(grid), dim3(g->plan.T), g->a_lds, st, a, g->c);
     else
@@ -5314,6 +5409,58 @@ int cn_robot_act(cn_engine *g, void *stream, int policy, float *actions)
                            c.orca_safety_space, (float)c.orca_neighbor_dist, (float)c.orca_time_horizon,
                            (float)c.time_step, actions);
     HIPCHK(hipGetLastError());
+    return CN_OK;
+}
+
+// cn_robot_act + cn_step for t = 0..T-1 with every step recorded at row t. Fused (the ROBOT kernels: up to seq_chunk
+// steps per launch, the controller inside the step workgroups) where cn_step_seq's multi-step launches apply and the
+// controller fits the step workgroup; launch pairs otherwise, the first step after cn_reset / cn_set_state included.
+int cn_rollout(cn_engine *g, void *stream, int policy, int T, const cn_rollout_out *out, int32_t *num_launches)
+{
+    if (num_launches) *num_launches = 0;
+    if (!g) return set_err(CN_EINVAL, "null engine");
+    if ((policy != CN_ROBOT_ORCA && policy != CN_ROBOT_SOCIAL_FORCE) || T < 0 || !out || !out->actions ||
+        !out->robot_node || !out->temporal_edges || !out->spatial_edges)
+        return set_err(CN_EINVAL, "cn_rollout: policy CN_ROBOT_ORCA / CN_ROBOT_SOCIAL_FORCE, T >= 0, out with actions "
+                                  "and the observation buffers required");
+    if (g->ngroups) return set_err(CN_EUNSUPPORTED, "cn_rollout: not on a mixed engine");
+    if (g->c.kinematics != CN_HOLONOMIC)
+        return set_err(CN_EUNSUPPORTED, "cn_rollout: the controllers return ActionXY (holonomic engines only)");
+    const int64_t E = g->E, N = g->N;
+    const bool every = (out->flags & CN_ROLLOUT_OBS_EVERY_STEP) != 0;
+    // the controller fits the step workgroup: social force (a lane per env) always, ORCA on its quad path
+    const bool fits = policy == CN_ROBOT_SOCIAL_FORCE || g->N + 1 <= 10;
+    const bool fusable = fits && g->seq_chunk > 1 && !g->rows && !g->devseq && !g->plan.kd;
+    const int64_t rollout = (int64_t)policy | ((int64_t)(out->flags & CN_ROLLOUT_OBS_EVERY_STEP) << 8);
+    int nl = 0;
+    for (int t = 0; t < T;) {
+        const int64_t ro = every ? t : 0;   // the observation's row
+        float *const act = out->actions + t * E * 2;
+        float *const rn = out->robot_node + ro * E * 7, *const te = out->temporal_edges + ro * E * 2;
+        float *const se = out->spatial_edges + ro * E * N * 2;
+        float *const rw = out->reward ? out->reward + t * E : nullptr;
+        uint8_t *const dn = out->done ? out->done + t * E : nullptr;
+        int8_t *const ev = out->event ? out->event + t * E : nullptr;
+        float *const inf = out->info ? out->info + t * E * CN_INFO_K : nullptr;
+        double *const epr = out->ep_return ? out->ep_return + t * E : nullptr;
+        int32_t *const epl = out->ep_len ? out->ep_len + t * E : nullptr;
+        int n = 1, rc;
+        if (fusable && !g->pend_all) {
+            n = T - t < g->seq_chunk ? T - t : g->seq_chunk;
+            // (a launch never straddles the end of cn_profile's window: cn_step_seq)
+            if (g->prof_on && g->prof_n < g->prof_cap && n > g->prof_cap - g->prof_n) n = g->prof_cap - g->prof_n;
+            rc = step_launch(g, stream, act, n, 2 * E, rn, te, se, rw, dn, ev, inf, epr, epl, rollout);
+            nl += 1;
+        } else {
+            rc = cn_robot_act(g, stream, policy, act);
+            if (rc) return rc;
+            rc = cn_step(g, stream, act, rn, te, se, rw, dn, ev, inf, epr, epl);
+            nl += 2;
+        }
+        if (rc) return rc;
+        t += n;
+        if (num_launches) *num_launches = nl;
+    }
     return CN_OK;
 }
 

@@ -71,6 +71,7 @@ class CrowdNavEngine:
         self.robot_actions = torch.zeros((E, 2), dtype=torch.float32, device=dev)   # robot_act()'s own output
         self._step_args = None   # cached output pointers of step() (the buffers above are never reallocated)
         self._seq_fn = None
+        self.seq_chunk = 32   # steps per multi-step launch (the library's CN_SEQ_CHUNK; set_seq_chunk)
 
     @classmethod
     def mixed(cls, cfgs, env_group, device=None):
@@ -195,6 +196,73 @@ class CrowdNavEngine:
             _lib.check(_lib.lib().cn_robot_act(self._h, self._stream(), self.ROBOT_POLICIES[policy], out.data_ptr()))
         return out
 
+    def rollout_buffers(self, T, obs_every_step=True):
+        """Fresh device tensors for rollout(T): the `out` dict without 'num_launches'."""
+        t, E, N, dev = self.torch, self.E, self.N, self.device
+        out = {"actions": t.zeros((T, E, 2), dtype=t.float32, device=dev)}
+        if obs_every_step:
+            out["robot_node"] = t.zeros((T, E, 1, 7), dtype=t.float32, device=dev)
+            out["temporal_edges"] = t.zeros((T, E, 1, 2), dtype=t.float32, device=dev)
+            out["spatial_edges"] = t.zeros((T, E, N, 2), dtype=t.float32, device=dev)
+        else:
+            out.update(self.obs())
+        out["reward"] = t.zeros((T, E), dtype=t.float32, device=dev)
+        out["done"] = t.zeros((T, E), dtype=t.uint8, device=dev)
+        out["event"] = t.zeros((T, E), dtype=t.int8, device=dev)
+        out["info"] = t.zeros((T, E, abi.INFO_K), dtype=t.float32, device=dev)
+        out["ep_return"] = t.zeros((T, E), dtype=t.float64, device=dev)
+        out["ep_len"] = t.zeros((T, E), dtype=t.int32, device=dev)
+        return out
+
+    _ROLLOUT_OPTIONAL = ("reward", "done", "event", "info", "ep_return", "ep_len")
+
+    def rollout(self, policy, T, obs_every_step=True, out=None):
+        """T closed-loop steps of the scripted robot (cn_rollout): robot_act(policy) -> step, every step recorded,
+        with the rows of that eager loop bit for bit. Returns a dict of device tensors: actions (T, E, 2);
+        robot_node / temporal_edges / spatial_edges (T, E, ...) = the observation AFTER step t (with
+        obs_every_step=False: the engine's own single-row buffers, holding the last step's); reward, done, event,
+        info, ep_return, ep_len (T, E, ...); 'num_launches' (int). `out`: a dict from an earlier call (or
+        rollout_buffers) to reuse; of the six per-step records any may be left out or None (not recorded). Where
+        the engine allows it the steps run inside multi-step launches with the controller in the step kernel; no
+        host sync either way."""
+        t = self.torch
+        if policy not in self.ROBOT_POLICIES:
+            raise ValueError("rollout: policy %r (one of %s)" % (policy, sorted(self.ROBOT_POLICIES)))
+        T = int(T)
+        if T < 0:
+            raise ValueError("rollout: T >= 0 required, got %d" % T)
+        E, N = self.E, self.N
+        if out is None:
+            out = self.rollout_buffers(T, obs_every_step)
+        else:
+            out = dict(out)
+        R = 1 if not obs_every_step else T
+        want = {"actions": (T * E * 2, t.float32), "robot_node": (R * E * 7, t.float32),
+                "temporal_edges": (R * E * 2, t.float32), "spatial_edges": (R * E * N * 2, t.float32),
+                "reward": (T * E, t.float32), "done": (T * E, t.uint8), "event": (T * E, t.int8),
+                "info": (T * E * abi.INFO_K, t.float32), "ep_return": (T * E, t.float64), "ep_len": (T * E, t.int32)}
+        ro = _lib.RolloutOut()
+        for k, (n, dt) in want.items():
+            v = out.get(k)
+            if v is None:
+                if k not in self._ROLLOUT_OPTIONAL:
+                    raise ValueError("rollout: out[%r] is required" % k)
+                continue
+            if v.dtype != dt or v.device != self.device or not v.is_contiguous() or v.numel() != n:
+                raise ValueError("rollout: out[%r] must be a contiguous %s tensor of %d elements on %s"
+                                 % (k, dt, n, self.device))
+            setattr(ro, k, v.data_ptr())
+        ro.flags = _lib.ROLLOUT_OBS_EVERY_STEP if obs_every_step else 0
+        nl = ctypes.c_int32(0)
+        if T == 0:   # (empty tensors have no address to pass; cn_rollout launches nothing for T = 0 either)
+            out["num_launches"] = 0
+            return out
+        with t.cuda.device(self.device):
+            _lib.check(_lib.lib().cn_rollout(self._h, self._stream(), self.ROBOT_POLICIES[policy], T,
+                                             ctypes.byref(ro), ctypes.byref(nl)))
+        out["num_launches"] = int(nl.value)
+        return out
+
     def get_state(self):
         """abi.StateView of the engine; a mixed engine: [(rows, StateView of the group)] in group order."""
         buf = np.zeros(self.state_bytes, np.uint8)
@@ -230,6 +298,7 @@ class CrowdNavEngine:
         """Steps per launch of step_seq's multi-step launches (cn_debug_set_seq_chunk); 1 = one step launch per
         step through the single-step kernels. Results do not depend on it."""
         _lib.check(_lib.lib().cn_debug_set_seq_chunk(self._h, int(n)))
+        self.seq_chunk = int(n)
 
     def spawn_stats(self):
         """Cumulative spawn counters (cn_debug_spawn_stats; synchronises): kd-tree path spawns parked before

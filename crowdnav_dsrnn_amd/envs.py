@@ -26,7 +26,7 @@ import time
 import numpy as np
 
 from . import abi, info as info_mod, spaces
-from .config import make_cn_config
+from .config import UnsupportedConfig, make_cn_config
 
 _REGISTRY = {}
 
@@ -320,6 +320,16 @@ class CrowdNavVecEnv:
         """The scripted robot's action ('orca' / 'social_force') for the state the last reset / step returned:
         (E, 2) float32 on the engine's GPU (CrowdNavEngine.robot_act; no host synchronisation)."""
         return self.engine.robot_act(policy)
+
+    def rollout(self, policy, T, obs_every_step=True, out=None):
+        """T closed-loop steps of the scripted robot ('orca' / 'social_force') from the state the last reset / step
+        left, every step recorded (CrowdNavEngine.rollout: a dict of (T, E, ...) tensors on the engine's GPU, no
+        host synchronisation). The recorded observation is the SRNN one, so obs_mode 'srnn' only."""
+        if self.obs_mode != "srnn":
+            raise UnsupportedConfig("rollout: obs_mode=%r (the rollout records the 'srnn' observation only)"
+                                    % self.obs_mode)
+        self._state_cache = None
+        return self.engine.rollout(policy, T, obs_every_step=obs_every_step, out=out)
 
     def _state(self):
         if self._state_cache is None:

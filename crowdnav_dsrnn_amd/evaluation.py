@@ -296,6 +296,58 @@ def evaluate(actor_critic, ob_rms, eval_envs, num_processes, device, config, log
     return _report(r, traces, config, logging, test_size, dt, gamma, side, scenario, eval_envs, verbose)
 
 
+def evaluate_scripted(name, eval_envs, num_processes, device, config, logging, chunk=None, keep_traces=True,
+                      verbose=True):
+    """evaluate() of the scripted robot `name` ('orca' / 'social_force') on whole rollouts: after reset(), rollouts
+    of `chunk` steps (default: the engine's steps per multi-step launch) through ScriptedRobot.rollout, every
+    recorded row fed to the same EpisodeRecorder, the end-of-run check once per chunk, the same report. Episodes
+    past test_size go to the recorder's spare slot, so the steps a chunk runs past the last counted episode do
+    not change the records: they equal evaluate(ScriptedRobot(eval_envs, name), ...)'s."""
+    from .config import UnsupportedConfig
+    from .policy_factory import ScriptedRobot
+
+    ScriptedRobot.check(eval_envs, name)
+    if getattr(eval_envs, "obs_mode", "srnn") != "srnn":
+        raise UnsupportedConfig("evaluate_scripted: obs_mode=%r (the rollout records the 'srnn' observation only)"
+                                % eval_envs.obs_mode)
+    E = eval_envs.num_envs
+    if num_processes != E:
+        raise ValueError("num_processes=%d but the VecEnv holds %d envs" % (num_processes, E))
+    robot = ScriptedRobot(eval_envs, name)
+    dist = _dist()
+    cn = eval_envs.cn_cfg
+    test_size = int(config.env.test_size)
+    side = bool(config.test.side_preference)
+    scenario = None
+    if side:
+        assert len(config.sim.test_sim) == 1
+        scenario = config.sim.test_sim[0]
+    gamma = 0.99
+    dt = float(config.env.time_step)
+    rec = EpisodeRecorder(E, test_size, int(cn.env_offset), int(cn.nenv), eval_envs.engine.device, dt, gamma,
+                          float(config.robot.v_pref), side, scenario, eval_envs.scenario_names, keep_traces)
+    C = int(chunk) if chunk is not None else int(eval_envs.engine.seq_chunk)
+    if C < 1:
+        raise ValueError("evaluate_scripted: chunk >= 1 required, got %d" % C)
+    obs = eval_envs.reset()
+    rec.start(obs)
+    buf = None
+    while True:
+        buf = robot.rollout(C, out=buf)
+        for t in range(C):
+            rec.step({"robot_node": buf["robot_node"][t], "temporal_edges": buf["temporal_edges"][t]},
+                     buf["reward"][t], buf["done"][t], buf["event"][t], buf["info"][t])
+        if rec.finished():
+            break
+    r = rec.host_records(dist)
+    traces = rec.episode_traces() if keep_traces else {}
+    if dist is not None and keep_traces:
+        gathered = [None] * dist.get_world_size()
+        dist.all_gather_object(gathered, traces)
+        traces = {k: v for d in gathered for k, v in d.items()}
+    return _report(r, traces, config, logging, test_size, dt, gamma, side, scenario, eval_envs, verbose)
+
+
 def _report(r, traces, config, logging, test_size, dt, gamma, side, scenario, eval_envs, verbose):
     """The reference's per-episode bookkeeping and logging (evaluation.py:233-332), replayed in episode
     order from the records."""

@@ -261,13 +261,19 @@ class ScriptedRobot:
 
     NAMES = ("orca", "social_force")
 
-    def __init__(self, venv, name):
-        if name not in self.NAMES:
-            raise UnsupportedConfig("ScriptedRobot: %r (one of %s)" % (name, ", ".join(self.NAMES)))
+    @classmethod
+    def check(cls, venv, name):
+        """UnsupportedConfig for an unknown controller or a unicycle config (before anything touches the GPU)."""
+        if name not in cls.NAMES:
+            raise UnsupportedConfig("ScriptedRobot: %r (one of %s)" % (name, ", ".join(cls.NAMES)))
         config = venv.config
         if config.action_space.kinematics != "holonomic":
             raise UnsupportedConfig("ScriptedRobot: action_space.kinematics=%r (the controllers return ActionXY: "
                                     "holonomic only)" % config.action_space.kinematics)
+
+    def __init__(self, venv, name):
+        self.check(venv, name)
+        config = venv.config
         self.venv = venv
         self.name = name
         self.base = _ScriptedBase(int(config.sim.human_num))
@@ -276,6 +282,17 @@ class ScriptedRobot:
         """Policy.act's signature and return shape (value, action, log-prob, hidden state). `obs` is not read:
         the engine's state is the state `obs` came from."""
         return None, self.venv.robot_act(self.name), None, hxs
+
+    def rollout(self, T, obs_every_step=True, out=None):
+        """T closed-loop steps of this controller from the env's current state, every step recorded
+        (CrowdNavVecEnv.rollout -> cn_rollout): a dict of (T, E, ...) device tensors -- actions, the observation
+        after each step, reward, done, event, info, ep_return, ep_len -- and 'num_launches'. Expert pairs are
+        (observation row t-1, actions row t), row -1 being the reset observation. 'srnn' observation only."""
+        self.check(self.venv, self.name)
+        if getattr(self.venv, "obs_mode", "srnn") != "srnn":
+            raise UnsupportedConfig("ScriptedRobot.rollout: obs_mode=%r (the rollout records the 'srnn' observation "
+                                    "only)" % self.venv.obs_mode)
+        return self.venv.rollout(self.name, T, obs_every_step=obs_every_step, out=out)
 
 
 policy_factory = {"orca": ORCA, "none": none_policy, "social_force": SOCIAL_FORCE, "srnn": SRNN, "convgru": SRNN}

@@ -33,6 +33,9 @@
  *                   policy_factory[name](config).predict(JointState) (crowd_nav/policy/policy_factory.py:1-17)
  *   cn_robot_act     ⟵ Robot.act of a scripted ('orca' / 'social_force') robot on its belief
  *                   (crowd_sim/envs/utils/robot.py:9-15, crowd_sim.py:1113-1114,1185-1188), every env in one launch
+ *   cn_rollout       ⟵ the closed loop `action = robot.act(ob); ob, ... = env.step(action)` of a scripted robot
+ *                   over T steps (crowd_nav test loop / expert demonstrations), every step recorded, in
+ *                   multi-step launches with the controller inside the step kernel
  *   cn_lidar_obs     ⟵ CrowdSimDict.generate_ob's 'convgru' observation (crowd_sim_dict.py:96-101) with
  *                   LidarSensor.sensor_spin (crowd_sim/envs/utils/lidarv2.py:398-427) evaluated at reset
  *   cn_lidar_scan    ⟵ the scan CrowdSimDict.step() takes every step and discards (crowd_sim_dict.py:224-251):
@@ -487,6 +490,41 @@ int cn_social_force_predict(void *stream, int64_t n, int M, const double *self, 
 #define CN_ROBOT_ORCA 0
 #define CN_ROBOT_SOCIAL_FORCE 1
 int cn_robot_act(cn_engine *eng, void *stream, int policy, float *actions);
+
+/* Closed-loop scripted rollout: T steps of the scripted robot driving the engine, every step recorded. For
+ * t = 0..T-1 the call does cn_robot_act(eng, stream, policy, actions_t) and then cn_step(eng, stream, actions_t,
+ * ...row t of every output...); every recorded row and the state blob afterwards equal that pair sequence bit for
+ * bit. actions[t] is computed from the state BEFORE step t (right after an auto-reset: the new episode's); an env
+ * that finishes in step t carries its new episode's first observation in row t, as cn_step returns it. The pairing
+ * for imitation data is therefore observation row t-1 -> actions row t (row -1: cn_reset's observation).
+ * Stream-ordered; no allocation, no synchronisation, no memset. *num_launches (host, may be NULL) receives the
+ * number of kernel launches issued.
+ *   Fused path: a plain holonomic engine on the step's quad path (at most 10 agents per simulator) outside graph
+ * mode, with a controller that fits the step workgroup (social force always; ORCA with N + 1 <= 10), runs
+ * ceil(T' / C) launches of up to C = seq_chunk steps (cn_debug_set_seq_chunk; split at the end of a cn_profile
+ * window, as cn_step_seq's): each step workgroup computes the actions of its own envs from the state its previous
+ * step wrote, with cn_robot_act's arithmetic, then steps them, so no workgroup waits for the grid's slowest one
+ * and no controller launch is issued. T' excludes a first step after cn_reset / cn_set_state, which is a pair.
+ *   Everything else cn_robot_act supports (chunk 1, graph mode, > 10 agents per simulator, ORCA at N + 1 > 10) is
+ * issued as T cn_robot_act + cn_step launch pairs from native code with the output pointers advanced to row t:
+ * the same rows.
+ * CN_EUNSUPPORTED: a unicycle or a mixed engine. CN_EINVAL: an unknown policy, T < 0, out / actions / an
+ * observation pointer NULL. All are checked before any launch (*num_launches = 0). T = 0 launches nothing. */
+typedef struct cn_rollout_out {
+    float   *actions;        /* [T][E][2]  required: the controller's action of step t (as cn_robot_act rounds it) */
+    float   *robot_node;     /* obs AFTER step t (what cn_step returns for it): [T][E][7], [T][E][2], [T][E][N][2]   */
+    float   *temporal_edges; /*   when flags & CN_ROLLOUT_OBS_EVERY_STEP; otherwise one row each ([E]..), holding   */
+    float   *spatial_edges;  /*   the last step's observation as cn_step_seq does. Required.                        */
+    float   *reward;         /* [T][E]    any of the following may be NULL                                          */
+    uint8_t *done;           /* [T][E]                                                                               */
+    int8_t  *event;          /* [T][E]                                                                               */
+    float   *info;           /* [T][E][CN_INFO_K]                                                                    */
+    double  *ep_return;      /* [T][E]    valid where done                                                           */
+    int32_t *ep_len;         /* [T][E]                                                                               */
+    int32_t  flags;
+} cn_rollout_out;
+#define CN_ROLLOUT_OBS_EVERY_STEP 1
+int cn_rollout(cn_engine *eng, void *stream, int policy, int T, const cn_rollout_out *out, int32_t *num_launches);
 
 /* Test hooks of the kd-tree path's resumable spawns (the spawn waves that draw upcoming episodes park a
  * crowded spawn between two humans once a wave has worked `cycles` clock cycles in a launch, and a later

@@ -9,7 +9,11 @@ default) and visible. The robot acts on its belief of the humans, every step com
 Prints one JSON line per (policy, visibility): success / collision / timeout rates, the mean navigation time of
 the successful episodes and the wall time of the run. Needs a GPU.
 
-Usage: python tools/baseline_eval.py [--envs 100] [--test-size 500] [--humans 5] [--out FILE]
+--rollout runs the same evaluation on whole rollouts (evaluate_scripted -> cn_rollout: the controller inside the
+multi-step launches, every step recorded, the end-of-run check once per chunk); the per-episode records, and so the
+rows, are the same.
+
+Usage: python tools/baseline_eval.py [--envs 100] [--test-size 500] [--humans 5] [--rollout] [--out FILE]
 """
 import argparse
 import json
@@ -24,7 +28,7 @@ import torch  # noqa: E402
 
 from crowdnav_dsrnn_amd.config import Config, clone_config  # noqa: E402
 from crowdnav_dsrnn_amd.envs import CrowdNavVecEnv  # noqa: E402
-from crowdnav_dsrnn_amd.evaluation import evaluate  # noqa: E402
+from crowdnav_dsrnn_amd.evaluation import evaluate, evaluate_scripted  # noqa: E402
 from crowdnav_dsrnn_amd.policy_factory import ScriptedRobot  # noqa: E402
 
 
@@ -33,6 +37,7 @@ def main():
     ap.add_argument("--envs", type=int, default=100)
     ap.add_argument("--test-size", type=int, default=500)
     ap.add_argument("--humans", type=int, default=5)
+    ap.add_argument("--rollout", action="store_true", help="evaluate on whole rollouts (evaluate_scripted)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -50,12 +55,17 @@ def main():
             E = args.envs
             envs = CrowdNavVecEnv(c, E, c.env.seed, "cuda:0", allow_early_resets=True, nenv=E, phase="test")
             t0 = time.time()
-            evaluate(ScriptedRobot(envs, name), None, envs, E, "cuda:0", c, log, keep_traces=False, verbose=False)
+            if args.rollout:
+                evaluate_scripted(name, envs, E, "cuda:0", c, log, keep_traces=False, verbose=False)
+            else:
+                evaluate(ScriptedRobot(envs, name), None, envs, E, "cuda:0", c, log, keep_traces=False, verbose=False)
             wall = time.time() - t0
             last = evaluate.last
             nav = last["metrics"]["navigation time"]
             rec = {"robot": name, "robot_visible": visible, "humans": args.humans, "episodes": args.test_size,
-                   "envs": E, "success_rate": round(last["success_rate"], 3),
+                   "envs": E, "path": "rollout" if args.rollout else "step",
+                   "counts": {k: int(v["total"]) for k, v in last["num_events"].items()},
+                   "success_rate": round(last["success_rate"], 3),
                    "collision_rate": round(last["collision_rate"], 3), "timeout_rate": round(last["timeout_rate"], 3),
                    "nav_time_mean_s": round(float(nav[0]), 2), "nav_time_std_s": round(float(nav[1]), 2),
                    "wall_s": round(wall, 2)}

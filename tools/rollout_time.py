@@ -1,0 +1,95 @@
+#!/usr/bin/env python
+"""HIP-event timings of closed-loop scripted rollouts (cn_rollout) against the launch pairs they replace.
+
+Per configuration (4096 envs, T = 256 steps, holonomic, ORCA humans): (a) 5 humans, ORCA robot; (b) 9 humans, ORCA
+robot; (c) 10 humans, social-force robot. Three paths over the same T steps, every step recorded:
+  fused         cn_rollout at the default chunk: the controller inside the multi-step launches
+  native_pairs  cn_rollout at chunk 1: cn_robot_act + cn_step launch pairs issued from native code
+  python_pairs  the Python loop of robot_act() + step() (what the library offered before cn_rollout; its outputs are
+                not kept per step, so it does strictly less)
+between two events on the current stream after one warm-up rollout, three alternating rounds; the median round
+is reported (us per step) with the rounds' spread. Needs a GPU; prints one JSON line per configuration.
+
+Usage: python tools/rollout_time.py [--envs 4096] [--steps 256] [--out FILE]
+"""
+import argparse
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import torch  # noqa: E402
+
+from crowdnav_dsrnn_amd.config import Config, clone_config, make_cn_config  # noqa: E402
+from crowdnav_dsrnn_amd.engine import CrowdNavEngine  # noqa: E402
+
+
+def timed(fn, steps):
+    fn()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) * 1e3 / steps      # us per step
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--envs", type=int, default=4096)
+    ap.add_argument("--steps", type=int, default=256)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("rollout_time: needs a GPU")
+    E, T = args.envs, args.steps
+    lines = []
+    for tag, N, name in (("a", 5, "orca"), ("b", 9, "orca"), ("c", 10, "social_force")):
+        c = clone_config(Config())
+        c.sim.human_num = N
+        c.action_space.kinematics = "holonomic"
+        c.humans.policy = "orca"
+        eng = CrowdNavEngine(make_cn_config(c, num_envs=E), "cuda:0")
+        chunk = eng.seq_chunk
+        eng.reset()
+        eng.step(eng.robot_act(name))   # (the first step after cn_reset is a pair on every path)
+        buf = eng.rollout_buffers(T)
+        launches = {}
+
+        def fused():
+            eng.set_seq_chunk(chunk)
+            launches["fused"] = eng.rollout(name, T, out=buf)["num_launches"]
+
+        def native_pairs():
+            eng.set_seq_chunk(1)
+            launches["native_pairs"] = eng.rollout(name, T, out=buf)["num_launches"]
+
+        def python_pairs():
+            for _ in range(T):
+                eng.step(eng.robot_act(name))
+            launches["python_pairs"] = 2 * T
+
+        fns = {"fused": fused, "native_pairs": native_pairs, "python_pairs": python_pairs}
+        rounds = {k: [] for k in fns}
+        for _ in range(3):
+            for k, fn in fns.items():
+                rounds[k].append(timed(fn, T))
+        rec = {"config": tag, "envs": E, "humans": N, "robot": name, "steps": T, "chunk": chunk,
+               "unit": "us per step (HIP events)", "device": torch.cuda.get_device_name(0), "launches": launches}
+        for k, v in rounds.items():
+            v = sorted(v)
+            rec[k] = round(v[1], 2)
+            rec[k + "_min_max"] = [round(v[0], 2), round(v[2], 2)]
+        rec["fused_over_native_pairs"] = round(rec["fused"] / rec["native_pairs"], 3)
+        rec["fused_over_python_pairs"] = round(rec["fused"] / rec["python_pairs"], 3)
+        eng.close()
+        lines.append(json.dumps(rec))
+        print(lines[-1], flush=True)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
