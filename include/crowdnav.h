@@ -116,7 +116,9 @@ extern "C" {
 #define CN_INFO_SIDE_LEFT 8    /* test.side_preference only (crowd_sim.py:977-992) */
 #define CN_INFO_SIDE_RIGHT 9
 #define CN_INFO_SEPARATION 10
-#define CN_INFO_OVERFLOW 11    /* bounded-rejection overflows so far in this episode (engine diagnostic) */
+#define CN_INFO_OVERFLOW 11    /* bounded-rejection overflows of this episode before this step: its spawn's and the
+                                  goal changes' of its earlier steps (engine diagnostic; the state blob's `overflow`
+                                  also holds this step's, or after an auto-reset the next episode's spawn's) */
 #define CN_INFO_K 12
 
 #define CN_MAX_SCENARIOS 8

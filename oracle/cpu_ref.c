@@ -1047,6 +1047,9 @@ static void env_step(ref_engine *g, int e, const float *actions, float *robot_no
     const int N = g->N, M = g->M;
     const int holo = g->c.kinematics == CN_HOLONOMIC;
     const double dt = g->c.time_step;
+    /* CN_INFO_OVERFLOW: the counter before this step. On a done row that is the finished episode's total, as no
+     * goal change runs on a done step; the value after env_reset would describe the next episode's spawn. */
+    const uint32_t pre_ovf = R1(overflow, e);
     /* --- clip_action (srnn.py:18-48), float32 --- */
     float a0 = actions[(int64_t)e * 2], a1 = actions[(int64_t)e * 2 + 1];
     double avx = 0, avy = 0;      /* ActionXY */
@@ -1237,7 +1240,7 @@ static void env_step(ref_engine *g, int e, const float *actions, float *robot_no
     }
     for (int i = 0; i < N; ++i)
         if (!(H(h_px, e, i) == H(h_px, e, i)) || !(H(h_py, e, i) == H(h_py, e, i))) R1(flags, e) |= CN_FLAG_NAN;
-    if (info) info[CN_INFO_OVERFLOW] = (float)R1(overflow, e);
+    if (info) info[CN_INFO_OVERFLOW] = (float)pre_ovf;
 }
 
 /* ------------------------------------------------------------------------------------------------ */

@@ -9,6 +9,7 @@ import torch
 
 from crowdnav_dsrnn_amd import abi, envs, info as info_mod, spaces
 from crowdnav_dsrnn_amd.config import Config, clone_config, make_cn_config
+from tests import helpers as H
 
 
 def _config(N=5, kin="holonomic", policy="orca", scen=("circle_crossing",)):
@@ -174,6 +175,11 @@ def test_sharded_envs_equal_unsharded_gloo(tmp_path, oracle):
 
 
 # ------------------------------------------------------------------------------------------- GPU
+_HOST_KEYS = {"aggregate_nav_time": abi.INFO_AGG_NAV_TIME, "path_violation": abi.INFO_PATH_VIOLATION,
+              "personal_violation": abi.INFO_PERSONAL_VIOLATION, "jerk_cost": abi.INFO_JERK_COST,
+              "dist_to_goal": abi.INFO_DIST_TO_GOAL, "speed_violation": abi.INFO_SPEED_VIOLATION}
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("kin", ["holonomic", "unicycle"])
 def test_vecenv_matches_oracle(oracle, kin):
@@ -188,6 +194,7 @@ def test_vecenv_matches_oracle(oracle, kin):
     rng = np.random.RandomState(3)
     scale = 0.1 if kin == "unicycle" else 0.8
     n_done = 0
+    tally = {}
     for s in range(120):
         a = rng.uniform(-scale, scale, (E, 2)).astype(np.float32)
         obs, rew, done, infos = venv.step(torch.from_numpy(a).to("cuda:0"))
@@ -198,7 +205,19 @@ def test_vecenv_matches_oracle(oracle, kin):
         np.testing.assert_allclose(rew.numpy()[:, 0], r_rew, atol=1e-5, rtol=0)
         for k in r_obs:
             np.testing.assert_allclose(obs[k].cpu().numpy(), r_obs[k], atol=1e-5, rtol=0)
+        # the row the host-visible dicts are built from (free running: helpers.compare_info's allowance for a
+        # PERSONAL_VIOLATION on the threshold, capped below), then the dicts against that row
+        row = infos._info
+        errs = H.compare_info(row, r_info, r_ev, where="s=%d " % s, min_personal_space=c.social.min_personal_space,
+                              tally=tally)
+        errs += H.compare_monitor(infos._ep_return, infos._ep_len, r_epr, r_epl, r_done, where="s=%d " % s)
+        assert not errs, errs
         for i, inf in enumerate(infos):
+            si = inf["info"]
+            assert [si[k] for k in _HOST_KEYS] == [row[i, col] for col in _HOST_KEYS.values()], (s, i, si)
+            assert si["scenario"] == abi.SCENARIOS[int(row[i, abi.INFO_SCENARIO])]
+            if r_ev[i] == abi.EV_DANGER:
+                assert si["event"].min_dist == row[i, abi.INFO_MIN_DIST]
             want = info_mod.make_event(int(r_ev[i]), r_info[i, abi.INFO_MIN_DIST])
             assert type(inf["info"]["event"]) is type(want)
             if done[i]:
@@ -206,6 +225,7 @@ def test_vecenv_matches_oracle(oracle, kin):
                 assert inf["episode"]["l"] == int(r_epl[i])
                 assert abs(inf["episode"]["r"] - round(float(r_epr[i]), 6)) < 1e-5
     assert n_done > 0
+    assert tally.get("personal_flips", 0) <= 0.001 * tally["rows"], tally
     venv.close()
 
 

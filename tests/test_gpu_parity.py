@@ -1,7 +1,9 @@
 """HIP engine parity (MI355X). The GPU path is called through the C ABI (crowdnav_dsrnn_amd.engine)
 and checked against (a) golden vectors recorded from the reference and (b) the CPU oracle.
 Tolerances: bit-exact on events / done / flags / indices / RNG stream, 1e-5 on positions, rewards
-and observations (BASELINE.json north star)."""
+and observations (BASELINE.json north star). Wherever GPU meets oracle the whole 12-column info row and the
+Monitor pair ep_return / ep_len are compared too, by the one definition in tests/helpers.py (compare_info /
+compare_monitor)."""
 import glob
 import os
 
@@ -69,8 +71,24 @@ def _cfg(N=10, kin="unicycle", scen="circle_crossing", policy="orca", E=256, fov
     return make_cn_config(c, num_envs=E)
 
 
-def _teacher_forced(gpu, oracle, cfg, kin, steps=60, seed=5):
-    """Norm zones: the zones are built around the robot itself, so its disc sits within
+def _actions(rng, cfg, kin, pre=None, sigma=0.8, bias=0.0, act=None):
+    """Action recipe of the teacher-forced tests: unicycle uniform(-0.15, 0.15) + bias, holonomic N(0, sigma);
+    `act(rng, pre)` computes them from the oracle's pre-step state instead."""
+    if act is not None:
+        a = act(rng, pre)
+    elif kin == "unicycle":
+        a = rng.uniform(-0.15, 0.15, (cfg.num_envs, 2)) + bias
+    else:
+        a = rng.normal(0, sigma, (cfg.num_envs, 2))
+    return a.astype(np.float32)
+
+
+def _teacher_forced(gpu, oracle, cfg, kin, steps=60, seed=5, **recipe):
+    """Returns the oracle's stacked (info [T][E][K], event [T][E]) for the callers' coverage floors. Every
+    step compares the whole info row and the Monitor pair (helpers.compare_info / compare_monitor: flags and
+    counts exact, as both sides start the step from the same float64 state).
+
+    Norm zones: the zones are built around the robot itself, so its disc sits within
     ~1e-8 m of a zone corner in a few % of states and the -0.5 penalty then depends on the last ulp of
     the heading: the GPU's atan2f / cos (ocml), the oracle's (glibc) and the reference's (numpy's SIMD
     float32 atan2, which differs from glibc's in ~40 % of inputs) are all different roundings. An
@@ -84,10 +102,10 @@ def _teacher_forced(gpu, oracle, cfg, kin, steps=60, seed=5):
     ref.reset()
     rng = np.random.RandomState(seed)
     mism = flips = 0
+    infos, events = [], []
     for t in range(steps):
-        a = (rng.uniform(-0.15, 0.15, (cfg.num_envs, 2)) if kin == "unicycle"
-             else rng.normal(0, 0.8, (cfg.num_envs, 2))).astype(np.float32)
         pre = ref.get_state()
+        a = _actions(rng, cfg, kin, pre, **recipe)
         g.set_state(pre)
         r_out = ref.step(a)
         g_out = g.step(a)
@@ -114,10 +132,41 @@ def _teacher_forced(gpu, oracle, cfg, kin, steps=60, seed=5):
         errs = H.compare_state(gs, d, "post_", tol=1e-5, where="t=%d " % t, skip=("ep_return",))
         errs += H.compare_state(gs, {"post_ep_return": d["post_ep_return"]}, "post_", tol=1e-5, env_mask=keep,
                                 where="t=%d " % t)
+        errs += H.compare_info(g_out[4], r_out[4], r_out[3], where="t=%d " % t)
+        errs += H.compare_monitor(g_out[5], g_out[6], r_out[5], r_out[6], r_out[2], where="t=%d " % t, keep=keep)
         assert not errs, errs
         mism += int((g_out[4][:, abi.INFO_PATH_VIOLATION] != r_out[4][:, abi.INFO_PATH_VIOLATION]).sum())
+        infos.append(r_out[4])
+        events.append(r_out[3])
     assert mism == 0, mism
     assert flips <= cfg.num_envs * steps * 0.001, flips
+    return np.stack(infos), np.stack(events)
+
+
+def _goal_seeker(rng, pre):
+    """Unit vector from the oracle's robot position to its goal + N(0, 0.3): episodes that end in ReachGoal."""
+    d = np.stack([pre.r_gx - pre.r_px, pre.r_gy - pre.r_py], axis=1)
+    return d / np.maximum(np.linalg.norm(d, axis=1, keepdims=True), 1e-9) + rng.normal(0, 0.3, d.shape)
+
+
+def _flagged(col):
+    return lambda info, ev: int((info[:, :, col] == 1).sum())
+
+
+# Cases of test_gpu_vs_oracle_configs that make otherwise dead info columns live: 64 envs x 60 steps = 3,840 rows,
+# RandomState(5). name: (action recipe, {what: (count over the ORACLE's outputs, floor)}). The floors keep a later
+# change of recipe from silently emptying the case; counts measured on the oracle are quoted in the test's docstring.
+_LIVE = {
+    "speed_violation_holo": (dict(sigma=1.2), {
+        "SPEED_VIOLATION rows": (_flagged(abi.INFO_SPEED_VIOLATION), 300),
+        "rows without SPEED_VIOLATION": (lambda info, ev: int((info[:, :, abi.INFO_SPEED_VIOLATION] == 0).sum()), 300)}),
+    "speed_violation_uni": (dict(bias=0.08), {"SPEED_VIOLATION rows": (_flagged(abi.INFO_SPEED_VIOLATION), 100)}),
+    "side_pref_unicycle": (dict(bias=0.05), {
+        "SIDE_LEFT rows": (_flagged(abi.INFO_SIDE_LEFT), 20), "SIDE_RIGHT rows": (_flagged(abi.INFO_SIDE_RIGHT), 20),
+        "rows with SEPARATION > 0": (lambda info, ev: int((info[:, :, abi.INFO_SEPARATION] > 0).sum()), 3840)}),
+    "goal_seeker_time_factor": (dict(act=_goal_seeker), {
+        "REACHGOAL rows": (lambda info, ev: int((ev == abi.EV_REACHGOAL).sum()), 10)}),
+}
 
 
 @pytest.mark.parametrize("name,kin,N,policy,scen,over", [
@@ -146,11 +195,32 @@ def _teacher_forced(gpu, oracle, cfg, kin, steps=60, seed=5):
     ("philox_social_metrics", "holonomic", 5, "orca",
      ("parallel_traffic", "perpendicular_traffic", "circle_crossing", "square_crossing"),
      {"env__rng": "philox", "test__social_metrics": True, "sim__circle_radius": 4}),
+    # the _LIVE cases (64 envs): robot.v_pref = 2.0 is above social.max_walking_speed = 1.5
+    ("speed_violation_holo", "holonomic", 5, "orca", "circle_crossing", {"robot__v_pref": 2.0}),
+    ("speed_violation_uni", "unicycle", 10, "orca", "circle_crossing", {"robot__v_pref": 2.0}),
+    ("side_pref_unicycle", "unicycle", 1, "orca", ("side_pref_passing", "side_pref_overtaking", "side_pref_crossing"),
+     {"test__side_preference": True, "sim__circle_radius": 4}),
+    ("goal_seeker_time_factor", "holonomic", 2, "orca", "circle_crossing",
+     {"reward__time_factor": True, "sim__circle_radius": 4}),
 ])
 def test_gpu_vs_oracle_configs(gpu, oracle, name, kin, N, policy, scen, over):
     """Teacher-forced GPU vs oracle over the option space the reference exposes (SURVEY §8d C5 shapes,
-    norm zones, side preference, social-metrics scenario order, visible robot, radius/v_pref jitter)."""
-    _teacher_forced(gpu, oracle, _cfg(N, kin, scen, policy, 256, 2.0, **over), kin)
+    norm zones, side preference, social-metrics scenario order, visible robot, radius/v_pref jitter).
+
+    The _LIVE cases drive the info columns and reward forms the other cases leave dead, and assert on the
+    oracle's outputs that they do. Measured on the oracle (3,840 rows each): speed_violation_holo 1,789 rows
+    flagged (the holonomic speed-violation branch, both outcomes); speed_violation_uni 622 rows flagged (the
+    commanded world-frame speed of the unicycle); side_pref_unicycle SIDE_LEFT 152 / SIDE_RIGHT 146 rows and
+    SEPARATION > 0 in every row (the only case where unicycle_position feeds the side test);
+    goal_seeker_time_factor 51 ReachGoal rows (the time_factor reward and a successful episode's ep_return),
+    173 Danger rows, 79 collisions."""
+    if name not in _LIVE:
+        _teacher_forced(gpu, oracle, _cfg(N, kin, scen, policy, 256, 2.0, **over), kin)
+        return
+    recipe, floors = _LIVE[name]
+    info, ev = _teacher_forced(gpu, oracle, _cfg(N, kin, scen, policy, 64, 2.0, **over), kin, **recipe)
+    for what, (count, floor) in floors.items():
+        assert count(info, ev) >= floor, "%s: %s = %d, below the floor %d" % (name, what, count(info, ev), floor)
 
 
 @pytest.mark.parametrize("kin,N,policy,scen,fov", [
@@ -185,9 +255,26 @@ def test_gpu_vs_oracle_teacher_forced(gpu, oracle, kin, N, policy, scen, fov):
         d = {"post_" + n: np.asarray(getattr(rs, n)) for n, _, _ in abi.STATE_FIELDS if n != "mt"}
         d["post_mt_crc"] = H.mt_crc(rs)
         errs = H.compare_state(gs, d, "post_", tol=1e-5, where="t=%d " % t)
+        errs += H.compare_info(g_out[4], r_out[4], r_out[3], where="t=%d " % t)
+        errs += H.compare_monitor(g_out[5], g_out[6], r_out[5], r_out[6], r_out[2], where="t=%d " % t)
         assert not errs, errs
         mism += int((g_out[4][:, abi.INFO_PATH_VIOLATION] != r_out[4][:, abi.INFO_PATH_VIOLATION]).sum())
     assert mism == 0, mism
+
+
+def _free_outputs(r_ref, r_gpu, cfg, tally, t):
+    """Whole info row and Monitor pair of one free-running step. The two sides' states agree only within
+    1e-5 here, so a PERSONAL_VIOLATION difference is let through where the oracle's own MIN_DIST lies within
+    POS_TOL of min_personal_space; _flip_cap bounds how many."""
+    errs = H.compare_info(r_gpu[4], r_ref[4], r_ref[3], where="t=%d " % t,
+                          min_personal_space=cfg.min_personal_space, tally=tally)
+    errs += H.compare_monitor(r_gpu[5], r_gpu[6], r_ref[5], r_ref[6], r_ref[2], where="t=%d " % t)
+    assert not errs, errs
+
+
+def _flip_cap(tally):
+    """At most 0.1 % of the rows compared (the cap of the norm-zone flips)."""
+    assert tally.get("personal_flips", 0) <= 0.001 * tally["rows"], tally
 
 
 @pytest.mark.parametrize("rng,shape", [("mt19937", "c2"), ("philox", "c2"), ("mt19937", "c3")])
@@ -195,7 +282,10 @@ def test_gpu_free_running_matches_oracle_short_horizon(gpu, oracle, rng, shape):
     """Free-running (no teacher forcing) rollout: identical for the first 40 steps, auto-resets from the
     spawns the spare workgroups draw ahead included. c3 (25 humans, square_crossing, FOV pi, kd-tree path)
     also runs the spawns' binned disc test and the workgroup-cooperative crowded rejection of the spare
-    workgroups (a few resets per step; teacher-forced tests redraw every spawn after set_state instead)."""
+    workgroups (a few resets per step; teacher-forced tests redraw every spawn after set_state instead).
+    Every step also compares the whole info row and the Monitor pair (_free_outputs). On c3 the overflow
+    counter moves within the step in ~9 % of the rows (asserted on the oracle: at least 100 of the rows
+    compared), which makes CN_INFO_OVERFLOW = the counter BEFORE the step a real check."""
     if shape == "c3":
         cfg = _cfg(25, "holonomic", "square_crossing", E=512, fov=1.0, env__rng=rng)
     else:
@@ -205,6 +295,7 @@ def test_gpu_free_running_matches_oracle_short_horizon(gpu, oracle, rng, shape):
     for k in o1:
         np.testing.assert_allclose(o2[k], o1[k], atol=1e-6, rtol=0)
     rng = np.random.RandomState(11)
+    tally, ovf_changes = {}, 0
     for t in range(40):
         a = (rng.uniform(-0.1, 0.1, (cfg.num_envs, 2)) if shape == "c2"
              else rng.normal(0, 0.5, (cfg.num_envs, 2))).astype(np.float32)
@@ -212,6 +303,14 @@ def test_gpu_free_running_matches_oracle_short_horizon(gpu, oracle, rng, shape):
         np.testing.assert_array_equal(r2[2], r1[2])
         np.testing.assert_array_equal(r2[3], r1[3])
         np.testing.assert_allclose(r2[1], r1[1], atol=1e-5, rtol=0)
+        _free_outputs(r1, r2, cfg, tally, t)
+        if shape == "c3":   # the oracle's counter after the step against the value its info row carries
+            ovf_changes += int((np.asarray(ref.get_state().overflow) != r1[4][:, abi.INFO_OVERFLOW]).sum())
+    _flip_cap(tally)
+    if shape == "c3":
+        # CN_INFO_OVERFLOW is the counter before the step; goal changes and auto-resets of the kd-tree path move
+        # it within the step in ~9 % of the rows (332 of 64 envs x 60 steps), so the two readings differ here
+        assert ovf_changes >= 100, ovf_changes
     if shape == "c3":   # every stream (spawn draws included) at the same position, states within 1e-5
         rs, gs = ref.get_state(), g.get_state()
         d = {"post_" + n: np.asarray(getattr(rs, n)) for n, _, _ in abi.STATE_FIELDS if n != "mt"}
@@ -221,8 +320,10 @@ def test_gpu_free_running_matches_oracle_short_horizon(gpu, oracle, rng, shape):
 
 
 def _free_run_exact(ref, g, cfg, steps, kind, seed):
-    """Free-running GPU vs oracle with identical actions: done / event exact, rewards 1e-5 every step."""
+    """Free-running GPU vs oracle with identical actions: done / event exact, rewards 1e-5, the info row and
+    the Monitor pair (_free_outputs) every step."""
     rng = np.random.RandomState(seed)
+    tally = {}
     for t in range(steps):
         a = (rng.uniform(-0.1, 0.1, (cfg.num_envs, 2)) if kind == "unicycle"
              else rng.normal(0, 0.5, (cfg.num_envs, 2))).astype(np.float32)
@@ -230,6 +331,8 @@ def _free_run_exact(ref, g, cfg, steps, kind, seed):
         np.testing.assert_array_equal(r2[2], r1[2], err_msg="done t=%d" % t)
         np.testing.assert_array_equal(r2[3], r1[3], err_msg="event t=%d" % t)
         np.testing.assert_allclose(r2[1], r1[1], atol=1e-5, rtol=0, err_msg="reward t=%d" % t)
+        _free_outputs(r1, r2, cfg, tally, t)
+    _flip_cap(tally)
 
 
 def test_gpu_forced_spawn_parking_matches_oracle(gpu, oracle):
@@ -295,6 +398,7 @@ def test_gpu_every_env_resets_every_launch(gpu, oracle, shape, budget, start, tl
     kind = "holonomic" if shape == "c3" else "unicycle"
     rng = np.random.RandomState(23)
     resets = 0
+    tally = {}
     for t in range(64):
         if start == "set_state" and t % 8 == 0:
             g.set_state(ref.get_state())
@@ -306,6 +410,8 @@ def test_gpu_every_env_resets_every_launch(gpu, oracle, shape, budget, start, tl
         np.testing.assert_array_equal(r2[2], r1[2], err_msg="done t=%d" % t)
         np.testing.assert_array_equal(r2[3], r1[3], err_msg="event t=%d" % t)
         np.testing.assert_allclose(r2[1], r1[1], atol=1e-5, rtol=0, err_msg="reward t=%d" % t)
+        _free_outputs(r1, r2, cfg, tally, t)   # the Monitor record of an episode ends up in no state blob
+    _flip_cap(tally)
     assert resets >= 64 * E // 6, resets   # episodes of at most 5 steps
     rs, gs = ref.get_state(), g.get_state()
     d = {"post_" + n: np.asarray(getattr(rs, n)) for n, _, _ in abi.STATE_FIELDS if n != "mt"}
@@ -339,6 +445,7 @@ def test_gpu_full_size_c3_free_running(gpu, oracle):
     n_ep, ret = [0, 0], [0.0, 0.0]
     ended = np.zeros(E, np.int64)
     tmax = int(round(cfg.time_limit / cfg.time_step)) + 1
+    tally = {}
     for t in range(400):
         a = rng.normal(0, 0.5, (E, 2)).astype(np.float32)
         r1, r2 = ref.step(a), g.step(a)
@@ -346,6 +453,7 @@ def test_gpu_full_size_c3_free_running(gpu, oracle):
             np.testing.assert_array_equal(r2[2], r1[2], err_msg="done t=%d" % t)
             np.testing.assert_array_equal(r2[3], r1[3], err_msg="event t=%d" % t)
             np.testing.assert_allclose(r2[1], r1[1], atol=1e-5, rtol=0, err_msg="reward t=%d" % t)
+            _free_outputs(r1, r2, cfg, tally, t)
         for k in r2[0]:
             assert np.isfinite(r2[0][k]).all(), (k, t)
         assert np.isfinite(r2[1]).all()
@@ -357,6 +465,7 @@ def test_gpu_full_size_c3_free_running(gpu, oracle):
             dd = r[2].astype(bool)
             n_ep[k] += int(dd.sum())
             ret[k] += float(r[5][dd].sum())
+    _flip_cap(tally)
     np.testing.assert_array_equal(np.asarray(g.get_state().reset_count) - rc0, ended)
     assert n_ep[1] > 1000, n_ep
     assert abs(n_ep[1] - n_ep[0]) <= 0.02 * n_ep[0], n_ep
@@ -382,6 +491,7 @@ def test_gpu_full_size_c2_free_running(gpu, oracle):
     n_ep = [0, 0]
     ret = [0.0, 0.0]
     tmax = int(round(cfg.time_limit / cfg.time_step)) + 1
+    tally = {}
     for t in range(400):
         a = rng.uniform(-0.1, 0.1, (4096, 2)).astype(np.float32)
         r1, r2 = ref.step(a), g.step(a)
@@ -389,6 +499,7 @@ def test_gpu_full_size_c2_free_running(gpu, oracle):
             np.testing.assert_array_equal(r2[2], r1[2], err_msg="done t=%d" % t)
             np.testing.assert_array_equal(r2[3], r1[3], err_msg="event t=%d" % t)
             np.testing.assert_allclose(r2[1], r1[1], atol=1e-5, rtol=0, err_msg="reward t=%d" % t)
+            _free_outputs(r1, r2, cfg, tally, t)
         for k in r2[0]:
             assert np.isfinite(r2[0][k]).all(), (k, t)
         assert np.isfinite(r2[1]).all()
@@ -399,6 +510,7 @@ def test_gpu_full_size_c2_free_running(gpu, oracle):
             dd = r[2].astype(bool)
             n_ep[k] += int(dd.sum())
             ret[k] += float(r[5][dd].sum())
+    _flip_cap(tally)
     assert n_ep[1] > 1000, n_ep
     assert abs(n_ep[1] - n_ep[0]) <= 0.02 * n_ep[0], n_ep
     assert abs(ret[1] / n_ep[1] - ret[0] / n_ep[0]) <= 0.02 * abs(ret[0] / n_ep[0]) + 0.05, (ret, n_ep)
@@ -417,6 +529,7 @@ def test_gpu_ragged_sizes_match_oracle(gpu, oracle, E, N, kin, scen, fov):
     for k in o1:
         np.testing.assert_allclose(o2[k], o1[k], atol=1e-6, rtol=0)
     rng = np.random.RandomState(13)
+    tally = {}
     for t in range(30):
         a = (rng.uniform(-0.1, 0.1, (E, 2)) if kin == "unicycle" else rng.normal(0, 0.5, (E, 2))).astype(np.float32)
         r1, r2 = ref.step(a), g.step(a)
@@ -425,6 +538,8 @@ def test_gpu_ragged_sizes_match_oracle(gpu, oracle, E, N, kin, scen, fov):
         np.testing.assert_allclose(r2[1], r1[1], atol=1e-5, rtol=0, err_msg="reward t=%d" % t)
         for k in r1[0]:
             np.testing.assert_allclose(r2[0][k], r1[0][k], atol=1e-5, rtol=0, err_msg="%s t=%d" % (k, t))
+        _free_outputs(r1, r2, cfg, tally, t)
+    _flip_cap(tally)
 
 
 def test_gpu_large_batch_properties(gpu):

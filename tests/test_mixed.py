@@ -117,7 +117,8 @@ def test_gpu_mixed_c5_vs_oracle(gpu_mixed, oracle):
     """C5 mixed engine on the GPU vs the oracle's, teacher-forced over 60 steps at 500 envs: events / done
     exact, rewards / observations (padding included) / states within 1e-5; a reward may differ by exactly
     the norm-zone penalty only where the oracle puts the robot's disc within one heading ulp of a zone
-    (the rule of tests/test_gpu_parity.py::_teacher_forced)."""
+    (the rule of tests/test_gpu_parity.py::_teacher_forced). Every info column and the Monitor pair go
+    through the row map too (helpers.compare_info / compare_monitor, exact flags: teacher-forced)."""
     _, mixed = gpu_mixed
     E = 500
     cfgs, eg = bench.c5_mixed(E, 0, E)
@@ -125,7 +126,7 @@ def test_gpu_mixed_c5_vs_oracle(gpu_mixed, oracle):
     o1 = ref.reset()
     g.set_state(ref.get_state())
     rng = np.random.RandomState(7)
-    flips = 0
+    flips = side_rows = 0
     for t in range(60):
         a = rng.normal(0, 0.8, (E, 2)).astype(np.float32)
         pre = ref.get_state()
@@ -156,6 +157,13 @@ def test_gpu_mixed_c5_vs_oracle(gpu_mixed, oracle):
             assert not errs, errs
         np.testing.assert_array_equal(g_out[4][:, abi.INFO_PATH_VIOLATION], r_out[4][:, abi.INFO_PATH_VIOLATION])
         np.testing.assert_array_equal(g_out[4][:, abi.INFO_SCENARIO], r_out[4][:, abi.INFO_SCENARIO])
+        # every info column and the Monitor pair through the row map (both groups; the N = 1 side-preference
+        # group is the one whose SIDE_LEFT / SIDE_RIGHT / SEPARATION are live)
+        errs = H.compare_info(g_out[4], r_out[4], r_out[3], where="t=%d " % t)
+        errs += H.compare_monitor(g_out[5], g_out[6], r_out[5], r_out[6], r_out[2], where="t=%d " % t, keep=keep)
+        assert not errs, errs
+        side_rows += int((r_out[4][:, abi.INFO_SIDE_LEFT] + r_out[4][:, abi.INFO_SIDE_RIGHT] > 0).sum())
+    assert side_rows > 0, "no side-preference row was live on the oracle"
     assert flips <= E * 60 * 0.001, flips
 
 
