@@ -10,6 +10,10 @@ oracle/shims (gym, shapely, rvo2, torchvision — see oracle/shims/README.md) an
   roll_*.npz     teacher-forced step sequences: per step the actions, the post-step state, the
                  observation, reward, done, event, info — with the VecEnv worker's auto-reset
                  (shmem_vec_env.py:164-168) and bench.Monitor's episode return
+  *_cfg_*.npz    the same two kinds at non-default numeric settings (config_cases: time step, time limit,
+                 geometry, radii / v_pref, goal-change chances, reward constants, ORCA / social-force parameters,
+                 norm-zone side and penalty, social thresholds, phase 'test' with a small test_size, seeds);
+                 the overrides are stored in the fixture (cfg_meta) and applied by tests/helpers.py
   dsrnn.npz      DSRNN Policy.act / evaluate_actions with procedural weights
                  (pytorchBaselines/a2c_ppo_acktr/model.py:63-104, srnn_model.py:409-504)
   eval_*.npz     pytorchBaselines/evaluation.py evaluate() + metrics.py Metrics driven by a scripted
@@ -115,7 +119,10 @@ EVENT_CODE = {ref_info.Nothing: 0, ref_info.Danger: 1, ref_info.Collision: 2, re
 
 def make_ref_config(kin="holonomic", policy="orca", scenarios=("circle_crossing",), N=5, fov_robot=2.0,
                     fov_human=2.0, side_pref=False, norm_zones=False, social_metrics=False, robot_visible=False,
-                    random_radii=False, random_v_pref=False, time_factor=False, time_step=0.25):
+                    random_radii=False, random_v_pref=False, time_factor=False, time_step=0.25, over=None):
+    """`over` maps "section__field" to a value, set after every other argument (the convention of the GPU tests'
+    _cfg). discomfort_penalty_factor follows time_step (10 * time_step) unless it is overridden itself. Every
+    override is recorded in the fixture (cfg_meta) so that tests/helpers.py rebuilds the same config."""
     c = clone_config(RefConfig())
     c.action_space.kinematics = kin
     c.humans.policy = policy
@@ -137,15 +144,29 @@ def make_ref_config(kin="holonomic", policy="orca", scenarios=("circle_crossing"
         c.humans.random_goal_changing = False
         c.humans.end_goal_changing = False
     c.reward.norm_zones = norm_zones
+    c.overrides = dict(over or {})
+    for k, v in c.overrides.items():
+        sec, fld = k.split("__")
+        assert hasattr(getattr(c, sec), fld), k
+        setattr(getattr(c, sec), fld, v)
+    if "reward__discomfort_penalty_factor" not in c.overrides:
+        c.reward.discomfort_penalty_factor = 10 * c.env.time_step
     return c
 
 
-def make_ref_env(cfg, this_seed, nenv):
+def default_phase(nenv):
+    return "train" if nenv > 1 else "test"
+
+
+def make_ref_env(cfg, rank, nenv, phase=None, seed=None):
+    """Env `rank` of `nenv` as the reference's make_env sets it up (envs.py:66-73): thisSeed = seed + rank
+    (seed defaults to config.env.seed), phase 'train' when nenv > 1 unless given."""
     env = ref_csd.CrowdSimDict()
     env.configure(cfg)
-    env.thisSeed = this_seed
+    env.rank = rank
+    env.thisSeed = (cfg.env.seed if seed is None else seed) + rank
     env.nenv = nenv
-    env.phase = "train" if nenv > 1 else "test"
+    env.phase = default_phase(nenv) if phase is None else phase
     env.ep_ret, env.ep_len = 0.0, 0
     return env
 
@@ -208,7 +229,7 @@ ref_csd.random = _ScenarioChoice
 
 
 def run_in(env, fn, *a):
-    _CUR["gidx"] = env.thisSeed
+    _CUR["gidx"] = getattr(env, "rank", env.thisSeed)
     if getattr(env, "rng_state", None) is not None:
         np.random.set_state(env.rng_state)
     _ACTIVE["env"] = env
@@ -260,8 +281,18 @@ def info_vec(info, scenario):
     return v, EVENT_CODE[type(ev)]
 
 
-def cfg_meta(cfg, E):
-    return dict(kinematics=cfg.action_space.kinematics, policy=cfg.humans.policy, N=cfg.sim.human_num, E=E,
+def cfg_meta(cfg, E, phase=None, seed=None):
+    """Fixture metadata. Overrides of make_ref_config(over=...) travel as data: numbers in over_keys / over_vals,
+    strings (norm_zone_side) in over_skeys / over_svals; phase, seed and the two case sizes always."""
+    over = getattr(cfg, "overrides", {})
+    num = sorted(k for k, v in over.items() if not isinstance(v, str))
+    txt = sorted(k for k, v in over.items() if isinstance(v, str))
+    extra = dict(phase=default_phase(E) if phase is None else phase, seed=int(cfg.env.seed if seed is None else seed),
+                 val_size=int(cfg.env.val_size), test_size=int(cfg.env.test_size))
+    if over:
+        extra.update(over_keys=np.array(num, dtype="U64"), over_vals=np.array([float(over[k]) for k in num], np.float64),
+                     over_skeys=np.array(txt, dtype="U64"), over_svals=np.array([over[k] for k in txt], dtype="U64"))
+    return dict(extra, kinematics=cfg.action_space.kinematics, policy=cfg.humans.policy, N=cfg.sim.human_num, E=E,
                 scenarios=",".join(cfg.sim.train_val_sim), robot_fov=cfg.robot.FOV, human_fov=cfg.humans.FOV,
                 side_pref=int(cfg.test.side_preference), norm_zones=int(cfg.reward.norm_zones),
                 social_metrics=int(cfg.test.social_metrics), robot_visible=int(cfg.robot.visible),
@@ -279,10 +310,10 @@ def pack_state(sv, prefix, out, with_mt):
                                        for e in range(sv.E)], np.uint32)
 
 
-def gen_spawn(name, cfg, E, resets, outdir):
+def gen_spawn(name, cfg, E, resets, outdir, phase=None, seed=None):
     nenv = E
-    envs = [make_ref_env(cfg, r, nenv) for r in range(E)]
-    out = {"meta_" + k: np.array(v) for k, v in cfg_meta(cfg, E).items()}
+    envs = [make_ref_env(cfg, r, nenv, phase, seed) for r in range(E)]
+    out = {"meta_" + k: np.array(v) for k, v in cfg_meta(cfg, E, phase, seed).items()}
     for k in range(resets):
         # start from a blank state carrying only the case counters (all the reset reads)
         pre = extract_pre_reset(envs, cfg)
@@ -318,14 +349,15 @@ def goal_action(env, kin, rng):
     return np.array([0.12, np.clip(dth, -0.15, 0.15)], np.float32)
 
 
-def gen_roll(name, cfg, E, T, outdir, seed=1, goal_frac=0.5):
+def gen_roll(name, cfg, E, T, outdir, act_seed=1, goal_frac=0.5, phase=None, seed=None):
+    """`act_seed` seeds the recorded actions; `phase` / `seed` are the envs' (make_ref_env)."""
     nenv = E
     kin = cfg.action_space.kinematics
-    envs = [make_ref_env(cfg, r, nenv) for r in range(E)]
+    envs = [make_ref_env(cfg, r, nenv, phase, seed) for r in range(E)]
     for env in envs:
         env_reset(env)
-    rng = np.random.RandomState(seed)
-    out = {"meta_" + k: np.array(v) for k, v in cfg_meta(cfg, E).items()}
+    rng = np.random.RandomState(act_seed)
+    out = {"meta_" + k: np.array(v) for k, v in cfg_meta(cfg, E, phase, seed).items()}
     pack_state(extract(envs, cfg), "init_", out, True)
     acts = np.zeros((T, E, 2), np.float32)
     keys = ["robot_node", "temporal", "spatial", "reward", "done", "event", "info", "ep_return", "ep_len"]
@@ -898,6 +930,37 @@ def gen_eval(outdir):
         print("eval", name, len(lines), "log lines")
 
 
+def config_cases():
+    """Non-default numeric settings (roll_cfg_* / spawn_cfg_*): name -> (make_ref_config kwargs, E, T, spawn
+    resets, phase). Every field varied here is read by the engine's step, reset or spawn kernels; the fixtures
+    carry the overrides as data (cfg_meta). test_wrap: 4 envs on test_size 5, so the case counter runs
+    0, 4, 3, 2, 1 over the spawn fixture's five resets."""
+    K = dict
+    return [
+        ("ts01", K(N=5, over={"env__time_step": 0.1}), 6, 60, 2, None),
+        ("ts04_uni", K(kin="unicycle", N=6, over={"env__time_step": 0.4}), 6, 40, 2, None),
+        ("tl7", K(N=3, over={"env__time_limit": 7}), 4, 60, 2, None),
+        ("radius35_uni", K(kin="unicycle", N=5, over={"sim__circle_radius": 3.5}), 6, 40, 2, None),
+        ("sq31", K(N=12, scenarios=("square_crossing",), over={"sim__square_width": 31}), 4, 40, 2, None),
+        ("rr045", K(over={"robot__radius": 0.45, "robot__v_pref": 0.7}), 6, 60, 2, None),
+        ("hum", K(N=6, over={"humans__radius": 0.22, "humans__v_pref": 1.4, "env__randomize_attributes": False}),
+         6, 60, 2, None),
+        ("goalchg", K(over={"humans__goal_change_chance": 0.7, "humans__end_goal_change_chance": 0.4}), 6, 60, 2, None),
+        ("rewards", K(over={"reward__success_reward": 3.5, "reward__collision_penalty": -7.25,
+                            "reward__potential_factor": 0.75, "reward__discomfort_penalty_factor": 1.3,
+                            "sim__circle_radius": 4}), 6, 60, 2, None),
+        ("disc06", K(over={"reward__discomfort_dist_front": 0.6, "reward__discomfort_dist_back": 0.6}), 6, 60, 2, None),
+        ("orca", K(N=9, over={"orca__neighbor_dist": 3, "orca__safety_space": 0.05, "orca__time_horizon": 2}),
+         4, 60, 2, None),
+        ("sf", K(policy="social_force", N=6, over={"sf__A": 3.5, "sf__B": 0.6, "sf__KI": 2.5}), 6, 60, 2, None),
+        ("nz_rhs", K(norm_zones=True, scenarios=("parallel_traffic", "perpendicular_traffic"),
+                     over={"reward__norm_zone_side": "rhs", "reward__norm_zone_penalty": -1.25}), 4, 40, 2, None),
+        ("social", K(over={"social__min_personal_space": 0.5, "social__max_walking_speed": 0.7}), 6, 60, 2, None),
+        ("test_wrap", K(over={"env__test_size": 5, "env__seed": 77, "env__time_limit": 4}), 4, 60, 5, "test"),
+        ("seed_train", K(over={"env__seed": 123456789, "env__time_limit": 4}), 4, 60, 2, None),
+    ]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(REPO, "tests", "golden"))
@@ -955,6 +1018,19 @@ def main():
                 gen_roll(name, cfg, E, T, args.out, goal_frac=0.0 if "timeout" in name else 0.5)
             except TimeoutError as ex:
                 print("roll", name, "SKIPPED:", ex)
+            signal.alarm(0)
+    for name, kw, E, T, resets, phase in config_cases():
+        for kind in ("spawn", "roll"):
+            if not want("%s_cfg_%s" % (kind, name)):
+                continue
+            signal.alarm(400)
+            try:
+                if kind == "spawn":
+                    gen_spawn("cfg_" + name, make_ref_config(**kw), E, resets, args.out, phase=phase)
+                else:
+                    gen_roll("cfg_" + name, make_ref_config(**kw), E, T, args.out, phase=phase)
+            except TimeoutError as ex:
+                print(kind, name, "SKIPPED:", ex)
             signal.alarm(0)
     if want("dsrnn"):
         gen_dsrnn(args.out)

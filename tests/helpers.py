@@ -45,13 +45,36 @@ def ref_config(meta):
         c.humans.random_goal_changing = False
         c.humans.end_goal_changing = False
     c.reward.norm_zones = bool(meta["meta_norm_zones"])
+    over = meta_overrides(meta)
+    for k, v in over.items():
+        sec, fld = k.split("__")
+        assert hasattr(getattr(c, sec), fld), k
+        setattr(getattr(c, sec), fld, v)   # numbers as float: make_cn_config converts every field itself
+    if "reward__discomfort_penalty_factor" not in over:
+        c.reward.discomfort_penalty_factor = 10 * c.env.time_step
+    for k in ("seed", "val_size", "test_size"):
+        if "meta_" + k in meta:
+            setattr(c.env, k, int(meta["meta_" + k]))
     return c
+
+
+def meta_overrides(meta):
+    """{"section__field": value} a fixture was recorded with (oracle/gen_golden.py:make_ref_config's `over`):
+    numbers from meta_over_keys / meta_over_vals, strings from meta_over_skeys / meta_over_svals. Fixtures
+    recorded at the default settings have none of these keys."""
+    over = {}
+    if "meta_over_keys" in meta:
+        over.update((str(k), float(v)) for k, v in zip(meta["meta_over_keys"], meta["meta_over_vals"]))
+    if "meta_over_skeys" in meta:
+        over.update((str(k), str(v)) for k, v in zip(meta["meta_over_skeys"], meta["meta_over_svals"]))
+    return over
 
 
 def cn_config_from_meta(meta, E=None):
     c = ref_config(meta)
     E = int(meta["meta_E"]) if E is None else E
-    return make_cn_config(c, num_envs=E, nenv=int(meta["meta_E"]))
+    phase = str(meta["meta_phase"]) if "meta_phase" in meta else None
+    return make_cn_config(c, num_envs=E, nenv=int(meta["meta_E"]), phase=phase)
 
 
 def state_from(d, prefix, cfg, mt=None):

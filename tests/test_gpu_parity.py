@@ -54,6 +54,7 @@ def test_gpu_rollout_vs_reference(gpu, name):
 
 
 def _cfg(N=10, kin="unicycle", scen="circle_crossing", policy="orca", E=256, fov=2.0, **over):
+    mk = {k: over.pop(k) for k in list(over) if "__" not in k}   # make_cn_config's own: phase, nenv, env_offset
     c = clone_config(Config())
     c.sim.human_num = N
     c.action_space.kinematics = kin
@@ -68,7 +69,7 @@ def _cfg(N=10, kin="unicycle", scen="circle_crossing", policy="orca", E=256, fov
     if c.test.side_preference:
         c.humans.random_goal_changing = False
         c.humans.end_goal_changing = False
-    return make_cn_config(c, num_envs=E)
+    return make_cn_config(c, num_envs=E, **mk)
 
 
 def _actions(rng, cfg, kin, pre=None, sigma=0.8, bias=0.0, act=None):

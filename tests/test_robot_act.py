@@ -109,9 +109,26 @@ def test_gpu_robot_act_equals_host_composition_bit_for_bit(N, E):
     composition, both policies, every env. N = 9 is the quad path's last size (A = 10, all three line slots per
     lane), N = 10 the smallest kd tree, N = 31 the engine's maximum; N = 5 runs with a robot FOV of pi, so that
     belief rows of unseen humans occur."""
+    _closed_loop_bits(_config(N, fov=1.0 if N == 5 else 2.0), N, E)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("N", [5, 12])
+def test_gpu_robot_act_equals_host_composition_at_tuned_parameters(N):
+    """The same check away from the default parameters: ORCA neighbor_dist 3 / safety_space 0.3 / time_horizon 2,
+    social force A 3.5 / B 0.6 / KI 2.5, time_step 0.1. cn_robot_act reads them from the engine's cn_config, the
+    host composition from the Python Config, so a default baked into either side shows. N = 5 is the quad path
+    (robot FOV pi), N = 12 the kd tree, where neighbor_dist 3 cuts the neighbour set."""
+    c = _config(N, fov=1.0 if N == 5 else 2.0)
+    c.orca.neighbor_dist, c.orca.safety_space, c.orca.time_horizon = 3, 0.3, 2
+    c.sf.A, c.sf.B, c.sf.KI = 3.5, 0.6, 2.5
+    c.env.time_step = 0.1
+    _closed_loop_bits(c, N, 37)
+
+
+def _closed_loop_bits(c, N, E):
     from crowdnav_dsrnn_amd.engine import CrowdNavEngine
 
-    c = _config(N, fov=1.0 if N == 5 else 2.0)
     eng = CrowdNavEngine(make_cn_config(c, num_envs=E, nenv=37), "cuda:0")
     unseen = moved = 0
     for drive in NAMES:
