@@ -17,6 +17,8 @@
 // Reference: crowd_sim/envs/crowd_sim_dict.py:105-271, crowd_sim/envs/crowd_sim.py:296-1161,
 // crowd_sim/envs/utils/agent.py:172-218, crowd_nav/policy/{orca,social_force,srnn}.py; RVO2 v2.0
 // (third-party) restated in float32. Numerics: see cn_math.h.
+// This file holds the device core (plan, geometry, ORCA, RNG / spawn, the step and reset kernels); the
+// stand-alone kernels and the host side (struct cn_engine, the C ABI) are in engine/*.h, included at the end.
 #include <hip/hip_runtime.h>
 #include <vector>
 #include <math.h>
@@ -3860,1690 +3862,12 @@ __global__ void __launch_bounds__(64) cn_reset_kernel(RngArgs g, cn_config c)
 }
 
 // ------------------------------------------------------------------------------------------------
-// fused DSRNN edge-feature assembly (srnn_model.py:160-161, 210-211, 466)
+// The rest of this translation unit lives in engine/*.h: the stand-alone kernels and all host code. They are
+// included here, after the device core above, because they use it (and must stay in this translation unit:
+// the host code launches the kernels above; the order below is the kernels' order in the code object).
 // ------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) cn_edge_features_kernel(int64_t E, int N, const float *__restrict__ robot_node,
-                                                               const float *__restrict__ temporal,
-                                                               const float *__restrict__ spatial,
-                                                               const float *__restrict__ Wt, const float *__restrict__ bt,
-                                                               const float *__restrict__ Ws, const float *__restrict__ bs,
-                                                               const float *__restrict__ Wr, const float *__restrict__ br,
-                                                               const float *__restrict__ Wn, const float *__restrict__ bn,
-                                                               float *__restrict__ t_out, float *__restrict__ s_out,
-                                                               float *__restrict__ n_out)
-{
-    // one thread per (row, 4 output features); rows = E temporal + E*N spatial + E node
-    const int64_t rows = E * (N + 2);
-    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t row = idx >> 4;
-    const int q = (int)(idx & 15) * 4;
-    if (row >= rows) return;
-    float o[4];
-    if (row < E) {  // temporal edge: relu(Wt x + bt), x = robot velocity
-        const float x0 = temporal[row * 2], x1 = temporal[row * 2 + 1];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) o[k] = fmaxf(__fmaf_rn(Wt[(q + k) * 2 + 1], x1, __fmaf_rn(Wt[(q + k) * 2], x0, bt[q + k])), 0.0f);
-        *(float4 *)(t_out + row * 64 + q) = make_float4(o[0], o[1], o[2], o[3]);
-    } else if (row < E + E * N) {  // spatial edges
-        const int64_t r = row - E;
-        const float x0 = spatial[r * 2], x1 = spatial[r * 2 + 1];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) o[k] = fmaxf(__fmaf_rn(Ws[(q + k) * 2 + 1], x1, __fmaf_rn(Ws[(q + k) * 2], x0, bs[q + k])), 0.0f);
-        *(float4 *)(s_out + r * 64 + q) = make_float4(o[0], o[1], o[2], o[3]);
-    } else {  // robot node: relu(Wn (Wr x + br) + bn)
-        const int64_t r = row - E - E * N;
-        float h[3];
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            float a = br[j];
-#pragma unroll
-            for (int k = 0; k < 7; ++k) a = __fmaf_rn(Wr[j * 7 + k], robot_node[r * 7 + k], a);
-            h[j] = a;
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            float a = bn[q + k];
-#pragma unroll
-            for (int j = 0; j < 3; ++j) a = __fmaf_rn(Wn[(q + k) * 3 + j], h[j], a);
-            o[k] = fmaxf(a, 0.0f);
-        }
-        *(float4 *)(n_out + r * 64 + q) = make_float4(o[0], o[1], o[2], o[3]);
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// C ABI
-// ------------------------------------------------------------------------------------------------
-// ------------------------------------------------------------------------------------------------
-// LiDAR observation of the ConvGRU policy: CrowdSimDict.generate_ob's 'convgru' branch
-// (crowd_sim_dict.py:96-101) over LidarSensor.sensor_spin (crowd_sim/envs/utils/lidarv2.py:398-427).
-// As shipped, the reference computes the scan only inside reset() (crowd_sim_dict.py:174-191, robot
-// heading atan2(0, 0) = 0, and only the LAST human is parsed: the append sits outside the loop), AFTER the
-// reset observation was built (:166), and step() never refreshes lidar_rel_dist. So the observation that
-// reset() returns carries the previous scan (zeros before the first), and every step of the episode
-// carries the scan taken at its reset. One 64-lane wave per env, three beams per lane, float64 as the
-// reference; the observation row is
-//   [clip(robot (px, py, r, gx, gy, v_pref, theta) / max_range, 0, 1), |1 - clip(dist / max_range, 0, 1)|].
-// ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double np_rem(double a, double b)   // numpy float remainder (sign of divisor)
-{
-    double m = fmod(a, b);
-    if (m != 0.0) { if ((b < 0) != (m < 0)) m += b; }
-    else m = copysign(0.0, b);
-    return m;
-}
-__device__ __forceinline__ double rescale_angle(double t) { return np_rem(t + 2.0 * CN_PI, 2.0 * CN_PI); }
-
-__device__ __forceinline__ int seg_orient(double px, double py, double qx, double qy, double rx, double ry)
-{   // get_intersect.py:25-37
-    const double v = ((qy - py) * (rx - qx)) - ((qx - px) * (ry - qy));
-    return v > 0 ? 1 : (v < 0 ? 2 : 0);
-}
-__device__ __forceinline__ bool on_seg(double px, double py, double qx, double qy, double rx, double ry)
-{   // get_intersect.py:12-21
-    return qx <= fmax(px, rx) && qx >= fmin(px, rx) && qy <= fmax(py, ry) && qy >= fmin(py, ry);
-}
-
-__global__ void __launch_bounds__(256) cn_lidar_obs_kernel(cn_state_ptrs S, int E, int N, double half_world,
-                                                           const uint8_t *__restrict__ reset_mask, int enable,
-                                                           int beams, double max_range, double robot_r,
-                                                           float *__restrict__ lidar, float *__restrict__ obs)
-{
-    const int e = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (e >= E) return;
-    const int D = 7 + beams;
-    float *o = obs + (int64_t)e * D;
-    if (lane < 7) {
-        double v;
-        switch (lane) {
-        case 0: v = S.r_px[e]; break;
-        case 1: v = S.r_py[e]; break;
-        case 2: v = S.r_radius[e]; break;
-        case 3: v = S.r_gx[e]; break;
-        case 4: v = S.r_gy[e]; break;
-        case 5: v = S.r_vpref[e]; break;
-        default: v = S.r_theta[e]; break;
-        }
-        v = v / max_range;
-        v = v < 0.0 ? 0.0 : (v > 1.0 ? 1.0 : v);   // np.clip
-        o[lane] = (float)v;
-    }
-    float *L = lidar + (int64_t)e * beams;
-    const bool fresh = reset_mask == nullptr || reset_mask[e] != 0;
-    if (fresh) {
-        if (enable) {
-            const double sx = S.r_px[e], sy = S.r_py[e];
-            const int hl = e * N + (N - 1);                 // the last human only (see above)
-            const double hx = S.h_px[hl], hy = S.h_py[hl], hr = S.h_r[hl];
-            // get_valid_angles (lidarv2.py:17-52) for the one obstacle, sorted (min, max)
-            const double rlx = hx - sx, rly = hy - sy;
-            const double hd = rescale_angle(atan2(rly, rlx));
-            const double ddx = hr * sin(hd), ddy = hr * cos(hd);
-            const double m0 = rescale_angle(atan2(rly - ddy, rlx + ddx));
-            const double m1 = rescale_angle(atan2(rly + ddy, rlx - ddx));
-            const double lo0 = m0 < m1 ? m0 : m1, up0 = m0 < m1 ? m1 : m0;
-            const double bstep = (2.0 * CN_PI) / (double)(beams - 1);   // np.linspace(0, 2 pi, beams)
-            const int npts = 500;                                         // max_range / 0.01 samples (+ endpoint)
-            const double sstep = max_range / (double)(npts - 1);
-            for (int b = lane; b < beams; b += 64) {
-                const double th0 = (b == beams - 1) ? 2.0 * CN_PI : (double)b * bstep;
-                const double th = rescale_angle(th0 + 0.0);
-                // get_valid_angle_idx (lidarv2.py:55-75) mutates the caller's (min, max) arrays in place and
-                // they are reused for every beam: replay the mutation sequence up to this beam
-                double lo = lo0, up = up0, tt = th;
-                for (int q = 0; q <= b; ++q) {
-                    const bool wide = up - lo >= CN_PI;
-                    double tq = th;
-                    if (wide) { const double nu = up - 2.0 * CN_PI; up = lo; lo = nu; tq -= 2.0 * CN_PI; }
-                    if (q == b) tt = tq;
-                }
-                const bool valid = np_rem(tt - lo, 2.0 * CN_PI) < np_rem(up - lo, 2.0 * CN_PI);
-                const double c = cos(th), sn = sin(th);
-                double ex = c * max_range + sx, ey = sn * max_range + sy;   // beam_end
-                bool hit = false;
-                if (valid) {   // check_dist_collision_polygon (lidarv2.py:164-198): first sample inside the disc
-                    const double wx = hx - sx, wy = hy - sy;
-                    const double proj = wx * c + wy * sn, perp2 = wx * wx + wy * wy - proj * proj;
-                    const double r2 = hr * hr;
-                    if (perp2 <= r2 * (1.0 + 1e-9) + 1e-12) {
-                        const double hw = sqrt(fmax(r2 - perp2, 0.0));
-                        const double s_in = proj - hw, s_out = proj + hw;
-                        int k0 = (int)floor(s_in / sstep) - 2, k1 = (int)ceil(s_out / sstep) + 2;
-                        k0 = k0 < 0 ? 0 : k0;
-                        k1 = k1 > npts - 1 ? npts - 1 : k1;
-                        for (int k = k0; k <= k1 && !hit; ++k) {
-                            const double sk = (k == npts - 1) ? max_range : (double)k * sstep;
-                            const double bx = c * sk + sx, by = sn * sk + sy;
-                            const double ax = hx - bx, ay = hy - by;
-                            if (sqrt(ax * ax + ay * ay) < hr) { ex = bx; ey = by; hit = true; }
-                        }
-                    }
-                }
-                if (!hit) {    // walls (lidarv2.py:261-275): first intersecting wall, kept if within range
-                    const double t = half_world;
-                    const double wxs[5] = {-t, t, t, -t, -t}, wys[5] = {-t, -t, t, t, -t};
-                    const double p1x = sx, p1y = sy, q1x = ex, q1y = ey;
-                    for (int j = 0; j < 4; ++j) {
-                        const double p2x = wxs[j], p2y = wys[j], q2x = wxs[j + 1], q2y = wys[j + 1];
-                        const int o1 = seg_orient(p1x, p1y, q1x, q1y, p2x, p2y);
-                        const int o2 = seg_orient(p1x, p1y, q1x, q1y, q2x, q2y);
-                        const int o3 = seg_orient(p2x, p2y, q2x, q2y, p1x, p1y);
-                        const int o4 = seg_orient(p2x, p2y, q2x, q2y, q1x, q1y);
-                        const bool inter = (o1 != o2 && o3 != o4) || (o1 == 0 && on_seg(p1x, p1y, p2x, p2y, q1x, q1y)) ||
-                                           (o2 == 0 && on_seg(p1x, p1y, q2x, q2y, q1x, q1y)) ||
-                                           (o3 == 0 && on_seg(p2x, p2y, p1x, p1y, q2x, q2y)) ||
-                                           (o4 == 0 && on_seg(p2x, p2y, q1x, q1y, q2x, q2y));
-                        if (!inter) continue;
-                        // line_intersection (get_intersect.py:72-89)
-                        const double xd0 = p1x - q1x, xd1 = p2x - q2x, yd0 = p1y - q1y, yd1 = p2y - q2y;
-                        const double div = xd0 * yd1 - xd1 * yd0;
-                        if (div != 0.0) {
-                            const double d0 = p1x * q1y - p1y * q1x, d1 = p2x * q2y - p2y * q2x;
-                            const double ix = (d0 * xd1 - d1 * xd0) / div, iy = (d0 * yd1 - d1 * yd0) / div;
-                            if (np_norm2(ix - sx, iy - sy) <= max_range) { ex = ix; ey = iy; }
-                        }
-                        break;
-                    }
-                }
-                if (np_norm2(ex - sx, ey - sy) < robot_r) {   // beams cannot end inside the robot
-                    ex = sx + robot_r * cos(th);
-                    ey = sy + robot_r * sin(th);
-                }
-                const double rx = ex - sx, ry = ey - sy;
-                double rd = sqrt(rx * rx + ry * ry) / max_range;
-                rd = rd < 0.0 ? 0.0 : (rd > 1.0 ? 1.0 : rd);
-                o[7 + b] = L[b];                 // the reset observation keeps the previous scan
-                L[b] = (float)fabs(1.0 - rd);
-            }
-            return;
-        }
-        for (int b = lane; b < beams; b += 64) { o[7 + b] = L[b]; L[b] = 0.0f; }
-        return;
-    }
-    for (int b = lane; b < beams; b += 64) o[7 + b] = L[b];
-}
-
-// ------------------------------------------------------------------------------------------------
-// Live LiDAR scan (cn_lidar_scan): the scan CrowdSimDict.step() computes every step and then discards
-// (crowd_sim_dict.py:224-251) — LidarSensor.sensor_spin at the robot's position, heading atan2(vy, vx),
-// against ALL humans (index order) and the world walls — written into the observation row of the current
-// state. float64 like the reference. One workgroup serves G consecutive envs (G chosen by the host so that
-// G * beams fills the 256 lanes): phase 1 stages every obstacle of the G envs in LDS once (centre, radius,
-// centre distance, angular window), phase 2 spreads the G * beams beams flat over the lanes, so neither a
-// small N nor a beam count off a multiple of 64 idles lanes.
-//
-// get_valid_angle_idx (lidarv2.py:55-75) flips a window that is at least pi wide IN PLACE, and the flipped
-// window serves every later beam. The flips do not depend on the beam, so phase 1 runs each obstacle's flip
-// sequence once: nflip flips until the window is narrower than pi (0 or 1 but for a window of exactly pi,
-// which flips back and forth: capped at the beam count). Beam b >= nflip sees the settled window and its own
-// angle; beam b < nflip replays b + 1 flips and tests its angle - 2 pi, as the reference does on a flip.
-// ------------------------------------------------------------------------------------------------
-#define CN_LIDAR_G 8   // envs per workgroup at most (LDS: 8 * 31 obstacles * 80 B = 19.4 KB)
-
-struct LidarObst {
-    double x, y, r, dist;     // centre, radius, |centre - sensor| (np.linalg.norm(axis=1): no fused multiply-add)
-    double lo, up, width;     // the settled window and np.remainder(up - lo, 2 pi)
-    double lo0, up0;          // the window before any flip
-    int nflip, pad;
-};
-
-// fmod(a, 2 pi) for |a| < 8 pi by exact subtractions (Sterbenz: x - b is exact for b <= x <= 2 b), then
-// numpy's sign rule: np.remainder(a, 2 pi). Falls back to fmod outside that range.
-__device__ __forceinline__ double np_rem_2pi(double a)
-{
-    const double b = 2.0 * CN_PI;
-    double x = fabs(a);
-    if (!(x < 4.0 * b)) return np_rem(a, b);
-    if (x >= 2.0 * b) x -= 2.0 * b;
-    if (x >= b) x -= b;
-    if (x == 0.0) return 0.0;
-    return a < 0.0 ? b - x : x;     // fmod keeps the sign of a; numpy then adds b: -x + b
-}
-
-__global__ void __launch_bounds__(256) cn_lidar_scan_kernel(cn_state_ptrs S, int E, int N, int G, double half_world,
-                                                            int beams, int npts, double max_range, double robot_r,
-                                                            float *__restrict__ obs)
-{
-    __shared__ LidarObst ob[CN_LIDAR_G * 31];
-    __shared__ double hd[CN_LIDAR_G][3];     // sensor x, y, heading
-    const int tid = threadIdx.x, e0 = blockIdx.x * G;
-    const int ne = min(G, E - e0);
-    const int D = 7 + beams;
-    const double TWO_PI = 2.0 * CN_PI;
-
-    for (int t = tid; t < ne * 7; t += 256) {          // the robot part of the row
-        const int e = e0 + t / 7, f = t % 7;
-        double v;
-        switch (f) {
-        case 0: v = S.r_px[e]; break;
-        case 1: v = S.r_py[e]; break;
-        case 2: v = S.r_radius[e]; break;
-        case 3: v = S.r_gx[e]; break;
-        case 4: v = S.r_gy[e]; break;
-        case 5: v = S.r_vpref[e]; break;
-        default: v = S.r_theta[e]; break;
-        }
-        v = v / max_range;
-        v = v < 0.0 ? 0.0 : (v > 1.0 ? 1.0 : v);   // np.clip
-        obs[(int64_t)e * D + f] = (float)v;
-    }
-    if (tid < ne) {
-        const int e = e0 + tid;
-        hd[tid][0] = S.r_px[e];
-        hd[tid][1] = S.r_py[e];
-        // float64 arctangent. (While the robot's velocity holds np.float32 values the reference's np.arctan2 is
-        // a float32 one, whose last ulp depends on the host's SIMD math library: within 1.2e-7 rad of this.)
-        hd[tid][2] = atan2(S.r_vy[e], S.r_vx[e]);
-    }
-    for (int t = tid; t < ne * N; t += 256) {          // phase 1: obstacles -> LDS
-        const int le = t / N, i = t % N, e = e0 + le;
-        const double sx = S.r_px[e], sy = S.r_py[e];
-        const int hi = e * N + i;
-        LidarObst o;
-        o.x = S.h_px[hi]; o.y = S.h_py[hi]; o.r = S.h_r[hi];
-        // get_valid_angles (lidarv2.py:17-52): sorted (min, max)
-        const double rlx = o.x - sx, rly = o.y - sy;
-        o.dist = sqrt(rlx * rlx + rly * rly);
-        const double ha = rescale_angle(atan2(rly, rlx));
-        const double ddx = o.r * sin(ha), ddy = o.r * cos(ha);
-        const double m0 = rescale_angle(atan2(rly - ddy, rlx + ddx));
-        const double m1 = rescale_angle(atan2(rly + ddy, rlx - ddx));
-        o.lo0 = m0 < m1 ? m0 : m1;
-        o.up0 = m0 < m1 ? m1 : m0;
-        double lo = o.lo0, up = o.up0;
-        int nf = 0;
-        while (up - lo >= CN_PI && nf < beams) { const double nu = up - TWO_PI; up = lo; lo = nu; ++nf; }
-        o.lo = lo; o.up = up; o.nflip = nf; o.pad = 0;
-        o.width = np_rem(up - lo, TWO_PI);
-        ob[t] = o;
-    }
-    __syncthreads();
-
-    const double bstep = TWO_PI / (double)(beams - 1);          // np.linspace(0, 2 pi, beams)
-    const double sstep = max_range / (double)(npts - 1);        // np.linspace(0, max_range, npts)
-    for (int item = tid; item < ne * beams; item += 256) {      // phase 2: one beam per lane
-        const int le = item / beams, b = item - le * beams, e = e0 + le;
-        const double sx = hd[le][0], sy = hd[le][1];
-        const double th0 = (b == beams - 1) ? TWO_PI : (double)b * bstep;
-        const double th = rescale_angle(th0 + hd[le][2]);
-        const double c = cos(th), sn = sin(th);
-        // the obstacle with the nearest centre among those whose window holds the beam (first on ties)
-        const LidarObst *O = ob + le * N;
-        int best = -1;
-        double bestd = 0.0;
-        for (int i = 0; i < N; ++i) {
-            double lo = O[i].lo, up = O[i].up, tt = th, width = O[i].width;
-            if (b < O[i].nflip) {
-                lo = O[i].lo0; up = O[i].up0;
-                for (int q = 0; q <= b; ++q) { const double nu = up - TWO_PI; up = lo; lo = nu; }
-                tt = th - TWO_PI;
-                width = np_rem(up - lo, TWO_PI);
-            }
-            const bool valid = np_rem_2pi(tt - lo) < width;
-            const double d = O[i].dist;
-            if (valid && (best < 0 || d < bestd)) { best = i; bestd = d; }
-        }
-        double ex = c * max_range + sx, ey = sn * max_range + sy;   // beam_end
-        bool hit = false;
-        if (best >= 0) {   // check_dist_collision_polygon (lidarv2.py:164-198): first sample inside the disc,
-                           // searched in a window around the analytic entry point
-            const double hx = O[best].x, hy = O[best].y, hr = O[best].r;
-            const double wx = hx - sx, wy = hy - sy;
-            const double proj = wx * c + wy * sn, perp2 = wx * wx + wy * wy - proj * proj;
-            const double r2 = hr * hr;
-            if (perp2 <= r2 * (1.0 + 1e-9) + 1e-12) {
-                const double hw = sqrt(fmax(r2 - perp2, 0.0));
-                const double k_in = floor((proj - hw) / sstep) - 2.0, k_out = ceil((proj + hw) / sstep) + 2.0;
-                const int k0 = k_in > 0.0 ? (k_in < (double)npts ? (int)k_in : npts) : 0;
-                const int k1 = k_out < (double)(npts - 1) ? (k_out > -1.0 ? (int)k_out : -1) : npts - 1;
-                for (int k = k0; k <= k1 && !hit; ++k) {
-                    const double sk = (k == npts - 1) ? max_range : (double)k * sstep;
-                    const double bx = c * sk + sx, by = sn * sk + sy;
-                    const double ax = hx - bx, ay = hy - by;
-                    if (sqrt(ax * ax + ay * ay) < hr) { ex = bx; ey = by; hit = true; }
-                }
-            }
-        }
-        if (!hit) {    // walls (lidarv2.py:261-275): first intersecting wall, kept if within range
-            const double t = half_world;
-            const double wxs[5] = {-t, t, t, -t, -t}, wys[5] = {-t, -t, t, t, -t};
-            const double p1x = sx, p1y = sy, q1x = ex, q1y = ey;
-            for (int j = 0; j < 4; ++j) {
-                const double p2x = wxs[j], p2y = wys[j], q2x = wxs[j + 1], q2y = wys[j + 1];
-                const int o1 = seg_orient(p1x, p1y, q1x, q1y, p2x, p2y);
-                const int o2 = seg_orient(p1x, p1y, q1x, q1y, q2x, q2y);
-                const int o3 = seg_orient(p2x, p2y, q2x, q2y, p1x, p1y);
-                const int o4 = seg_orient(p2x, p2y, q2x, q2y, q1x, q1y);
-                const bool inter = (o1 != o2 && o3 != o4) || (o1 == 0 && on_seg(p1x, p1y, p2x, p2y, q1x, q1y)) ||
-                                   (o2 == 0 && on_seg(p1x, p1y, q2x, q2y, q1x, q1y)) ||
-                                   (o3 == 0 && on_seg(p2x, p2y, p1x, p1y, q2x, q2y)) ||
-                                   (o4 == 0 && on_seg(p2x, p2y, q1x, q1y, q2x, q2y));
-                if (!inter) continue;
-                // line_intersection (get_intersect.py:72-89)
-                const double xd0 = p1x - q1x, xd1 = p2x - q2x, yd0 = p1y - q1y, yd1 = p2y - q2y;
-                const double div = xd0 * yd1 - xd1 * yd0;
-                if (div != 0.0) {
-                    const double d0 = p1x * q1y - p1y * q1x, d1 = p2x * q2y - p2y * q2x;
-                    const double ix = (d0 * xd1 - d1 * xd0) / div, iy = (d0 * yd1 - d1 * yd0) / div;
-                    if (np_norm2(ix - sx, iy - sy) <= max_range) { ex = ix; ey = iy; }
-                }
-                break;
-            }
-        }
-        if (np_norm2(ex - sx, ey - sy) < robot_r) {   // beams cannot end inside the robot
-            ex = sx + robot_r * c;
-            ey = sy + robot_r * sn;
-        }
-        const double rx = ex - sx, ry = ey - sy;
-        double rd = sqrt(rx * rx + ry * ry) / max_range;
-        rd = rd < 0.0 ? 0.0 : (rd > 1.0 ? 1.0 : rd);
-        obs[(int64_t)e * D + 7 + b] = (float)fabs(1.0 - rd);
-    }
-}
-
-struct cn_engine {
-    cn_config c;
-    int device;
-    int E, N, A;
-    StepPlan plan;
-    void *state;
-    int64_t state_bytes;
-    cn_state_ptrs s;
-    uint32_t *work;       // [E]
-    uint32_t *work_count; // [16]: [2..4] spawn-list counters (triple buffered), [5..7] parked-spawn counters,
-                          // [8..11] spawn statistics (PendLaunch::stats), [15] inline reset draws
-    uint32_t *plist;      // [3][E + 64][4] envs whose spawn after next kernel A draws, with their counters
-    uint32_t *rlist;      // [3][2E][4] spawns parked by a launch (resumed by the next); counters work_count[5..7]
-    int devseq;           // graph mode (cn_set_graph_mode): the step sequence lives in work_count[12..14]
-    uint32_t ctl_host[4];
-    int pend_all;         // next kernel A's pending mode: PEND_BOTH (after cn_set_state) or PEND_FRESH (after cn_reset)
-    uint64_t nstep;
-    long long spawn_budget;   // clock cycles a spawning wave works per step of a launch before parking (0: never)
-    int seq_chunk;        // steps per launch of cn_step_seq (1: a cn_step launch per step)
-    void *pend_mem;       // pending next-episode spawns (PendPtrs)
-    PendPtrs pend;
-    int pend_blocks;      // spare workgroups of kernel A running spawn waves
-    int pend_waves;       // spawning waves per spare workgroup
-    int a_lds;            // kernel A dynamic LDS: max(step plan, spawn waves)
-    int64_t case_size, counter_offset;
-    int rng_grid;
-    // kernel timing (cn_profile)
-    int prof_on, prof_cap, prof_n;
-    hipEvent_t *ev;  // [2]: before the first, after the last launch of the window
-    // output view (a group of a mixed engine: its envs' rows in the caller's buffers and the padded human
-    // stride; identity / N for a plain engine)
-    int32_t *rows;   // device [E] or nullptr
-    int NS;
-    // mixed engine (cn_create_mixed): the groups, each a plain engine over its envs; E = all envs,
-    // N = NS = the largest human count
-    int ngroups;
-    cn_engine **grp;
-    hipStream_t *gstream;   // [ngroups]: group k > 0 steps on gstream[k] (forked from / joined to the caller's)
-    hipEvent_t *gev;        // [ngroups + 1]: fork, then one join event per forked group
-};
-
-// unit-circle table of GEOS's 64-gon point buffer (norm zones), per device; every entry point whose
-// kernels read it (cn_create, cn_debug_disc_quad) uploads it first
-static hipError_t circ_table_init()
-{
-    double cs[64], sn[64];
-    for (int k = 0; k < 64; ++k) { const double a = -(k * (CN_PI / 2 / 16)); cs[k] = cos(a); sn[k] = sin(a); }
-    hipError_t e = hipMemcpyToSymbol(HIP_SYMBOL(c_circ_cos), cs, sizeof cs);
-    if (e == hipSuccess) e = hipMemcpyToSymbol(HIP_SYMBOL(c_circ_sin), sn, sizeof sn);
-    return e;
-}
-
-static thread_local char g_err[512];
-static int set_err(int code, const char *fmt, const char *a = "")
-{
-    snprintf(g_err, sizeof g_err, fmt, a);
-    return code;
-}
-int cn_set_error(int code, const char *msg) { return set_err(code, "%s", msg); }   // for cn_gru.hip
-#define HIPCHK(x)                                                                       \
-    do {                                                                                \
-        hipError_t _e = (x);                                                            \
-        if (_e != hipSuccess) return set_err(CN_EHIP, "HIP error: %s", hipGetErrorString(_e)); \
-    } while (0)
-
-__global__ void __launch_bounds__(64) cn_disc_quad_kernel(int64_t n, int mode, const double *px, const double *py,
-                                                          const double *r, const double *qx, const double *qy,
-                                                          int32_t *out)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    if (mode == 2)   // the robot's norm-zone penalty predicate: qx[i] = {vx, f32, ...}, qy[i] = {vy, lhs, ...}
-        out[i] = robot_norm_zone_violation(px[i], py[i], qx[4 * i], qy[4 * i], r[i], qx[4 * i + 1] != 0.0,
-                                           (int)qy[4 * i + 1]);
-    else
-        out[i] = mode ? disc_quad_sat(px[i], py[i], r[i], qx + 4 * i, qy + 4 * i)
-                      : disc_quad_intersect(px[i], py[i], r[i], qx + 4 * i, qy + 4 * i);
-}
-
-// cn_debug_copy64: one wave per segment of `seg` doubles
-__global__ void __launch_bounds__(64) cn_copy64_kernel(int64_t n, int seg, const double *__restrict__ src,
-                                                       double *__restrict__ dst)
-{
-    const int64_t k = (int64_t)blockIdx.x * seg + threadIdx.x;
-    if ((int)threadIdx.x < seg && k < n) dst[k] = src[k];
-}
-
-// cn_debug_orca: one quad per simulator (16 per 64-lane workgroup), the step kernel's quad-path functions
-__global__ void __launch_bounds__(64) cn_orca_kernel(int64_t n, int A, const float *__restrict__ ag,
-                                                     const float *__restrict__ self, float nd, float th, float ts,
-                                                     float *__restrict__ out)
-{
-    __shared__ float4 Ls[16][9];
-    const int q = threadIdx.x >> 2, sq = threadIdx.x & 3;
-    const int64_t i = (int64_t)blockIdx.x * 16 + q;
-    const bool act = i < n;
-    const float *a = ag + (act ? i : 0) * A * 5;
-    const int M = A - 1;
-    int cnt = 0;
-    if (act)
-        cnt = orca_lines_quad(
-            [&](int k, float &x, float &y, float &vx, float &vy, float &r) {
-                const float *o = a + (k + 1) * 5;
-                x = o[0]; y = o[1]; vx = o[2]; vy = o[3]; r = o[4];
-            },
-            M, sq, a[0], a[1], a[2], a[3], a[4], nd * nd, fdiv(1.0f, th), fdiv(1.0f, ts), Ls[q]);
-    wsync();
-    if (act) {
-        const float vmax = self[3 * i], ox = self[3 * i + 1], oy = self[3 * i + 2];
-        float rx, ry;
-        float4 R[3];
-#pragma unroll
-        for (int u = 0; u < 3; ++u) R[u] = sq + 4 * u < cnt ? Ls[q][sq + 4 * u] : make_float4(0.f, 0.f, 0.f, 0.f);
-        const int fail_at = lp2_r<3>(R, cnt, vmax, ox, oy, sq, rx, ry);
-        if (fail_at < cnt) lp3_r<3>(R, Ls[q], cnt, fail_at, vmax, sq, rx, ry);
-        if (sq == 0) {
-            out[4 * i] = rx; out[4 * i + 1] = ry; out[4 * i + 2] = (float)fail_at; out[4 * i + 3] = (float)cnt;
-        }
-    }
-}
-
-// cn_orca_predict_kd: ORCA.predict of simulators of any size up to CN_ORCA_MAXA agents, with RVO2's KdTree
-// (MAX_LEAF_SIZE 10) and its persisted agents_ order. One quad per simulator (16 per 64-lane workgroup):
-// lane 0 of the quad builds the tree (buildAgentTreeRecursive, which re-permutes agents_ in place) and runs
-// the query (queryAgentTreeRecursive + insertAgentNeighbor with maxNeighbors = A - 1), both sequential as
-// in RVO2 -- the plugin serves one predict per agent per env step, off the batched step path, which has its
-// own ballot-partitioned walk; then the quad builds the ORCA lines in neighbour order and runs the quad
-// linear programs of the step kernel. Oracle: cpu_ref.c:kd_build / kd_query / rvo2_agent0.
-#define CN_ORCA_MAXA 64
-// 20 B per node: ranges and child indices fit bytes (A <= 64 agents, < 2A nodes); the build / query stacks
-// below are bytes too -- the per-lane private arrays were 5.7 KB of scratch per lane with ints, 3.3 KB now
-struct KdNodeS { uint8_t begin, end, left, right; float minX, maxX, minY, maxY; };
-
-__device__ __forceinline__ float kd_bdist(const KdNodeS &t, float x, float y)
-{
-    const float a = (0.0f < t.minX - x) ? t.minX - x : 0.0f, b = (0.0f < x - t.maxX) ? x - t.maxX : 0.0f;
-    const float cc = (0.0f < t.minY - y) ? t.minY - y : 0.0f, d = (0.0f < y - t.maxY) ? y - t.maxY : 0.0f;
-    return a * a + b * b + cc * cc + d * d;
-}
-
-// lane-sequential KdTree build + query over X / Y [A] (LDS), perm [A] (LDS, updated in place); writes the
-// neighbours of agent 0 in insertion-sorted order to nb [A - 1] (agent ids) and returns their count
-__device__ int kd_neighbors_seq(int A, const float *X, const float *Y, uint8_t *perm, float rangeSq, uint8_t *nb)
-{
-    KdNodeS T[2 * CN_ORCA_MAXA];
-    uint8_t stk[CN_ORCA_MAXA + 2][3];
-    int sp = 0;
-    stk[sp][0] = 0; stk[sp][1] = (uint8_t)A; stk[sp][2] = 0; ++sp;
-    while (sp > 0) {   // any order of the recursive calls gives the same tree: children own disjoint ranges
-        --sp;
-        const int begin = stk[sp][0], end = stk[sp][1], node = stk[sp][2];
-        KdNodeS t;
-        t.begin = (uint8_t)begin; t.end = (uint8_t)end; t.left = t.right = 0;
-        t.minX = t.maxX = X[perm[begin]];
-        t.minY = t.maxY = Y[perm[begin]];
-        for (int i = begin + 1; i < end; ++i) {
-            const float x = X[perm[i]], y = Y[perm[i]];
-            t.maxX = t.maxX < x ? x : t.maxX; t.minX = x < t.minX ? x : t.minX;
-            t.maxY = t.maxY < y ? y : t.maxY; t.minY = y < t.minY ? y : t.minY;
-        }
-        if (end - begin > 10) {
-            const bool vert = t.maxX - t.minX > t.maxY - t.minY;
-            const float split = vert ? 0.5f * (t.maxX + t.minX) : 0.5f * (t.maxY + t.minY);
-            int left = begin, right = end;
-            while (left < right) {
-                while (left < right && (vert ? X[perm[left]] : Y[perm[left]]) < split) ++left;
-                while (right > left && (vert ? X[perm[right - 1]] : Y[perm[right - 1]]) >= split) --right;
-                if (left < right) {
-                    const uint8_t s = perm[left]; perm[left] = perm[right - 1]; perm[right - 1] = s;
-                    ++left; --right;
-                }
-            }
-            if (left == begin) { ++left; ++right; }
-            t.left = (uint8_t)(node + 1);
-            t.right = (uint8_t)(node + 2 * (left - begin));
-            stk[sp][0] = (uint8_t)left; stk[sp][1] = (uint8_t)end; stk[sp][2] = t.right; ++sp;
-            stk[sp][0] = (uint8_t)begin; stk[sp][1] = (uint8_t)left; stk[sp][2] = t.left; ++sp;
-        }
-        T[node] = t;
-    }
-    // query: a node popped with distance d is walked only if d < rangeSq at that moment (the recursion tests
-    // the nearer child at once and the farther one after the nearer subtree; ties visit the right first)
-    const int maxN = A - 1;
-    float nd[CN_ORCA_MAXA];
-    int cnt = 0;
-    float dst[CN_ORCA_MAXA + 2];
-    uint8_t nst[CN_ORCA_MAXA + 2];
-    sp = 0;
-    nst[0] = 0; dst[0] = -1.0f; sp = 1;
-    const float x0 = X[0], y0 = Y[0];
-    while (sp > 0) {
-        --sp;
-        const int node = nst[sp];
-        if (!(dst[sp] < rangeSq)) continue;
-        const KdNodeS &t = T[node];
-        if (t.end - t.begin <= 10) {
-            for (int i = t.begin; i < t.end; ++i) {   // Agent::insertAgentNeighbor
-                const int a = perm[i];
-                if (a == 0) continue;
-                const float dx = x0 - X[a], dy = y0 - Y[a];
-                const float distSq = dx * dx + dy * dy;
-                if (distSq < rangeSq) {
-                    if (cnt < maxN) { nd[cnt] = distSq; nb[cnt] = (uint8_t)a; ++cnt; }
-                    int k = cnt - 1;
-                    while (k != 0 && distSq < nd[k - 1]) { nd[k] = nd[k - 1]; nb[k] = nb[k - 1]; --k; }
-                    nd[k] = distSq; nb[k] = (uint8_t)a;
-                    if (cnt == maxN) rangeSq = nd[cnt - 1];
-                }
-            }
-            continue;
-        }
-        const float dl = kd_bdist(T[t.left], x0, y0), dr = kd_bdist(T[t.right], x0, y0);
-        if (dl < dr) { nst[sp] = t.right; dst[sp] = dr; nst[sp + 1] = t.left; dst[sp + 1] = dl; }
-        else { nst[sp] = t.left; dst[sp] = dl; nst[sp + 1] = t.right; dst[sp + 1] = dr; }
-        sp += 2;
-    }
-    return cnt;
-}
-
-// LDS of one cn_orca_kd_kernel workgroup, sized by the simulators' agent count A (dynamic): 16 quads' lines
-// and projected lines [A - 1] float4 each, positions [A] float x 2, agents_ order and neighbours [A] bytes, counts.
-// (Sized for CN_ORCA_MAXA it was 42.5 KB, 3 one-wave workgroups per CU; at A = 26, 17 KB: 9.)
-__host__ __device__ inline int orca_kd_lds(int A)
-{
-    return 16 * (2 * 16 * (A - 1) + 2 * 4 * A) + ((2 * 16 * A + 15) & ~15) + 16 * 4;
-}
-
-__global__ void __launch_bounds__(64) cn_orca_kd_kernel(int64_t n, int A, const float *__restrict__ ag,
-                                                        const float *__restrict__ self, float nd, float th, float ts,
-                                                        uint8_t *__restrict__ perm_io, float *__restrict__ out)
-{
-    extern __shared__ __attribute__((aligned(16))) char kd_smem[];
-    const int q = threadIdx.x >> 2, sq = threadIdx.x & 3;
-    float4 *Lq = (float4 *)kd_smem + q * (A - 1);                 // [16][A - 1]
-    float4 *Pq = (float4 *)kd_smem + 16 * (A - 1) + q * (A - 1);  // [16][A - 1]
-    float *Xq = (float *)(kd_smem + 16 * 2 * 16 * (A - 1)) + q * A;
-    float *Yq = (float *)(kd_smem + 16 * 2 * 16 * (A - 1)) + 16 * A + q * A;
-    uint8_t *Pmq = (uint8_t *)(kd_smem + 16 * (2 * 16 * (A - 1) + 2 * 4 * A)) + q * A;
-    uint8_t *Nbq = (uint8_t *)(kd_smem + 16 * (2 * 16 * (A - 1) + 2 * 4 * A)) + 16 * A + q * A;
-    int *Cn = (int *)(kd_smem + orca_kd_lds(A) - 16 * 4);
-    const int64_t i = (int64_t)blockIdx.x * 16 + q;
-    const bool act = i < n;
-    const float *a = ag + (act ? i : 0) * A * 5;
-    if (act)
-        for (int k = sq; k < A; k += 4) {
-            Xq[k] = a[k * 5]; Yq[k] = a[k * 5 + 1];
-            Pmq[k] = perm_io ? perm_io[i * A + k] : (uint8_t)k;
-        }
-    wsync();
-    if (act && sq == 0) Cn[q] = A > 1 ? kd_neighbors_seq(A, Xq, Yq, Pmq, nd * nd, Nbq) : 0;
-    wsync();
-    if (act) {
-        const int cnt = Cn[q];
-        const float invTH = fdiv(1.0f, th), invTS = fdiv(1.0f, ts);
-        for (int k = sq; k < cnt; k += 4) {
-            const float *o = a + Nbq[k] * 5;
-            Lq[k] = orca_line(a[0], a[1], a[2], a[3], a[4], o[0], o[1], o[2], o[3], o[4], invTH, invTS);
-        }
-        if (perm_io)
-            for (int k = sq; k < A; k += 4) perm_io[i * A + k] = Pmq[k];
-    }
-    wsync();
-    if (act) {
-        const int cnt = Cn[q];
-        const float vmax = self[3 * i], ox = self[3 * i + 1], oy = self[3 * i + 2];
-        float rx, ry;
-        const int fail_at = lp2_q<uint64_t>(Lq, cnt, vmax, ox, oy, sq, rx, ry);
-        if (fail_at < cnt) lp3_q<uint64_t>(Lq, Pq, cnt, fail_at, vmax, sq, rx, ry);
-        if (sq == 0) {
-            out[4 * i] = rx; out[4 * i + 1] = ry; out[4 * i + 2] = (float)fail_at; out[4 * i + 3] = (float)cnt;
-        }
-    }
-}
-
-// cn_social_force_predict: SOCIAL_FORCE.predict (social_force.py:11-66) for n agents, one lane each, f64 in
-// the reference's operation order (the step kernel's phase 2 on caller-given states)
-__global__ void __launch_bounds__(64) cn_sf_predict_kernel(int64_t n, int M, const double *__restrict__ self,
-                                                           const double *__restrict__ others, double A, double B,
-                                                           double KI, double dt, double *__restrict__ out)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const double *s = self + 9 * i;   // px, py, vx, vy, radius, gx, gy, v_pref, theta
-    const double px = s[0], py = s[1], vx0 = s[2], vy0 = s[3], rad = s[4], vpref = s[7];
-    const double gdx = s[5] - px, gdy = s[6] - py;
-    const double dg = dsqrt(gdx * gdx + gdy * gdy);
-    const double dvx = ddiv(gdx, dg) * vpref, dvy = ddiv(gdy, dg) * vpref;
-    const double cdx = KI * (dvx - vx0), cdy = KI * (dvy - vy0);
-    double ix = 0.0, iy = 0.0;
-    for (int k = 0; k < M; ++k) {
-        const double *o = others + (i * M + k) * 5;   // px, py, vx, vy, radius
-        const double ddx = px - o[0], ddy = py - o[1];
-        const double d = dsqrt(ddx * ddx + ddy * ddy);
-        const double ex = exp(ddiv(rad + o[4] - d, B));
-        ix += A * ex * ddiv(ddx, d);
-        iy += A * ex * ddiv(ddy, d);
-    }
-    const double nx = vx0 + (cdx + ix) * dt, ny = vy0 + (cdy + iy) * dt;
-    const double nn = np_norm2(nx, ny);
-    if (nn > vpref) { out[2 * i] = ddiv(nx, nn) * vpref; out[2 * i + 1] = ddiv(ny, nn) * vpref; }
-    else { out[2 * i] = nx; out[2 * i + 1] = ny; }
-}
-
-// ------------------------------------------------------------------------------------------------
-// cn_robot_act: the scripted robot (ORCA / social force) on the engine's CURRENT state, read straight from
-// the blob: policy_factory[name](config).predict(JointState(robot FullState, [ObservableState(b_px, b_py,
-// b_vx, b_vy, b_r) of the N humans in index order])) of a fresh policy object per env, rounded to float32.
-// Pure functions of the state (nothing held between calls), one launch each.
-// ------------------------------------------------------------------------------------------------
-// (robot_sim_agent, robot_pref_velocity, robot_orca_lines / robot_orca_solve and robot_sf_velocity are defined above
-// cn_step_kernel, whose rollout variant computes the same actions inside its multi-step launches)
-// ORCA, N + 1 <= 10 agents: cn_orca_kernel's quad path (one quad per env, 16 envs per 64-lane workgroup).
-// `act` depends on the quad alone, so a quad is whole or absent and its control flow uniform (DESIGN.md §4,
-// "Cross-lane reads"): the quad's 4 lanes read the same state words.
-__global__ void __launch_bounds__(64) cn_robot_orca_kernel(cn_state_ptrs S, int E, int N, double safety, float nd,
-                                                           float th, float ts, float *__restrict__ actions)
-{
-    __shared__ float4 Ls[16][9];
-    const int q = threadIdx.x >> 2, sq = threadIdx.x & 3;
-    const int64_t e = (int64_t)blockIdx.x * 16 + q;
-    const bool act = e < E;
-    int cnt = 0;
-    if (act) cnt = robot_orca_lines(S, safety, e, N, sq, nd, th, ts, Ls[q]);
-    wsync();
-    if (act) {
-        float rx, ry;
-        robot_orca_solve(S, e, cnt, sq, Ls[q], rx, ry);
-        if (sq == 0) { actions[2 * e] = rx; actions[2 * e + 1] = ry; }
-    }
-}
-
-// ORCA, N + 1 > 10 agents: cn_orca_kd_kernel's path with a fresh simulator's identity agent order (LDS sized by
-// A = N + 1: orca_kd_lds)
-__global__ void __launch_bounds__(64) cn_robot_orca_kd_kernel(cn_state_ptrs S, int E, int N, double safety, float nd,
-                                                              float th, float ts, float *__restrict__ actions)
-{
-    extern __shared__ __attribute__((aligned(16))) char kd_smem[];
-    const int A = N + 1;
-    const int q = threadIdx.x >> 2, sq = threadIdx.x & 3;
-    float4 *Lq = (float4 *)kd_smem + q * (A - 1);                 // [16][A - 1]
-    float4 *Pq = (float4 *)kd_smem + 16 * (A - 1) + q * (A - 1);  // [16][A - 1]
-    float *Xq = (float *)(kd_smem + 16 * 2 * 16 * (A - 1)) + q * A;
-    float *Yq = (float *)(kd_smem + 16 * 2 * 16 * (A - 1)) + 16 * A + q * A;
-    uint8_t *Pmq = (uint8_t *)(kd_smem + 16 * (2 * 16 * (A - 1) + 2 * 4 * A)) + q * A;
-    uint8_t *Nbq = (uint8_t *)(kd_smem + 16 * (2 * 16 * (A - 1) + 2 * 4 * A)) + 16 * A + q * A;
-    int *Cn = (int *)(kd_smem + orca_kd_lds(A) - 16 * 4);
-    const int64_t e = (int64_t)blockIdx.x * 16 + q;
-    const bool act = e < E;
-    if (act)
-        for (int k = sq; k < A; k += 4) {
-            float x, y, vx, vy, r;
-            robot_sim_agent(S, safety, e, N, k, x, y, vx, vy, r);
-            Xq[k] = x; Yq[k] = y;
-            Pmq[k] = (uint8_t)k;
-        }
-    wsync();
-    if (act && sq == 0) Cn[q] = kd_neighbors_seq(A, Xq, Yq, Pmq, nd * nd, Nbq);
-    wsync();
-    if (act) {
-        const int cnt = Cn[q];
-        const float invTH = fdiv(1.0f, th), invTS = fdiv(1.0f, ts);
-        float X0, Y0, VX0, VY0, R0;
-        robot_sim_agent(S, safety, e, N, 0, X0, Y0, VX0, VY0, R0);
-        for (int k = sq; k < cnt; k += 4) {
-            float x, y, vx, vy, r;
-            robot_sim_agent(S, safety, e, N, Nbq[k], x, y, vx, vy, r);
-            Lq[k] = orca_line(X0, Y0, VX0, VY0, R0, x, y, vx, vy, r, invTH, invTS);
-        }
-    }
-    wsync();
-    if (act) {
-        const int cnt = Cn[q];
-        float vmax, ox, oy, rx, ry;
-        robot_pref_velocity(S, e, vmax, ox, oy);
-        const int fail_at = lp2_q<uint64_t>(Lq, cnt, vmax, ox, oy, sq, rx, ry);
-        if (fail_at < cnt) lp3_q<uint64_t>(Lq, Pq, cnt, fail_at, vmax, sq, rx, ry);
-        if (sq == 0) { actions[2 * e] = rx; actions[2 * e + 1] = ry; }
-    }
-}
-
-// Social force: cn_sf_predict_kernel's float64 arithmetic on the robot's FullState and the N belief humans,
-// one lane per env; the ActionXY rounded to float32
-__global__ void __launch_bounds__(64) cn_robot_sf_kernel(cn_state_ptrs S, int E, int N, double A, double B, double KI,
-                                                         double dt, float *__restrict__ actions)
-{
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= E) return;
-    double nx, ny, nn, vpref;
-    robot_sf_velocity(S, e, N, A, B, KI, dt, nx, ny, nn, vpref);
-    if (nn > vpref) { actions[2 * e] = (float)(ddiv(nx, nn) * vpref); actions[2 * e + 1] = (float)(ddiv(ny, nn) * vpref); }
-    else { actions[2 * e] = (float)nx; actions[2 * e + 1] = (float)ny; }
-}
-
-// One control word of the engine set from the stream (graph mode's draw-all flag after cn_reset /
-// cn_set_state). A kernel, not hipMemsetAsync: captured into a hipGraph it is a kernel node, and this
-// runtime replays memset nodes with stale bytes (cn_graph_node_counts).
-__global__ void cn_ctl_set_kernel(uint32_t *w, uint32_t v)
-{
-    if (threadIdx.x == 0) *w = v;
-}
-
-static int ctl_set(uint32_t *w, uint32_t v, hipStream_t st)
-{
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(cn_ctl_set_kernel, dim3(1), dim3(64), 0, st, w, v);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? CN_OK : set_err(CN_EHIP, hipGetErrorString(e));
-}
-
-// Key snapshot for a PEND_BOTH launch (after cn_set_state, and the quad path's cn_reset): every env's
-// {e, reset_count, case_counter lo, hi} into the spawn list the next step launch reads (kr = (t + 2) % 3 for
-// launch t: the host's sequence number, or graph mode's device word). That launch's spawn waves key both of an
-// env's pending spawns from this entry, not from the state its own step workgroups rewrite when a terminal env
-// resets inline (crowd_sim_dict.py:147-164: the seed of the k-th reset is offset + case_counter + thisSeed).
-__global__ void cn_keysnap_kernel(const int32_t *__restrict__ reset_count, const int64_t *__restrict__ case_counter,
-                                  uint32_t *plist_base, const uint32_t *ctl, int host_kr, int E)
-{
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= E) return;
-    const int64_t kr = host_kr >= 0 ? host_kr : (int64_t)((ctl[CN_CTL_NSTEP] + 2u) % 3u);
-    uint32_t *q = plist_base + kr * 4 * ((int64_t)E + 64) + 4 * (int64_t)e;
-    const uint64_t cc = (uint64_t)case_counter[e];
-    const uint4 v = make_uint4((uint32_t)e, (uint32_t)reset_count[e], (uint32_t)cc, (uint32_t)(cc >> 32));
-    *(uint4 *)q = v;
-}
-
-// the snapshot for the engine's next step launch (g->nstep: the host sequence; graph mode reads the device's)
-static int keysnap(const cn_engine *g, hipStream_t st)
-{
-    const int host_kr = g->devseq ? -1 : (int)((g->nstep + 2) % 3);
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(cn_keysnap_kernel, dim3((g->E + 255) / 256), dim3(256), 0, st, g->s.reset_count, g->s.case_counter,
-                       g->plist, (const uint32_t *)g->work_count, host_kr, (int)g->E);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? CN_OK : set_err(CN_EHIP, hipGetErrorString(e));
-}
-
-extern "C" {
-
-int cn_graph_node_counts(void *graph, int64_t *counts, int n, int64_t *total)
-{
-    if (!graph || (n > 0 && !counts) || n < 0 || n > 32) return set_err(CN_EINVAL, "cn_graph_node_counts: graph, 0 <= n <= 32");
-    for (int k = 0; k < n; ++k) counts[k] = 0;
-    size_t num = 0;
-    HIPCHK(hipGraphGetNodes((hipGraph_t)graph, nullptr, &num));
-    std::vector<hipGraphNode_t> nodes(num);
-    if (num) HIPCHK(hipGraphGetNodes((hipGraph_t)graph, nodes.data(), &num));
-    for (size_t i = 0; i < num; ++i) {
-        hipGraphNodeType t;
-        HIPCHK(hipGraphNodeGetType(nodes[i], &t));
-        if ((int)t >= 0 && (int)t < n) ++counts[(int)t];
-    }
-    if (total) *total = (int64_t)num;
-    return CN_OK;
-}
-
-const char *cn_last_error(void) { return g_err; }
-#ifndef CN_SRC_HASH
-#define CN_SRC_HASH "unversioned"
-#endif
-// build.py passes the sha256 of the flags + sources; _lib.lib() compares it with the sources on disk
-const char *cn_version(void) { return "crowdnav_dsrnn_amd 0.2 (gfx950) CN_SRC_HASH=" CN_SRC_HASH; }
-
-int cn_config_validate(const cn_config *c)
-{
-    if (!c) return set_err(CN_EINVAL, "null config");
-    if (c->num_envs <= 0) return set_err(CN_EINVAL, "num_envs must be > 0");
-    if ((int64_t)c->num_envs * (c->human_num + 1) >= (1LL << 31) / 8)
-        return set_err(CN_EUNSUPPORTED, "num_envs * human_num too large for one engine (shard over engines)");
-    if (c->human_num < 1 || c->human_num > 31) return set_err(CN_EUNSUPPORTED, "human_num must be in [1, 31]");
-    if (c->human_num + (c->robot_visible ? 1 : 0) > CN_MAX_A) return set_err(CN_EUNSUPPORTED, "too many agents");
-    if (c->num_scenarios < 1 || c->num_scenarios > CN_MAX_SCENARIOS) return set_err(CN_EINVAL, "num_scenarios");
-    for (int k = 0; k < c->num_scenarios; ++k)
-        if (c->scenarios[k] < 0 || c->scenarios[k] > CN_SC_SIDE_PREF_CROSSING) return set_err(CN_EINVAL, "scenario id");
-    if (c->kinematics != CN_HOLONOMIC && c->kinematics != CN_UNICYCLE) return set_err(CN_EINVAL, "kinematics");
-    if (c->rng_mode != CN_RNG_MT19937 && c->rng_mode != CN_RNG_PHILOX) return set_err(CN_EINVAL, "rng_mode");
-    if (c->human_policy != CN_POLICY_ORCA && c->human_policy != CN_POLICY_SOCIAL_FORCE)
-        return set_err(CN_EUNSUPPORTED, "human policy");
-    if (!c->potential_based) return set_err(CN_EUNSUPPORTED, "only potential-based reward shaping is supported");
-    if (!(c->time_step > 0)) return set_err(CN_EINVAL, "time_step must be > 0");
-    if (c->phase < 0 || c->phase > 2) return set_err(CN_EINVAL, "phase");
-    if (c->nenv <= 0) return set_err(CN_EINVAL, "nenv must be > 0");
-    if (c->max_tries <= 0) return set_err(CN_EINVAL, "max_tries must be > 0");
-    return CN_OK;
-}
-
-int cn_state_field_info(int field, const char **name, int *type_code, int *count_kind)
-{
-    static const char *names[] = {
-#define X(n, ct, tc, ck) #n,
-        CN_STATE_FIELDS(X)
-#undef X
-    };
-    static const int tcs[] = {
-#define X(n, ct, tc, ck) tc,
-        CN_STATE_FIELDS(X)
-#undef X
-    };
-    static const int cks[] = {
-#define X(n, ct, tc, ck) ck,
-        CN_STATE_FIELDS(X)
-#undef X
-    };
-    if (field < 0 || field >= CN_NUM_FIELDS) return set_err(CN_EINVAL, "field index");
-    if (name) *name = names[field];
-    if (type_code) *type_code = tcs[field];
-    if (count_kind) *count_kind = cks[field];
-    return CN_OK;
-}
-
-int cn_state_layout_offsets(const cn_config *cfg, int64_t *offsets, int64_t *total)
-{
-    if (!cfg) return set_err(CN_EINVAL, "null config");
-    const int64_t t = cn_state_layout(cfg->num_envs, cfg->human_num, cfg->robot_visible, offsets);
-    if (total) *total = t;
-    return CN_OK;
-}
-
-int cn_create(const cn_config *cfg, int device, cn_engine **out)
-{
-    if (!out) return set_err(CN_EINVAL, "null out");
-    *out = nullptr;
-    int rc = cn_config_validate(cfg);
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(device));
-    cn_engine *g = new cn_engine();
-    g->c = *cfg;
-    g->device = device;
-    g->E = cfg->num_envs;
-    g->N = cfg->human_num;
-    g->NS = g->N;
-    g->A = cn_sim_agents(g->N, cfg->robot_visible);
-    g->plan = cn_step_plan(g->N, cfg->robot_visible);
-    g->state_bytes = cn_state_layout(g->E, g->N, cfg->robot_visible, nullptr);
-    switch (cfg->phase) {
-    case CN_PHASE_TRAIN: g->case_size = 4294967295LL - 2000; g->counter_offset = 2000; break;
-    case CN_PHASE_VAL: g->case_size = cfg->val_size; g->counter_offset = 0; break;
-    default: g->case_size = cfg->test_size; g->counter_offset = 1000; break;
-    }
-    if (g->case_size <= 0) { delete g; return set_err(CN_EINVAL, "case size (val_size/test_size) must be > 0"); }
-    const int64_t E = g->E, EN = (int64_t)g->E * g->N;
-    auto al = [](int64_t b) { return (b + 255) & ~(int64_t)255; };
-    // pending spawns: every array holds both slots ([2][...], pend_slot)
-    const int64_t pb_mt = al(2 * E * CN_MT_N * 4), pb_i = al(2 * E * 4), pb_cc = al(2 * E * 8), pb_r = al(2 * 5 * E * 8),
-                  pb_h = al(2 * 7 * EN * 8);
-    const int64_t pend_bytes = pb_mt + 5 * pb_i + 2 * pb_cc + pb_r + pb_h;
-    hipError_t e1 = hipMalloc(&g->state, g->state_bytes);
-    hipError_t e2 = hipMalloc(&g->work, sizeof(uint32_t) * (g->E + 64));
-    hipError_t e3 = hipMalloc(&g->work_count, 64);
-    hipError_t e4 = hipMalloc(&g->plist, sizeof(uint32_t) * 3 * 4 * (g->E + 64));
-    hipError_t e6 = hipMalloc(&g->rlist, sizeof(uint32_t) * 3 * 4 * (2 * (int64_t)g->E + 64));
-    hipError_t e5 = hipMalloc(&g->pend_mem, pend_bytes);
-    if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess || e4 != hipSuccess || e5 != hipSuccess ||
-        e6 != hipSuccess) {
-        (void)hipFree(g->state); (void)hipFree(g->work); (void)hipFree(g->work_count); (void)hipFree(g->plist); (void)hipFree(g->pend_mem);
-        (void)hipFree(g->rlist);
-        delete g;
-        return set_err(CN_ENOMEM, "hipMalloc failed");
-    }
-    if (hipMemset(g->state, 0, g->state_bytes) != hipSuccess || hipMemset(g->work_count, 0, 64) != hipSuccess ||
-        hipMemset(g->pend_mem, 0, pend_bytes) != hipSuccess) {
-        cn_destroy(g);
-        return set_err(CN_EHIP, "hipMemset failed");
-    }
-    {
-        char *b = (char *)g->pend_mem;
-        g->pend.mt = (uint32_t *)b; b += pb_mt;
-        g->pend.pos = (int32_t *)b; b += pb_i;
-        g->pend.ovf = (uint32_t *)b; b += pb_i;
-        g->pend.sc = (int32_t *)b; b += pb_i;
-        g->pend.rc = (int32_t *)b; b += pb_i;
-        g->pend.ok = (uint64_t *)b; b += pb_cc;
-        g->pend.prog = (int32_t *)b; b += pb_i;
-        g->pend.cc = (int64_t *)b; b += pb_cc;
-        g->pend.r = (double *)b; b += pb_r;
-        g->pend.h = (double *)b;
-    }
-    g->pend_all = PEND_BOTH;
-    {
-        // the plan holds phase 5's RNG regions (laid over the ORCA scratch); spare workgroups run as many
-        // spawning waves as regions fit in the same allocation
-        g->a_lds = g->plan.total;
-        const int fit = g->a_lds / g->plan.rng_stride;
-        g->pend_waves = fit < g->plan.T / 64 ? fit : g->plan.T / 64;
-        const int nw = g->pend_waves;
-        const int64_t need = (E + nw - 1) / nw;
-        // ~128 spawning waves on the quad path; 256 on the kd-tree path, whose crowded spawns (~1M cycles
-        // each at 25 humans in square_crossing, ~4 % of the envs per step) must not queue behind each other
-        const int cap = (g->plan.kd ? 256 : CN_QUAD_SPAWN_WAVES) / nw;
-        const int pb = (int)(need < cap ? need : cap);
-        g->pend_blocks = g->plan.kd ? (pb + 7) & ~7 : pb;   // leading: a multiple of 8 (XCD placement)
-        // kd-tree path: a crowded spawn may take longer than the launch's step rounds; each spawning wave parks
-        // its spawn after ~0.6 M cycles and a later launch resumes it (the spawn is needed one whole episode
-        // later). Round 5: spawn-list entries carry the counters of the reset that queued them (a spawn wave
-        // that read them from the state could see a later reset of the same env and queue a key that the next
-        // launch queued again: two writers of one pending slot, one of them resuming from it -- 5 of 149 C3 runs
-        // departed; 0 of 149 with keyed entries). The quad path parks after CN_QUAD_BUDGET cycles (round 6).
-        g->spawn_budget = g->plan.kd ? 600000 : (CN_QUAD_PARK ? CN_QUAD_BUDGET : 0);
-        g->seq_chunk = CN_SEQ_CHUNK;
-    }
-    cn_state_bind(&g->s, g->state, g->E, g->N, cfg->robot_visible);
-    if (circ_table_init() != hipSuccess) {
-        cn_destroy(g);
-        return set_err(CN_EHIP, "hipMemcpyToSymbol failed");
-    }
-    if (g->a_lds > 160 * 1024) { cn_destroy(g); return set_err(CN_EUNSUPPORTED, "LDS plan exceeds 160 KiB"); }
-    if (g->a_lds > 64 * 1024) {
-        const void *ks[10] = {(const void *)cn_step_kernel<false, false, false, false, true>,
-                              (const void *)cn_step_kernel<false, true, false, false, true>,
-                             (const void *)cn_step_kernel<true, false, false>, (const void *)cn_step_kernel<false, false, false>,
-                             (const void *)cn_step_kernel<true, true, false>, (const void *)cn_step_kernel<false, true, false>,
-                             (const void *)cn_step_kernel<true, false, true>, (const void *)cn_step_kernel<false, false, true>,
-                             (const void *)cn_step_kernel<true, true, true>, (const void *)cn_step_kernel<false, true, true>};
-        for (const void *k : ks) (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, g->a_lds);
-    }
-    g->rng_grid = g->E < 2048 ? g->E : 2048;
-    // the first launch draws every env's spawns (PEND_BOTH) from the key snapshot of the zeroed state
-    if (keysnap(g, nullptr) != CN_OK) { cn_destroy(g); return CN_EHIP; }
-    HIPCHK(hipDeviceSynchronize());
-    *out = g;
-    return CN_OK;
-}
-
-// Mixed engine (per-env scenario dispatch with per-env human counts). Env r of the engine
-// (global index cfg.env_offset + r) belongs to group env_group[r]; each group is a plain engine over its
-// envs with its own cn_config (human count, scenario set, circle radius, side preference, goal changing,
-// ...), stepping them in the caller's (E, ...) buffers at their own rows (spatial_edges padded to the
-// largest human count). Seeds and round-robin scenarios use the global index, so groups[g].scenarios
-// must be the full scenario list and env r's scenario (scenarios[(env_offset + r) % num_scenarios]) must
-// be one its group was configured for -- which the caller guarantees by assigning groups per scenario.
-int cn_create_mixed(const cn_config *groups, int num_groups, const int32_t *env_group, int64_t num_envs, int device,
-                    cn_engine **out)
-{
-    if (!out) return set_err(CN_EINVAL, "null out");
-    *out = nullptr;
-    if (!groups || !env_group || num_groups < 1 || num_groups > 64 || num_envs <= 0)
-        return set_err(CN_EINVAL, "cn_create_mixed: 1..64 groups, env_group[num_envs] required");
-    if (num_envs >= (1LL << 31) / 64) return set_err(CN_EUNSUPPORTED, "cn_create_mixed: too many envs");
-    std::vector<std::vector<int32_t>> rows(num_groups);
-    for (int64_t r = 0; r < num_envs; ++r) {
-        if (env_group[r] < 0 || env_group[r] >= num_groups) return set_err(CN_EINVAL, "cn_create_mixed: env_group out of range");
-        rows[env_group[r]].push_back((int32_t)r);
-    }
-    int NS = 0;
-    for (int k = 0; k < num_groups; ++k) {
-        const cn_config &c = groups[k];
-        if ((int64_t)c.num_envs != (int64_t)rows[k].size())
-            return set_err(CN_EINVAL, "cn_create_mixed: groups[g].num_envs must equal the envs assigned to group g");
-        if (c.env_offset != groups[0].env_offset || c.nenv != groups[0].nenv || c.seed != groups[0].seed ||
-            c.phase != groups[0].phase)
-            return set_err(CN_EINVAL, "cn_create_mixed: env_offset / nenv / seed / phase must agree across groups");
-        if (c.scenario_mode != CN_SCMODE_ROUND_ROBIN)
-            return set_err(CN_EUNSUPPORTED, "cn_create_mixed: round-robin scenario mode only");
-        NS = c.human_num > NS ? c.human_num : NS;
-    }
-    HIPCHK(hipSetDevice(device));
-    cn_engine *m = new cn_engine();
-    m->c = groups[0];
-    m->c.num_envs = (int32_t)num_envs;
-    m->c.human_num = NS;
-    m->device = device;
-    m->E = (int)num_envs;
-    m->N = m->NS = NS;
-    m->grp = new cn_engine *[num_groups]();
-    for (int k = 0; k < num_groups; ++k) {
-        if (groups[k].num_envs == 0) continue;
-        int rc = cn_create(&groups[k], device, &m->grp[m->ngroups]);
-        if (rc) { cn_destroy(m); return rc; }
-        cn_engine *g = m->grp[m->ngroups++];
-        g->NS = NS;
-        if (hipMalloc(&g->rows, sizeof(int32_t) * rows[k].size()) != hipSuccess) {
-            cn_destroy(m);
-            return set_err(CN_ENOMEM, "hipMalloc failed");
-        }
-        if (hipMemcpy(g->rows, rows[k].data(), sizeof(int32_t) * rows[k].size(), hipMemcpyHostToDevice) != hipSuccess) {
-            cn_destroy(m);
-            return set_err(CN_EHIP, "hipMemcpy failed");
-        }
-        m->state_bytes += g->state_bytes;
-    }
-    // the groups' step launches are independent (disjoint envs and output rows): run them concurrently,
-    // group 0 on the caller's stream, group k > 0 on its own stream forked after the caller's prior work
-    // and joined back before the caller's next work (stream order is kept for the caller)
-    m->gstream = new hipStream_t[m->ngroups]();
-    m->gev = new hipEvent_t[m->ngroups + 1]();
-    for (int k = 0; k <= m->ngroups; ++k)
-        if (hipEventCreateWithFlags(&m->gev[k], hipEventDisableTiming) != hipSuccess) {
-            cn_destroy(m);
-            return set_err(CN_EHIP, "hipEventCreate failed");
-        }
-    for (int k = 1; k < m->ngroups; ++k)
-        if (hipStreamCreateWithFlags(&m->gstream[k], hipStreamNonBlocking) != hipSuccess) {
-            cn_destroy(m);
-            return set_err(CN_EHIP, "hipStreamCreate failed");
-        }
-    *out = m;
-    return CN_OK;
-}
-
-// per-env human count of an engine (plain: N everywhere), into host memory [E]
-int cn_env_humans(const cn_engine *g, int32_t *dst)
-{
-    if (!g || !dst) return set_err(CN_EINVAL, "null argument");
-    if (!g->ngroups) {
-        for (int64_t r = 0; r < g->E; ++r) dst[r] = g->N;
-        return CN_OK;
-    }
-    for (int k = 0; k < g->ngroups; ++k) {
-        const cn_engine *q = g->grp[k];
-        std::vector<int32_t> rows(q->E);
-        HIPCHK(hipMemcpy(rows.data(), q->rows, sizeof(int32_t) * q->E, hipMemcpyDeviceToHost));
-        for (int64_t e = 0; e < q->E; ++e) dst[rows[e]] = q->N;
-    }
-    return CN_OK;
-}
-
-static void prof_free(cn_engine *g)
-{
-    if (g->ev) {
-        for (int k = 0; k < 2; ++k) (void)hipEventDestroy(g->ev[k]);
-        delete[] g->ev;
-    }
-    g->ev = nullptr;
-    g->prof_cap = g->prof_n = g->prof_on = 0;
-}
-
-// Two events bracket the whole window of `max_steps` launches (one before the first, one after the
-// last): per-launch event pairs cost ~12 us of stream time each on this GPU, more than the launch gaps
-// they would exclude (back-to-back step launches are separated by < 0.2 us).
-int cn_profile(cn_engine *g, int enable, int max_steps)
-{
-    if (!g) return set_err(CN_EINVAL, "null engine");
-    prof_free(g);
-    if (!enable) return CN_OK;
-    if (max_steps <= 0) return set_err(CN_EINVAL, "max_steps must be > 0");
-    g->ev = new hipEvent_t[2];
-    for (int k = 0; k < 2; ++k) HIPCHK(hipEventCreate(&g->ev[k]));
-    g->prof_cap = max_steps;
-    g->prof_on = 1;
-    return CN_OK;
-}
-
-int cn_profile_read(cn_engine *g, double *a_ms, double *b_ms, int64_t *launches)
-{
-    if (!g) return set_err(CN_EINVAL, "null engine");
-    float ta = 0;
-    if (g->prof_n > 0) {
-        if (g->prof_n < g->prof_cap) return set_err(CN_EINVAL, "profile window not complete (fewer launches than max_steps)");
-        HIPCHK(hipEventSynchronize(g->ev[1]));
-        HIPCHK(hipEventElapsedTime(&ta, g->ev[0], g->ev[1]));
-    }
-    if (a_ms) *a_ms = ta;
-    if (b_ms) *b_ms = 0;
-    if (launches) *launches = g->prof_n;
-    return CN_OK;
-}
-
-void cn_destroy(cn_engine *g)
-{
-    if (!g) return;
-    (void)hipSetDevice(g->device);
-    prof_free(g);
-    if (g->grp) {
-        for (int k = 0; k < g->ngroups; ++k) cn_destroy(g->grp[k]);
-        if (g->gstream)
-            for (int k = 1; k < g->ngroups; ++k) (void)hipStreamDestroy(g->gstream[k]);
-        if (g->gev)
-            for (int k = 0; k <= g->ngroups; ++k) (void)hipEventDestroy(g->gev[k]);
-        delete[] g->grp;
-        delete[] g->gstream;
-        delete[] g->gev;
-        delete g;
-        return;
-    }
-    (void)hipFree(g->rows);
-    (void)hipFree(g->state);
-    (void)hipFree(g->work);
-    (void)hipFree(g->work_count);
-    (void)hipFree(g->plist);
-    (void)hipFree(g->rlist);
-    (void)hipFree(g->pend_mem);
-    delete g;
-}
-
-int cn_reset(cn_engine *g, void *stream, float *robot_node, float *temporal, float *spatial)
-{
-    if (!g || !robot_node || !temporal || !spatial) return set_err(CN_EINVAL, "null argument");
-    hipStream_t st = (hipStream_t)stream;
-    if (g->ngroups) {
-        for (int k = 0; k < g->ngroups; ++k) {
-            const int rc = cn_reset(g->grp[k], stream, robot_node, temporal, spatial);
-            if (rc) return rc;
-        }
-        return CN_OK;
-    }
-    RngArgs a;
-    a.o.s = g->s; a.o.robot_node = robot_node; a.o.temporal = temporal; a.o.spatial = spatial;
-    a.o.case_size = g->case_size;
-    a.o.ov.row = g->rows; a.o.ov.NS = g->NS;
-    a.pend = g->pend; a.E = g->E; a.counter_offset = g->counter_offset;
-    // the reset kernel draws the next two spawns too, so the first step launches (whose spawns would otherwise
-    // run inline in step workgroups until the budgeted spawn waves catch up) find them drawn (PEND_FRESH);
-    // without quad-path parking the quad path's first launch draws them (PEND_BOTH, as after cn_set_state)
-    a.draw_next = (g->plan.kd || CN_QUAD_PARK) ? 1 : 0;
-    (void)hipGetLastError();   // a stale error of an earlier call (any library) is not this launch's
-    hipLaunchKernelGGL(cn_reset_kernel, dim3(g->rng_grid), dim3(64), 0, st, a, g->c);
-    HIPCHK(hipGetLastError());
-    // every env starts a new episode (kd-tree path: with its next two spawns drawn): the next step launch
-    // draws them (none) and ignores the earlier launches' lists (host flag; graph mode: the device flag,
-    // stream-ordered)
-    g->pend_all = a.draw_next ? PEND_FRESH : PEND_BOTH;
-    if (!a.draw_next) {   // PEND_BOTH keys its items from a snapshot of the counters the reset kernel wrote
-        const int rk = keysnap(g, st);
-        if (rk) return rk;
-    }
-    if (g->devseq) return ctl_set(g->work_count + CN_CTL_ALL, (uint32_t)g->pend_all, st);
-    return CN_OK;
-}
-
-// One step launch. nsteps == 1: cn_step's launch (every engine, graph mode). nsteps > 1: a multi-step launch of
-// cn_step_seq (a plain quad-path engine outside graph mode, pend_all == 0: seq_fusable), whose step workgroups
-// run nsteps steps with the actions at actions + t * action_stride. g->nstep counts LAUNCHES (the triple-buffer
-// index of the spawn lists, the launch id, graph mode's hand-over); cn_profile's window counts STEPS.
-// rollout >= 0 (cn_rollout's fused launches, nsteps >= 1, same engines): StepArgs::rollout of the ROBOT kernels,
-// which compute the actions themselves and record every step at row t of the outputs (`actions` is written).
-static int step_launch(cn_engine *g, void *stream, const float *actions, int nsteps, int64_t action_stride,
-                       float *robot_node, float *temporal, float *spatial, float *reward, uint8_t *done, int8_t *event,
-                       float *info, double *ep_return, int32_t *ep_len, int64_t rollout = -1)
-{
-    if (!g || !actions || !robot_node || !temporal || !spatial) return set_err(CN_EINVAL, "null argument");
-    hipStream_t st = (hipStream_t)stream;
-    // spawn lists, triple-buffered: launch t appends to t%3, reads (t-1)%3, zeroes (t+1)%3 (host sequence;
-    // graph mode keeps it on the device, StepArgs::devseq)
-    const int kw = (int)(g->nstep % 3), kr = (int)((g->nstep + 2) % 3), kz = (int)((g->nstep + 1) % 3);
-    ++g->nstep;
-    // the window's events: before the launch of its first step, after the launch that completes the count
-    // (cn_step_seq splits a chunk that would straddle the end of the window)
-    const bool prof = g->prof_on && g->prof_n < g->prof_cap;
-    if (prof && g->prof_n == 0) HIPCHK(hipEventRecord(g->ev[0], st));
-    if (g->ngroups) {   // one step launch per group, concurrently (fork / join around the caller's stream)
-        if (g->ngroups > 1) HIPCHK(hipEventRecord(g->gev[0], st));
-        for (int k = 0; k < g->ngroups; ++k) {
-            hipStream_t sk = st;
-            if (k > 0) { sk = g->gstream[k]; HIPCHK(hipStreamWaitEvent(sk, g->gev[0], 0)); }
-            const int rc = cn_step(g->grp[k], (void *)sk, actions, robot_node, temporal, spatial, reward, done, event,
-                                   info, ep_return, ep_len);
-            if (rc) {   // join the groups already forked, so no side-stream work outlives the caller's order
-                for (int j = 1; j < k; ++j) (void)hipStreamWaitEvent(st, g->gev[j], 0);
-                return rc;
-            }
-            if (k > 0) HIPCHK(hipEventRecord(g->gev[k], sk));
-        }
-        for (int k = 1; k < g->ngroups; ++k) HIPCHK(hipStreamWaitEvent(st, g->gev[k], 0));
-        if (prof && ++g->prof_n == g->prof_cap) HIPCHK(hipEventRecord(g->ev[1], st));
-        return CN_OK;
-    }
-    StepArgs a;
-    a.s = g->s; a.actions = actions; a.robot_node = robot_node; a.temporal = temporal; a.spatial = spatial;
-    a.reward = reward; a.done = done; a.event = event; a.info = info; a.ep_return = ep_return; a.ep_len = ep_len;
-    a.E = g->E;
-    a.case_size = g->case_size;
-    a.ctl = g->work_count; a.plist_base = g->plist; a.rlist_base = g->rlist;
-    a.plist_w = g->plist + (int64_t)kw * 4 * (g->E + 64);
-    a.pcount_w = g->work_count + 2 + kw;
-    a.pcount_zero = g->work_count + 2 + kz;
-    a.rcount_zero = g->work_count + 5 + kz;
-    a.pend.rlist = g->rlist + (int64_t)kr * 4 * (2 * (int64_t)g->E + 64); a.pend.rcount = g->work_count + 5 + kr;
-    a.pend.rlist_w = g->rlist + (int64_t)kw * 4 * (2 * (int64_t)g->E + 64); a.pend.rcount_w = g->work_count + 5 + kw;
-    // the budget is clock cycles per STEP: a multi-step launch lasts nsteps times as long and draws the spawns its
-    // predecessor queued over as many steps, so its spawning waves get nsteps times the budget, the default one
-    // and one set through cn_debug_set_spawn_budget alike. (Taken per launch, a small test budget left a run of
-    // 300 steps with ~10 launches of one or two humans' progress each: no parked spawn ever completed.)
-    a.pend.budget = g->spawn_budget * nsteps;
-    a.nsteps = nsteps;
-    if (nsteps > 1) a.action_stride = action_stride;   // (shares ctl's slot: the SEQ kernels are never graph mode's)
-    if (rollout >= 0) a.rollout = rollout;
-    a.pend.stats = g->work_count + 8;
-    a.pend.launch_id = (uint32_t)(g->nstep % 0x7ffffffeu) + 1u;   // nonzero, differs from the neighbours'
-    const int blocks = (g->E + g->plan.EPB - 1) / g->plan.EPB;
-    a.pend.P = g->pend; a.pend.list = g->plist + (int64_t)kr * 4 * (g->E + 64); a.pend.count = g->work_count + 2 + kr;
-    a.pend.all = g->pend_all;
-    a.pend.step_blocks = blocks; a.pend.pend_blocks = g->pend_blocks; a.pend.counter_offset = g->counter_offset;
-    a.pend.first = g->plan.kd ? 1 : 0;
-    a.pend.waves = g->pend_waves;
-    a.pend.stride = g->plan.rng_stride;
-    a.pend.case_size = g->case_size;
-    a.ov.row = g->rows; a.ov.NS = g->NS;
-    a.pend.ov = a.ov;
-    a.cth_h = cos(g->c.human_fov / 2); a.cth_r = cos(g->c.robot_fov / 2);
-    g->pend_all = 0;
-    const int grid = blocks + g->pend_blocks;
-    const bool phx = g->c.rng_mode == CN_RNG_PHILOX;
-    const int variant = (g->plan.kd ? 4 : 0) | (phx ? 2 : 0) | (g->rows ? 1 : 0);
-    void (*const kern[8])(StepArgs, cn_config) = {
-        cn_step_kernel<false, false, false>, cn_step_kernel<false, false, true>, cn_step_kernel<false, true, false>,
-        cn_step_kernel<false, true, true>,   cn_step_kernel<true, false, false>,  cn_step_kernel<true, false, true>,
-        cn_step_kernel<true, true, false>,   cn_step_kernel<true, true, true>};
-    void (*const kern_dev[4])(StepArgs, cn_config) = {   // graph mode (plain engines)
-        cn_step_kernel<false, false, false, true>, cn_step_kernel<false, true, false, true>,
-        cn_step_kernel<true, false, false, true>, cn_step_kernel<true, true, false, true>};
-    void (*const kern_seq[2])(StepArgs, cn_config) = {   // multi-step launches (plain quad-path engines)
-        cn_step_kernel<false, false, false, false, true>, cn_step_kernel<false, true, false, false, true>};
-    void (*const kern_robot[2])(StepArgs, cn_config) = {   // cn_rollout's launches (the same engines)
-        cn_step_kernel<false, false, false, false, true, true>, cn_step_kernel<false, true, false, false, true, true>};
-    (void)hipGetLastError();   // a stale error of an earlier call (any library) is not this launch's
-    if (nsteps > 1 || rollout >= 0) {
-        if (g->devseq || g->rows || g->plan.kd || a.pend.all)
-            return set_err(CN_EINVAL, "multi-step launch: plain quad-path engine outside graph mode required");
-        hipLaunchKernelGGL((rollout >= 0 ? kern_robot : kern_seq)[phx ? 1 : 0], dim3(grid), dim3(g->plan.T), g->a_lds, st,
-                           a, g->c);
-    } else if (g->devseq)
-        hipLaunchKernelGGL(kern_dev[variant >> 1], dim3(grid), dim3(g->plan.T), g->a_lds, st, a, g->c);
-    else
-        hipLaunchKernelGGL(kern[variant], dim3(grid), dim3(g->plan.T), g->a_lds, st, a, g->c);
-    HIPCHK(hipGetLastError());
-    if (prof && (g->prof_n += nsteps) >= g->prof_cap) HIPCHK(hipEventRecord(g->ev[1], st));
-    return CN_OK;
-}
-
-int cn_step(cn_engine *g, void *stream, const float *actions, float *robot_node, float *temporal, float *spatial,
-            float *reward, uint8_t *done, int8_t *event, float *info, double *ep_return, int32_t *ep_len)
-{
-    return step_launch(g, stream, actions, 1, 0, robot_node, temporal, spatial, reward, done, event, info, ep_return,
-                       ep_len);
-}
-
-// T steps as ceil(T / C) multi-step launches of up to C = seq_chunk steps (the last one of the remainder), with
-// the results of T cn_step launches bit for bit. A launch per step where the multi-step kernels do not apply:
-// C == 1, mixed engines, graph mode, the kd-tree path (> 10 agents per simulator), and the first launch after
-// cn_reset / cn_set_state (pend_all != 0: its spawn waves redraw or ignore the pending lists; the chunks start
-// after it).
-int cn_step_seq(cn_engine *g, void *stream, int T, const float *actions, int64_t action_stride, float *robot_node,
-                float *temporal, float *spatial, float *reward, uint8_t *done, int8_t *event, float *info,
-                double *ep_return, int32_t *ep_len)
-{
-    if (!g || !actions) return set_err(CN_EINVAL, "null argument");
-    if (T < 0 || (T > 1 && action_stride < 2 * g->E))
-        return set_err(CN_EINVAL, "cn_step_seq: T >= 0 and action_stride >= 2 * E required");
-    const bool fusable = g->seq_chunk > 1 && !g->ngroups && !g->rows && !g->devseq && !g->plan.kd;
-    for (int t = 0; t < T;) {
-        int n = 1;
-        if (fusable && !g->pend_all) {
-            n = T - t < g->seq_chunk ? T - t : g->seq_chunk;
-            // a chunk never straddles the end of cn_profile's window: its last event follows the launch that
-            // completes the count
-            if (g->prof_on && g->prof_n < g->prof_cap && n > g->prof_cap - g->prof_n) n = g->prof_cap - g->prof_n;
-        }
-        const int rc = step_launch(g, stream, actions + (int64_t)t * action_stride, n, action_stride, robot_node,
-                                   temporal, spatial, reward, done, event, info, ep_return, ep_len);
-        if (rc) return rc;
-        t += n;
-    }
-    return CN_OK;
-}
-
-int cn_set_graph_mode(cn_engine *g, void *stream, int on)
-{
-    if (!g) return set_err(CN_EINVAL, "null argument");
-    hipStream_t st = (hipStream_t)stream;
-    if (g->ngroups || g->rows) return set_err(CN_EUNSUPPORTED, "graph mode: plain engines only (not cn_create_mixed)");
-    if (on && !g->devseq) {   // hand the host sequence to the device
-        g->ctl_host[0] = (uint32_t)g->nstep; g->ctl_host[1] = (uint32_t)g->pend_all; g->ctl_host[2] = 0u;
-        HIPCHK(hipMemcpyAsync(g->work_count + CN_CTL_NSTEP, g->ctl_host, 3 * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-        HIPCHK(hipStreamSynchronize(st));   // ctl_host may be rewritten by the next call
-    } else if (!on && g->devseq) {   // and back
-        HIPCHK(hipMemcpyAsync(g->ctl_host, g->work_count + CN_CTL_NSTEP, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        g->nstep = g->ctl_host[0]; g->pend_all = (int)g->ctl_host[1];
-    }
-    g->devseq = on ? 1 : 0;
-    return CN_OK;
-}
-
-int cn_state_bytes(const cn_engine *g, int64_t *bytes)
-{
-    if (!g || !bytes) return set_err(CN_EINVAL, "null argument");
-    *bytes = g->state_bytes;
-    return CN_OK;
-}
-
-const void *cn_state_device_ptr(const cn_engine *g) { return g && !g->ngroups ? g->state : nullptr; }
-
-int cn_get_state(cn_engine *g, void *stream, void *dst, int dst_on_host)
-{
-    if (!g || !dst) return set_err(CN_EINVAL, "null argument");
-    hipStream_t st = (hipStream_t)stream;
-    if (g->ngroups) {   // the groups' blobs, concatenated in group order
-        char *d = (char *)dst;
-        for (int k = 0; k < g->ngroups; ++k) {
-            const int rc = cn_get_state(g->grp[k], stream, d, dst_on_host);
-            if (rc) return rc;
-            d += g->grp[k]->state_bytes;
-        }
-        return CN_OK;
-    }
-    if (dst_on_host) {
-        HIPCHK(hipMemcpyAsync(dst, g->state, g->state_bytes, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-    } else {
-        HIPCHK(hipMemcpyAsync(dst, g->state, g->state_bytes, hipMemcpyDeviceToDevice, st));
-    }
-    return CN_OK;
-}
-
-int cn_set_state(cn_engine *g, void *stream, const void *src, int src_on_host)
-{
-    if (!g || !src) return set_err(CN_EINVAL, "null argument");
-    hipStream_t st = (hipStream_t)stream;
-    if (g->ngroups) {
-        const char *d = (const char *)src;
-        for (int k = 0; k < g->ngroups; ++k) {
-            const int rc = cn_set_state(g->grp[k], stream, d, src_on_host);
-            if (rc) return rc;
-            d += g->grp[k]->state_bytes;
-        }
-        return CN_OK;
-    }
-    if (src_on_host) {
-        HIPCHK(hipMemcpyAsync(g->state, src, g->state_bytes, hipMemcpyHostToDevice, st));
-        HIPCHK(hipStreamSynchronize(st));
-    } else {
-        HIPCHK(hipMemcpyAsync(g->state, src, g->state_bytes, hipMemcpyDeviceToDevice, st));
-    }
-    // pending spawns are keyed by (case_counter, reset_count); redraw them for the new state, keyed from a
-    // snapshot of its counters (the next launch's own resets rewrite the state's while its spawn waves run)
-    g->pend_all = PEND_BOTH;
-    const int rk = keysnap(g, st);
-    if (rk) return rk;
-    if (g->devseq) return ctl_set(g->work_count + CN_CTL_ALL, PEND_BOTH, st);
-    return CN_OK;
-}
-
-#ifdef CN_STAMPS
-int cn_debug_stamps_c(unsigned long long *c, unsigned long long *p)
-{
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpyFromSymbol(c, HIP_SYMBOL(cn_stamp_c), sizeof(unsigned long long) * 8192 * 4));
-    HIPCHK(hipMemcpyFromSymbol(p, HIP_SYMBOL(cn_stamp_p), sizeof(unsigned long long) * 8192 * 2));
-    return CN_OK;
-}
-
-// per-workgroup start / end on the device-wide 100 MHz realtime clock; spawn_env's segment stamps
-int cn_debug_stamps_r(unsigned long long *r, unsigned long long *sp)
-{
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpyFromSymbol(r, HIP_SYMBOL(cn_stamp_r), sizeof(unsigned long long) * 8192 * 2));
-    if (sp) HIPCHK(hipMemcpyFromSymbol(sp, HIP_SYMBOL(cn_stamp_s), sizeof(unsigned long long) * 8192 * 16));
-    unsigned long long l3[14];
-    HIPCHK(hipMemcpyFromSymbol(l3, HIP_SYMBOL(cn_lp3_cnt), sizeof(l3)));
-    for (int k = 0; k < 14; ++k) r[8192 * 2 - 14 + k] = l3[k];   // (the last workgroup slots: never a real grid here)
-    return CN_OK;
-}
-
-// per workgroup [8192][4]: HW_REG_XCC_ID, HW_REG_HW_ID, start / end on the XCD's shader clock
-int cn_debug_stamps_x(unsigned long long *x)
-{
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpyFromSymbol(x, HIP_SYMBOL(cn_stamp_x), sizeof(unsigned long long) * 8192 * 4));
-    return CN_OK;
-}
-
-int cn_debug_stamps(unsigned long long *a, unsigned long long *b)
-{
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpyFromSymbol(a, HIP_SYMBOL(cn_stamp_a), sizeof(unsigned long long) * 4096 * CN_NSTAMP));
-    HIPCHK(hipMemcpyFromSymbol(b, HIP_SYMBOL(cn_stamp_b), sizeof(unsigned long long) * 8192 * CN_NSTAMP));
-    return CN_OK;
-}
-#endif
-
-int cn_debug_set_spawn_budget(cn_engine *g, long long cycles)
-{
-    if (!g || cycles < 0) return set_err(CN_EINVAL, "cn_debug_set_spawn_budget: engine and cycles >= 0 required");
-    for (int k = 0; k < g->ngroups; ++k) cn_debug_set_spawn_budget(g->grp[k], cycles);
-    if (!g->ngroups && (g->plan.kd || CN_QUAD_PARK)) g->spawn_budget = cycles;   // (parking paths only)
-    return CN_OK;
-}
-
-int cn_debug_set_seq_chunk(cn_engine *g, int n)
-{
-    if (!g || n < 1) return set_err(CN_EINVAL, "cn_debug_set_seq_chunk: engine and n >= 1 required");
-    for (int k = 0; k < g->ngroups; ++k) cn_debug_set_seq_chunk(g->grp[k], n);   // (mixed engines step per launch)
-    g->seq_chunk = n;
-    return CN_OK;
-}
-
-int cn_debug_spawn_stats(cn_engine *g, uint32_t *out)
-{
-    if (!g || !out) return set_err(CN_EINVAL, "null argument");
-    for (int j = 0; j < 5; ++j) out[j] = 0;
-    if (g->ngroups) {
-        for (int k = 0; k < g->ngroups; ++k) {
-            uint32_t v[5];
-            const int rc = cn_debug_spawn_stats(g->grp[k], v);
-            if (rc) return rc;
-            for (int j = 0; j < 5; ++j) out[j] += v[j];
-        }
-        return CN_OK;
-    }
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(out, g->work_count + 8, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(out + 4, g->work_count + 15, sizeof(uint32_t), hipMemcpyDeviceToHost));
-    return CN_OK;
-}
-
-int cn_lidar_obs(cn_engine *g, void *stream, const uint8_t *reset_mask, int enable, int beams, double max_range,
-                 double robot_radius, float *lidar, float *obs)
-{
-    if (!g) return set_err(CN_EINVAL, "null engine");
-    if (g->ngroups) return set_err(CN_EUNSUPPORTED, "cn_lidar_obs: not on a mixed engine");
-    if (beams < 2 || beams > 4096 || !(max_range > 0) || !lidar || !obs)
-        return set_err(CN_EINVAL, "cn_lidar_obs: beams in [2, 4096], max_range > 0 and buffers required");
-    (void)hipGetLastError();   // a stale error of an earlier call (any library) is not this launch's
-    hipLaunchKernelGGL(cn_lidar_obs_kernel, dim3((unsigned)((g->E + 3) / 4)), dim3(256), 0, (hipStream_t)stream, g->s,
-                       g->E, g->N, 0.5 * g->c.square_width, reset_mask, enable, beams, max_range, robot_radius,
-                       lidar, obs);
-    HIPCHK(hipGetLastError());
-    return CN_OK;
-}
-
-int cn_lidar_scan(cn_engine *g, void *stream, int beams, double max_range, double robot_radius, float *obs)
-{
-    if (!g) return set_err(CN_EINVAL, "null engine");
-    if (g->ngroups) return set_err(CN_EUNSUPPORTED, "cn_lidar_scan: not on a mixed engine");
-    if (beams < 2 || beams > 4096 || !(max_range > 0) || !(max_range <= 1e4) || !obs)
-        return set_err(CN_EINVAL, "cn_lidar_scan: beams in [2, 4096], max_range in (0, 1e4] and obs required");
-    // beam samples every 0.01 m (lidarv2.py:130-133): max_range / 0.01 of them, rounded up
-    const double q = max_range / 0.01;
-    const int npts = fmod(q, 1.0) != 0.0 ? (int)q + 1 : (int)q;
-    if (npts < 2) return set_err(CN_EINVAL, "cn_lidar_scan: max_range below two 0.01 m samples");
-    // envs per workgroup: the G in [1, CN_LIDAR_G] whose G * beams beams fill whole 256-lane rounds best
-    int G = 1;
-    double fill = 0.0;
-    for (int k = 1; k <= CN_LIDAR_G && k <= g->E; ++k) {
-        const int items = k * beams;
-        const double f = (double)items / (double)(((items + 255) / 256) * 256);
-        if (f > fill + 1e-9) { fill = f; G = k; }
-    }
-    (void)hipGetLastError();   // a stale error of an earlier call (any library) is not this launch's
-    hipLaunchKernelGGL(cn_lidar_scan_kernel, dim3((unsigned)((g->E + G - 1) / G)), dim3(256), 0, (hipStream_t)stream,
-                       g->s, g->E, g->N, G, 0.5 * g->c.square_width, beams, npts, max_range, robot_radius, obs);
-    HIPCHK(hipGetLastError());
-    return CN_OK;
-}
-
-int cn_robot_act(cn_engine *g, void *stream, int policy, float *actions)
-{
-    if (!g) return set_err(CN_EINVAL, "null engine");
-    if ((policy != CN_ROBOT_ORCA && policy != CN_ROBOT_SOCIAL_FORCE) || !actions)
-        return set_err(CN_EINVAL, "cn_robot_act: policy CN_ROBOT_ORCA / CN_ROBOT_SOCIAL_FORCE and actions required");
-    if (g->ngroups) return set_err(CN_EUNSUPPORTED, "cn_robot_act: not on a mixed engine");
-    if (g->c.kinematics != CN_HOLONOMIC)
-        return set_err(CN_EUNSUPPORTED, "cn_robot_act: the controllers return ActionXY (holonomic engines only)");
-    const cn_config &c = g->c;
-    const hipStream_t st = (hipStream_t)stream;
-    (void)hipGetLastError();   // a stale error of an earlier call (any library) is not this launch's
-    if (policy == CN_ROBOT_SOCIAL_FORCE)
-        hipLaunchKernelGGL(cn_robot_sf_kernel, dim3((unsigned)((g->E + 63) / 64)), dim3(64), 0, st, g->s, g->E, g->N,
-                           c.sf_A, c.sf_B, c.sf_KI, c.time_step, actions);
-    else if (g->N + 1 > 10)
-        hipLaunchKernelGGL(cn_robot_orca_kd_kernel, dim3((unsigned)((g->E + 15) / 16)), dim3(64), orca_kd_lds(g->N + 1),
-                           st, g->s, g->E, g->N, c.orca_safety_space, (float)c.orca_neighbor_dist,
-                           (float)c.orca_time_horizon, (float)c.time_step, actions);
-    else
-        hipLaunchKernelGGL(cn_robot_orca_kernel, dim3((unsigned)((g->E + 15) / 16)), dim3(64), 0, st, g->s, g->E, g->N,
-                           c.orca_safety_space, (float)c.orca_neighbor_dist, (float)c.orca_time_horizon,
-                           (float)c.time_step, actions);
-    HIPCHK(hipGetLastError());
-    return CN_OK;
-}
-
-// cn_robot_act + cn_step for t = 0..T-1 with every step recorded at row t. Fused (the ROBOT kernels: up to seq_chunk
-// steps per launch, the controller inside the step workgroups) where cn_step_seq's multi-step launches apply and the
-// controller fits the step workgroup; launch pairs otherwise, the first step after cn_reset / cn_set_state included.
-int cn_rollout(cn_engine *g, void *stream, int policy, int T, const cn_rollout_out *out, int32_t *num_launches)
-{
-    if (num_launches) *num_launches = 0;
-    if (!g) return set_err(CN_EINVAL, "null engine");
-    if ((policy != CN_ROBOT_ORCA && policy != CN_ROBOT_SOCIAL_FORCE) || T < 0 || !out || !out->actions ||
-        !out->robot_node || !out->temporal_edges || !out->spatial_edges)
-        return set_err(CN_EINVAL, "cn_rollout: policy CN_ROBOT_ORCA / CN_ROBOT_SOCIAL_FORCE, T >= 0, out with actions "
-                                  "and the observation buffers required");
-    if (g->ngroups) return set_err(CN_EUNSUPPORTED, "cn_rollout: not on a mixed engine");
-    if (g->c.kinematics != CN_HOLONOMIC)
-        return set_err(CN_EUNSUPPORTED, "cn_rollout: the controllers return ActionXY (holonomic engines only)");
-    const int64_t E = g->E, N = g->N;
-    const bool every = (out->flags & CN_ROLLOUT_OBS_EVERY_STEP) != 0;
-    // the controller fits the step workgroup: social force (a lane per env) always, ORCA on its quad path
-    const bool fits = policy == CN_ROBOT_SOCIAL_FORCE || g->N + 1 <= 10;
-    const bool fusable = fits && g->seq_chunk > 1 && !g->rows && !g->devseq && !g->plan.kd;
-    const int64_t rollout = (int64_t)policy | ((int64_t)(out->flags & CN_ROLLOUT_OBS_EVERY_STEP) << 8);
-    int nl = 0;
-    for (int t = 0; t < T;) {
-        const int64_t ro = every ? t : 0;   // the observation's row
-        float *const act = out->actions + t * E * 2;
-        float *const rn = out->robot_node + ro * E * 7, *const te = out->temporal_edges + ro * E * 2;
-        float *const se = out->spatial_edges + ro * E * N * 2;
-        float *const rw = out->reward ? out->reward + t * E : nullptr;
-        uint8_t *const dn = out->done ? out->done + t * E : nullptr;
-        int8_t *const ev = out->event ? out->event + t * E : nullptr;
-        float *const inf = out->info ? out->info + t * E * CN_INFO_K : nullptr;
-        double *const epr = out->ep_return ? out->ep_return + t * E : nullptr;
-        int32_t *const epl = out->ep_len ? out->ep_len + t * E : nullptr;
-        int n = 1, rc;
-        if (fusable && !g->pend_all) {
-            n = T - t < g->seq_chunk ? T - t : g->seq_chunk;
-            // (a launch never straddles the end of cn_profile's window: cn_step_seq)
-            if (g->prof_on && g->prof_n < g->prof_cap && n > g->prof_cap - g->prof_n) n = g->prof_cap - g->prof_n;
-            rc = step_launch(g, stream, act, n, 2 * E, rn, te, se, rw, dn, ev, inf, epr, epl, rollout);
-            nl += 1;
-        } else {
-            rc = cn_robot_act(g, stream, policy, act);
-            if (rc) return rc;
-            rc = cn_step(g, stream, act, rn, te, se, rw, dn, ev, inf, epr, epl);
-            nl += 2;
-        }
-        if (rc) return rc;
-        t += n;
-        if (num_launches) *num_launches = nl;
-    }
-    return CN_OK;
-}
-
-int cn_debug_disc_quad(void *stream, int64_t n, int mode, const double *px, const double *py, const double *r,
-                       const double *qx, const double *qy, int32_t *out)
-{
-    if (n <= 0 || !px || !py || !r || !qx || !qy || !out) return set_err(CN_EINVAL, "cn_debug_disc_quad: n > 0 and buffers required");
-    HIPCHK(circ_table_init());
-    (void)hipGetLastError();   // a stale error of an earlier call (any library) is not this launch's
-    hipLaunchKernelGGL(cn_disc_quad_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, (hipStream_t)stream, n, mode,
-                       px, py, r, qx, qy, out);
-    HIPCHK(hipGetLastError());
-    return CN_OK;
-}
-
-int cn_debug_copy64(void *stream, int64_t n, int seg, const double *src, double *dst)
-{
-    if (n <= 0 || seg < 1 || seg > 64 || !src || !dst) return set_err(CN_EINVAL, "cn_debug_copy64: n > 0, 1 <= seg <= 64");
-    (void)hipGetLastError();   // a stale error of an earlier call (any library) is not this launch's
-    hipLaunchKernelGGL(cn_copy64_kernel, dim3((unsigned)((n + seg - 1) / seg)), dim3(64), 0, (hipStream_t)stream, n, seg,
-                       src, dst);
-    HIPCHK(hipGetLastError());
-    return CN_OK;
-}
-
-int cn_debug_orca(void *stream, int64_t n, int A, const float *agents, const float *self, float neighbor_dist,
-                  float time_horizon, float time_step, float *out)
-{
-    if (n <= 0 || !agents || !self || !out) return set_err(CN_EINVAL, "cn_debug_orca: n > 0 and buffers required");
-    if (A < 1 || A > 10) return set_err(CN_EUNSUPPORTED, "cn_debug_orca: 1 <= A <= 10 (the quad path)");
-    (void)hipGetLastError();   // a stale error of an earlier call (any library) is not this launch's
-    hipLaunchKernelGGL(cn_orca_kernel, dim3((unsigned)((n + 15) / 16)), dim3(64), 0, (hipStream_t)stream, n, A,
-                       agents, self, neighbor_dist, time_horizon, time_step, out);
-    HIPCHK(hipGetLastError());
-    return CN_OK;
-}
-
-int cn_orca_predict_kd(void *stream, int64_t n, int A, const float *agents, const float *self, float neighbor_dist,
-                       float time_horizon, float time_step, uint8_t *perm, float *out)
-{
-    if (n <= 0 || !agents || !self || !out) return set_err(CN_EINVAL, "cn_orca_predict_kd: n > 0 and buffers required");
-    if (A < 1 || A > CN_ORCA_MAXA) return set_err(CN_EUNSUPPORTED, "cn_orca_predict_kd: 1 <= A <= 64");
-    (void)hipGetLastError();   // a stale error of an earlier call (any library) is not this launch's
-    hipLaunchKernelGGL(cn_orca_kd_kernel, dim3((unsigned)((n + 15) / 16)), dim3(64), orca_kd_lds(A), (hipStream_t)stream,
-                       n, A, agents, self, neighbor_dist, time_horizon, time_step, perm, out);
-    HIPCHK(hipGetLastError());
-    return CN_OK;
-}
-
-int cn_orca_predict(void *stream, int64_t n, int A, const float *agents, const float *self, float neighbor_dist,
-                    float time_horizon, float time_step, float *out)
-{
-    if (A > 10)   // a fresh simulator per call: identity KdTree order
-        return cn_orca_predict_kd(stream, n, A, agents, self, neighbor_dist, time_horizon, time_step, nullptr, out);
-    return cn_debug_orca(stream, n, A, agents, self, neighbor_dist, time_horizon, time_step, out);
-}
-
-int cn_social_force_predict(void *stream, int64_t n, int M, const double *self, const double *others, double A,
-                            double B, double KI, double time_step, double *out)
-{
-    if (n <= 0 || M < 0 || M > 64 || !self || (M && !others) || !out)
-        return set_err(CN_EINVAL, "cn_social_force_predict: n > 0, 0 <= M <= 64 and buffers required");
-    (void)hipGetLastError();   // a stale error of an earlier call (any library) is not this launch's
-    hipLaunchKernelGGL(cn_sf_predict_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, (hipStream_t)stream, n, M,
-                       self, others, A, B, KI, time_step, out);
-    HIPCHK(hipGetLastError());
-    return CN_OK;
-}
-
-int cn_edge_features(void *stream, int64_t E, int N, const float *robot_node, const float *temporal_edges,
-                     const float *spatial_edges, const float *Wt, const float *bt, const float *Ws, const float *bs,
-                     const float *Wr, const float *br, const float *Wn, const float *bn, float *temporal_embed,
-                     float *spatial_embed, float *node_embed)
-{
-    if (E <= 0 || N <= 0) return set_err(CN_EINVAL, "E, N must be > 0");
-    const int64_t threads = E * (N + 2) * 16;
-    const int64_t blocks = (threads + 255) / 256;
-    (void)hipGetLastError();   // a stale error of an earlier call (any library) is not this launch's
-    hipLaunchKernelGGL(cn_edge_features_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, E, N,
-                       robot_node, temporal_edges, spatial_edges, Wt, bt, Ws, bs, Wr, br, Wn, bn, temporal_embed,
-                       spatial_embed, node_embed);
-    HIPCHK(hipGetLastError());
-    return CN_OK;
-}
-
-}  // extern "C"
+#include "engine/edge_features.h"  // cn_edge_features_kernel
+#include "engine/lidar.h"          // cn_lidar_obs_kernel, cn_lidar_scan_kernel
+#include "engine/aux_kernels.h"    // debug / predictor kernels, cn_robot_act's kernels, ctl / key-snapshot kernels
+#include "engine/host_engine.h"    // struct cn_engine, error text, the table of cn_step_kernel's instantiations
+#include "engine/host_api.h"       // extern "C": the functions of include/crowdnav.h

@@ -1,0 +1,359 @@
+// aux_kernels.h -- the small stand-alone kernels: the debug / predictor kernels that expose the step kernel's
+// device functions on caller-given inputs (cn_disc_quad, cn_copy64, cn_orca, cn_orca_kd with RVO2's sequential
+// KdTree, cn_sf_predict), cn_robot_act's three kernels, and the two stream-ordered helpers of the host API
+// (cn_ctl_set_kernel, cn_keysnap_kernel). Part of cn_engine.hip's translation unit: included there after the
+// device core, whose geometry, ORCA and scripted-robot functions these kernels call.
+#pragma once
+
+__global__ void __launch_bounds__(64) cn_disc_quad_kernel(int64_t n, int mode, const double *px, const double *py,
+                                                          const double *r, const double *qx, const double *qy,
+                                                          int32_t *out)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (mode == 2)   // the robot's norm-zone penalty predicate: qx[i] = {vx, f32, ...}, qy[i] = {vy, lhs, ...}
+        out[i] = robot_norm_zone_violation(px[i], py[i], qx[4 * i], qy[4 * i], r[i], qx[4 * i + 1] != 0.0,
+                                           (int)qy[4 * i + 1]);
+    else
+        out[i] = mode ? disc_quad_sat(px[i], py[i], r[i], qx + 4 * i, qy + 4 * i)
+                      : disc_quad_intersect(px[i], py[i], r[i], qx + 4 * i, qy + 4 * i);
+}
+
+// cn_debug_copy64: one wave per segment of `seg` doubles
+__global__ void __launch_bounds__(64) cn_copy64_kernel(int64_t n, int seg, const double *__restrict__ src,
+                                                       double *__restrict__ dst)
+{
+    const int64_t k = (int64_t)blockIdx.x * seg + threadIdx.x;
+    if ((int)threadIdx.x < seg && k < n) dst[k] = src[k];
+}
+
+// cn_debug_orca: one quad per simulator (16 per 64-lane workgroup), the step kernel's quad-path functions
+__global__ void __launch_bounds__(64) cn_orca_kernel(int64_t n, int A, const float *__restrict__ ag,
+                                                     const float *__restrict__ self, float nd, float th, float ts,
+                                                     float *__restrict__ out)
+{
+    __shared__ float4 Ls[16][9];
+    const int q = threadIdx.x >> 2, sq = threadIdx.x & 3;
+    const int64_t i = (int64_t)blockIdx.x * 16 + q;
+    const bool act = i < n;
+    const float *a = ag + (act ? i : 0) * A * 5;
+    const int M = A - 1;
+    int cnt = 0;
+    if (act)
+        cnt = orca_lines_quad(
+            [&](int k, float &x, float &y, float &vx, float &vy, float &r) {
+                const float *o = a + (k + 1) * 5;
+                x = o[0]; y = o[1]; vx = o[2]; vy = o[3]; r = o[4];
+            },
+            M, sq, a[0], a[1], a[2], a[3], a[4], nd * nd, fdiv(1.0f, th), fdiv(1.0f, ts), Ls[q]);
+    wsync();
+    if (act) {
+        const float vmax = self[3 * i], ox = self[3 * i + 1], oy = self[3 * i + 2];
+        float rx, ry;
+        float4 R[3];
+#pragma unroll
+        for (int u = 0; u < 3; ++u) R[u] = sq + 4 * u < cnt ? Ls[q][sq + 4 * u] : make_float4(0.f, 0.f, 0.f, 0.f);
+        const int fail_at = lp2_r<3>(R, cnt, vmax, ox, oy, sq, rx, ry);
+        if (fail_at < cnt) lp3_r<3>(R, Ls[q], cnt, fail_at, vmax, sq, rx, ry);
+        if (sq == 0) {
+            out[4 * i] = rx; out[4 * i + 1] = ry; out[4 * i + 2] = (float)fail_at; out[4 * i + 3] = (float)cnt;
+        }
+    }
+}
+
+// cn_orca_predict_kd: ORCA.predict of simulators of any size up to CN_ORCA_MAXA agents, with RVO2's KdTree
+// (MAX_LEAF_SIZE 10) and its persisted agents_ order. One quad per simulator (16 per 64-lane workgroup):
+// lane 0 of the quad builds the tree (buildAgentTreeRecursive, which re-permutes agents_ in place) and runs
+// the query (queryAgentTreeRecursive + insertAgentNeighbor with maxNeighbors = A - 1), both sequential as
+// in RVO2 -- the plugin serves one predict per agent per env step, off the batched step path, which has its
+// own ballot-partitioned walk; then the quad builds the ORCA lines in neighbour order and runs the quad
+// linear programs of the step kernel. Oracle: cpu_ref.c:kd_build / kd_query / rvo2_agent0.
+#define CN_ORCA_MAXA 64
+// 20 B per node: ranges and child indices fit bytes (A <= 64 agents, < 2A nodes); the build / query stacks
+// below are bytes too -- the per-lane private arrays were 5.7 KB of scratch per lane with ints, 3.3 KB now
+struct KdNodeS { uint8_t begin, end, left, right; float minX, maxX, minY, maxY; };
+
+__device__ __forceinline__ float kd_bdist(const KdNodeS &t, float x, float y)
+{
+    const float a = (0.0f < t.minX - x) ? t.minX - x : 0.0f, b = (0.0f < x - t.maxX) ? x - t.maxX : 0.0f;
+    const float cc = (0.0f < t.minY - y) ? t.minY - y : 0.0f, d = (0.0f < y - t.maxY) ? y - t.maxY : 0.0f;
+    return a * a + b * b + cc * cc + d * d;
+}
+
+// lane-sequential KdTree build + query over X / Y [A] (LDS), perm [A] (LDS, updated in place); writes the
+// neighbours of agent 0 in insertion-sorted order to nb [A - 1] (agent ids) and returns their count
+__device__ int kd_neighbors_seq(int A, const float *X, const float *Y, uint8_t *perm, float rangeSq, uint8_t *nb)
+{
+    KdNodeS T[2 * CN_ORCA_MAXA];
+    uint8_t stk[CN_ORCA_MAXA + 2][3];
+    int sp = 0;
+    stk[sp][0] = 0; stk[sp][1] = (uint8_t)A; stk[sp][2] = 0; ++sp;
+    while (sp > 0) {   // any order of the recursive calls gives the same tree: children own disjoint ranges
+        --sp;
+        const int begin = stk[sp][0], end = stk[sp][1], node = stk[sp][2];
+        KdNodeS t;
+        t.begin = (uint8_t)begin; t.end = (uint8_t)end; t.left = t.right = 0;
+        t.minX = t.maxX = X[perm[begin]];
+        t.minY = t.maxY = Y[perm[begin]];
+        for (int i = begin + 1; i < end; ++i) {
+            const float x = X[perm[i]], y = Y[perm[i]];
+            t.maxX = t.maxX < x ? x : t.maxX; t.minX = x < t.minX ? x : t.minX;
+            t.maxY = t.maxY < y ? y : t.maxY; t.minY = y < t.minY ? y : t.minY;
+        }
+        if (end - begin > 10) {
+            const bool vert = t.maxX - t.minX > t.maxY - t.minY;
+            const float split = vert ? 0.5f * (t.maxX + t.minX) : 0.5f * (t.maxY + t.minY);
+            int left = begin, right = end;
+            while (left < right) {
+                while (left < right && (vert ? X[perm[left]] : Y[perm[left]]) < split) ++left;
+                while (right > left && (vert ? X[perm[right - 1]] : Y[perm[right - 1]]) >= split) --right;
+                if (left < right) {
+                    const uint8_t s = perm[left]; perm[left] = perm[right - 1]; perm[right - 1] = s;
+                    ++left; --right;
+                }
+            }
+            if (left == begin) { ++left; ++right; }
+            t.left = (uint8_t)(node + 1);
+            t.right = (uint8_t)(node + 2 * (left - begin));
+            stk[sp][0] = (uint8_t)left; stk[sp][1] = (uint8_t)end; stk[sp][2] = t.right; ++sp;
+            stk[sp][0] = (uint8_t)begin; stk[sp][1] = (uint8_t)left; stk[sp][2] = t.left; ++sp;
+        }
+        T[node] = t;
+    }
+    // query: a node popped with distance d is walked only if d < rangeSq at that moment (the recursion tests
+    // the nearer child at once and the farther one after the nearer subtree; ties visit the right first)
+    const int maxN = A - 1;
+    float nd[CN_ORCA_MAXA];
+    int cnt = 0;
+    float dst[CN_ORCA_MAXA + 2];
+    uint8_t nst[CN_ORCA_MAXA + 2];
+    sp = 0;
+    nst[0] = 0; dst[0] = -1.0f; sp = 1;
+    const float x0 = X[0], y0 = Y[0];
+    while (sp > 0) {
+        --sp;
+        const int node = nst[sp];
+        if (!(dst[sp] < rangeSq)) continue;
+        const KdNodeS &t = T[node];
+        if (t.end - t.begin <= 10) {
+            for (int i = t.begin; i < t.end; ++i) {   // Agent::insertAgentNeighbor
+                const int a = perm[i];
+                if (a == 0) continue;
+                const float dx = x0 - X[a], dy = y0 - Y[a];
+                const float distSq = dx * dx + dy * dy;
+                if (distSq < rangeSq) {
+                    if (cnt < maxN) { nd[cnt] = distSq; nb[cnt] = (uint8_t)a; ++cnt; }
+                    int k = cnt - 1;
+                    while (k != 0 && distSq < nd[k - 1]) { nd[k] = nd[k - 1]; nb[k] = nb[k - 1]; --k; }
+                    nd[k] = distSq; nb[k] = (uint8_t)a;
+                    if (cnt == maxN) rangeSq = nd[cnt - 1];
+                }
+            }
+            continue;
+        }
+        const float dl = kd_bdist(T[t.left], x0, y0), dr = kd_bdist(T[t.right], x0, y0);
+        if (dl < dr) { nst[sp] = t.right; dst[sp] = dr; nst[sp + 1] = t.left; dst[sp + 1] = dl; }
+        else { nst[sp] = t.left; dst[sp] = dl; nst[sp + 1] = t.right; dst[sp + 1] = dr; }
+        sp += 2;
+    }
+    return cnt;
+}
+
+// LDS of one cn_orca_kd_kernel workgroup, sized by the simulators' agent count A (dynamic): 16 quads' lines
+// and projected lines [A - 1] float4 each, positions [A] float x 2, agents_ order and neighbours [A] bytes, counts.
+// (Sized for CN_ORCA_MAXA it was 42.5 KB, 3 one-wave workgroups per CU; at A = 26, 17 KB: 9.)
+__host__ __device__ inline int orca_kd_lds(int A)
+{
+    return 16 * (2 * 16 * (A - 1) + 2 * 4 * A) + ((2 * 16 * A + 15) & ~15) + 16 * 4;
+}
+
+__global__ void __launch_bounds__(64) cn_orca_kd_kernel(int64_t n, int A, const float *__restrict__ ag,
+                                                        const float *__restrict__ self, float nd, float th, float ts,
+                                                        uint8_t *__restrict__ perm_io, float *__restrict__ out)
+{
+    extern __shared__ __attribute__((aligned(16))) char kd_smem[];
+    const int q = threadIdx.x >> 2, sq = threadIdx.x & 3;
+    float4 *Lq = (float4 *)kd_smem + q * (A - 1);                 // [16][A - 1]
+    float4 *Pq = (float4 *)kd_smem + 16 * (A - 1) + q * (A - 1);  // [16][A - 1]
+    float *Xq = (float *)(kd_smem + 16 * 2 * 16 * (A - 1)) + q * A;
+    float *Yq = (float *)(kd_smem + 16 * 2 * 16 * (A - 1)) + 16 * A + q * A;
+    uint8_t *Pmq = (uint8_t *)(kd_smem + 16 * (2 * 16 * (A - 1) + 2 * 4 * A)) + q * A;
+    uint8_t *Nbq = (uint8_t *)(kd_smem + 16 * (2 * 16 * (A - 1) + 2 * 4 * A)) + 16 * A + q * A;
+    int *Cn = (int *)(kd_smem + orca_kd_lds(A) - 16 * 4);
+    const int64_t i = (int64_t)blockIdx.x * 16 + q;
+    const bool act = i < n;
+    const float *a = ag + (act ? i : 0) * A * 5;
+    if (act)
+        for (int k = sq; k < A; k += 4) {
+            Xq[k] = a[k * 5]; Yq[k] = a[k * 5 + 1];
+            Pmq[k] = perm_io ? perm_io[i * A + k] : (uint8_t)k;
+        }
+    wsync();
+    if (act && sq == 0) Cn[q] = A > 1 ? kd_neighbors_seq(A, Xq, Yq, Pmq, nd * nd, Nbq) : 0;
+    wsync();
+    if (act) {
+        const int cnt = Cn[q];
+        const float invTH = fdiv(1.0f, th), invTS = fdiv(1.0f, ts);
+        for (int k = sq; k < cnt; k += 4) {
+            const float *o = a + Nbq[k] * 5;
+            Lq[k] = orca_line(a[0], a[1], a[2], a[3], a[4], o[0], o[1], o[2], o[3], o[4], invTH, invTS);
+        }
+        if (perm_io)
+            for (int k = sq; k < A; k += 4) perm_io[i * A + k] = Pmq[k];
+    }
+    wsync();
+    if (act) {
+        const int cnt = Cn[q];
+        const float vmax = self[3 * i], ox = self[3 * i + 1], oy = self[3 * i + 2];
+        float rx, ry;
+        const int fail_at = lp2_q<uint64_t>(Lq, cnt, vmax, ox, oy, sq, rx, ry);
+        if (fail_at < cnt) lp3_q<uint64_t>(Lq, Pq, cnt, fail_at, vmax, sq, rx, ry);
+        if (sq == 0) {
+            out[4 * i] = rx; out[4 * i + 1] = ry; out[4 * i + 2] = (float)fail_at; out[4 * i + 3] = (float)cnt;
+        }
+    }
+}
+
+// cn_social_force_predict: SOCIAL_FORCE.predict (social_force.py:11-66) for n agents, one lane each, f64 in
+// the reference's operation order (the step kernel's phase 2 on caller-given states)
+__global__ void __launch_bounds__(64) cn_sf_predict_kernel(int64_t n, int M, const double *__restrict__ self,
+                                                           const double *__restrict__ others, double A, double B,
+                                                           double KI, double dt, double *__restrict__ out)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double *s = self + 9 * i;   // px, py, vx, vy, radius, gx, gy, v_pref, theta
+    const double px = s[0], py = s[1], vx0 = s[2], vy0 = s[3], rad = s[4], vpref = s[7];
+    const double gdx = s[5] - px, gdy = s[6] - py;
+    const double dg = dsqrt(gdx * gdx + gdy * gdy);
+    const double dvx = ddiv(gdx, dg) * vpref, dvy = ddiv(gdy, dg) * vpref;
+    const double cdx = KI * (dvx - vx0), cdy = KI * (dvy - vy0);
+    double ix = 0.0, iy = 0.0;
+    for (int k = 0; k < M; ++k) {
+        const double *o = others + (i * M + k) * 5;   // px, py, vx, vy, radius
+        const double ddx = px - o[0], ddy = py - o[1];
+        const double d = dsqrt(ddx * ddx + ddy * ddy);
+        const double ex = exp(ddiv(rad + o[4] - d, B));
+        ix += A * ex * ddiv(ddx, d);
+        iy += A * ex * ddiv(ddy, d);
+    }
+    const double nx = vx0 + (cdx + ix) * dt, ny = vy0 + (cdy + iy) * dt;
+    const double nn = np_norm2(nx, ny);
+    if (nn > vpref) { out[2 * i] = ddiv(nx, nn) * vpref; out[2 * i + 1] = ddiv(ny, nn) * vpref; }
+    else { out[2 * i] = nx; out[2 * i + 1] = ny; }
+}
+
+// ------------------------------------------------------------------------------------------------
+// cn_robot_act: the scripted robot (ORCA / social force) on the engine's CURRENT state, read straight from
+// the blob: policy_factory[name](config).predict(JointState(robot FullState, [ObservableState(b_px, b_py,
+// b_vx, b_vy, b_r) of the N humans in index order])) of a fresh policy object per env, rounded to float32.
+// Pure functions of the state (nothing held between calls), one launch each.
+// ------------------------------------------------------------------------------------------------
+// (robot_sim_agent, robot_pref_velocity, robot_orca_lines / robot_orca_solve and robot_sf_velocity are defined above
+// cn_step_kernel, whose rollout variant computes the same actions inside its multi-step launches)
+// ORCA, N + 1 <= 10 agents: cn_orca_kernel's quad path (one quad per env, 16 envs per 64-lane workgroup).
+// `act` depends on the quad alone, so a quad is whole or absent and its control flow uniform (DESIGN.md §4,
+// "Cross-lane reads"): the quad's 4 lanes read the same state words.
+__global__ void __launch_bounds__(64) cn_robot_orca_kernel(cn_state_ptrs S, int E, int N, double safety, float nd,
+                                                           float th, float ts, float *__restrict__ actions)
+{
+    __shared__ float4 Ls[16][9];
+    const int q = threadIdx.x >> 2, sq = threadIdx.x & 3;
+    const int64_t e = (int64_t)blockIdx.x * 16 + q;
+    const bool act = e < E;
+    int cnt = 0;
+    if (act) cnt = robot_orca_lines(S, safety, e, N, sq, nd, th, ts, Ls[q]);
+    wsync();
+    if (act) {
+        float rx, ry;
+        robot_orca_solve(S, e, cnt, sq, Ls[q], rx, ry);
+        if (sq == 0) { actions[2 * e] = rx; actions[2 * e + 1] = ry; }
+    }
+}
+
+// ORCA, N + 1 > 10 agents: cn_orca_kd_kernel's path with a fresh simulator's identity agent order (LDS sized by
+// A = N + 1: orca_kd_lds)
+__global__ void __launch_bounds__(64) cn_robot_orca_kd_kernel(cn_state_ptrs S, int E, int N, double safety, float nd,
+                                                              float th, float ts, float *__restrict__ actions)
+{
+    extern __shared__ __attribute__((aligned(16))) char kd_smem[];
+    const int A = N + 1;
+    const int q = threadIdx.x >> 2, sq = threadIdx.x & 3;
+    float4 *Lq = (float4 *)kd_smem + q * (A - 1);                 // [16][A - 1]
+    float4 *Pq = (float4 *)kd_smem + 16 * (A - 1) + q * (A - 1);  // [16][A - 1]
+    float *Xq = (float *)(kd_smem + 16 * 2 * 16 * (A - 1)) + q * A;
+    float *Yq = (float *)(kd_smem + 16 * 2 * 16 * (A - 1)) + 16 * A + q * A;
+    uint8_t *Pmq = (uint8_t *)(kd_smem + 16 * (2 * 16 * (A - 1) + 2 * 4 * A)) + q * A;
+    uint8_t *Nbq = (uint8_t *)(kd_smem + 16 * (2 * 16 * (A - 1) + 2 * 4 * A)) + 16 * A + q * A;
+    int *Cn = (int *)(kd_smem + orca_kd_lds(A) - 16 * 4);
+    const int64_t e = (int64_t)blockIdx.x * 16 + q;
+    const bool act = e < E;
+    if (act)
+        for (int k = sq; k < A; k += 4) {
+            float x, y, vx, vy, r;
+            robot_sim_agent(S, safety, e, N, k, x, y, vx, vy, r);
+            Xq[k] = x; Yq[k] = y;
+            Pmq[k] = (uint8_t)k;
+        }
+    wsync();
+    if (act && sq == 0) Cn[q] = kd_neighbors_seq(A, Xq, Yq, Pmq, nd * nd, Nbq);
+    wsync();
+    if (act) {
+        const int cnt = Cn[q];
+        const float invTH = fdiv(1.0f, th), invTS = fdiv(1.0f, ts);
+        float X0, Y0, VX0, VY0, R0;
+        robot_sim_agent(S, safety, e, N, 0, X0, Y0, VX0, VY0, R0);
+        for (int k = sq; k < cnt; k += 4) {
+            float x, y, vx, vy, r;
+            robot_sim_agent(S, safety, e, N, Nbq[k], x, y, vx, vy, r);
+            Lq[k] = orca_line(X0, Y0, VX0, VY0, R0, x, y, vx, vy, r, invTH, invTS);
+        }
+    }
+    wsync();
+    if (act) {
+        const int cnt = Cn[q];
+        float vmax, ox, oy, rx, ry;
+        robot_pref_velocity(S, e, vmax, ox, oy);
+        const int fail_at = lp2_q<uint64_t>(Lq, cnt, vmax, ox, oy, sq, rx, ry);
+        if (fail_at < cnt) lp3_q<uint64_t>(Lq, Pq, cnt, fail_at, vmax, sq, rx, ry);
+        if (sq == 0) { actions[2 * e] = rx; actions[2 * e + 1] = ry; }
+    }
+}
+
+// Social force: cn_sf_predict_kernel's float64 arithmetic on the robot's FullState and the N belief humans,
+// one lane per env; the ActionXY rounded to float32
+__global__ void __launch_bounds__(64) cn_robot_sf_kernel(cn_state_ptrs S, int E, int N, double A, double B, double KI,
+                                                         double dt, float *__restrict__ actions)
+{
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= E) return;
+    double nx, ny, nn, vpref;
+    robot_sf_velocity(S, e, N, A, B, KI, dt, nx, ny, nn, vpref);
+    if (nn > vpref) { actions[2 * e] = (float)(ddiv(nx, nn) * vpref); actions[2 * e + 1] = (float)(ddiv(ny, nn) * vpref); }
+    else { actions[2 * e] = (float)nx; actions[2 * e + 1] = (float)ny; }
+}
+
+// One control word of the engine set from the stream (graph mode's draw-all flag after cn_reset /
+// cn_set_state). A kernel, not hipMemsetAsync: captured into a hipGraph it is a kernel node, and this
+// runtime replays memset nodes with stale bytes (cn_graph_node_counts).
+__global__ void cn_ctl_set_kernel(uint32_t *w, uint32_t v)
+{
+    if (threadIdx.x == 0) *w = v;
+}
+
+// Key snapshot for a PEND_BOTH launch (after cn_set_state, and the quad path's cn_reset): every env's
+// {e, reset_count, case_counter lo, hi} into the spawn list the next step launch reads (kr = (t + 2) % 3 for
+// launch t: the host's sequence number, or graph mode's device word). That launch's spawn waves key both of an
+// env's pending spawns from this entry, not from the state its own step workgroups rewrite when a terminal env
+// resets inline (crowd_sim_dict.py:147-164: the seed of the k-th reset is offset + case_counter + thisSeed).
+__global__ void cn_keysnap_kernel(const int32_t *__restrict__ reset_count, const int64_t *__restrict__ case_counter,
+                                  uint32_t *plist_base, const uint32_t *ctl, int host_kr, int E)
+{
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= E) return;
+    const int64_t kr = host_kr >= 0 ? host_kr : (int64_t)((ctl[CN_CTL_NSTEP] + 2u) % 3u);
+    uint32_t *q = plist_base + kr * 4 * ((int64_t)E + 64) + 4 * (int64_t)e;
+    const uint64_t cc = (uint64_t)case_counter[e];
+    const uint4 v = make_uint4((uint32_t)e, (uint32_t)reset_count[e], (uint32_t)cc, (uint32_t)(cc >> 32));
+    *(uint4 *)q = v;
+}

@@ -1,6 +1,6 @@
 """Device-resident batched CrowdSimDict engine (torch tensors in, torch tensors out).
 
-Thin host wrapper over the C ABI (include/crowdnav.h, crowdnav_dsrnn_amd/csrc/cn_engine.hip): it
+Thin host wrapper over the C ABI (include/crowdnav.h, crowdnav_dsrnn_amd/csrc/engine/host_api.h): it
 owns the output buffers (torch, on the engine's device) and passes `data_ptr()`s and the current
 torch stream to `cn_reset` / `cn_step`. No compute happens here and there is no CPU fallback.
 """

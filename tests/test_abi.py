@@ -182,6 +182,30 @@ def test_make_cn_config_defaults_follow_make_env():
     assert abs(c.robot_fov - 2 * 3.141592653589793) < 1e-12
 
 
+def test_build_deps_cover_every_included_file():
+    """build.DEPS (what CN_SRC_HASH is taken over) holds every file the compiled sources reach through
+    `#include "..."`, followed recursively: a header left out would let a stale library pass for a fresh one.
+    The list is SOURCES first, then the headers sorted, without duplicates (a deterministic hash)."""
+    from crowdnav_dsrnn_amd import build
+
+    reached, todo = set(), list(build.SOURCES)
+    while todo:
+        f = os.path.realpath(todo.pop())
+        if f in reached:
+            continue
+        reached.add(f)
+        assert os.path.exists(f), f
+        for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', open(f).read(), re.M):
+            todo.append(os.path.join(os.path.dirname(f), inc))
+    deps = [os.path.realpath(d) for d in build.DEPS]
+    assert any(os.sep + "engine" + os.sep in f for f in reached)   # (the walk went into csrc/engine/)
+    assert reached <= set(deps), sorted(reached - set(deps))
+    assert len(set(deps)) == len(deps)
+    n = len(build.SOURCES)
+    assert build.DEPS[:n] == build.SOURCES
+    assert build.DEPS[n:] == sorted(build.DEPS[n:])
+
+
 def test_library_built_from_sources_on_disk(L):
     """The loaded library embeds the sha256 of the sources it was built from (build.py) and it equals
     the hash of the committed sources: GPU evidence produced with it belongs to this tree."""

@@ -428,3 +428,47 @@ def test_graph_mode_replays_equal_eager_with_spawns_drawn_ahead(shape):
         eng.close()
     assert out[1][1] <= out[0][1] + 2, (out[0][1], out[1][1])
     np.testing.assert_array_equal(out[0][0], out[1][0])
+
+
+@pytest.mark.gpu
+def test_graph_mode_at_most_humans_has_its_lds():
+    """Graph mode on the kd-tree path at the engine's maximum of 31 humans (square_crossing, holonomic, 8 envs),
+    where the step kernel's LDS plan (~76 KB) exceeds the 64 KiB a kernel may use without its dynamic-LDS limit
+    raised: cn_create raises it for EVERY instantiation of the step kernel (one table, csrc/engine/host_engine.h),
+    the graph-mode ones included. One eager warm-up step, then a HIP graph of 4 cn_step launches (a single chain
+    on one stream) replayed 3 times equals 13 eager steps from the same reset and actions, state blobs bit for
+    bit. The smallest shape that selects a graph-mode kernel with a plan over 64 KiB."""
+    from crowdnav_dsrnn_amd.engine import CrowdNavEngine
+
+    E, T, R = 8, 4, 3
+    c = clone_config(Config())
+    c.humans.policy = "orca"
+    c.sim.human_num = 31
+    c.sim.train_val_sim = c.sim.test_sim = ["square_crossing"]
+    c.action_space.kinematics = "holonomic"
+    cfg = make_cn_config(c, num_envs=E, nenv=E, phase="train")
+    g = torch.Generator(device="cuda:0").manual_seed(7)
+    acts = (torch.randn((T * R + 1, E, 2), generator=g, device="cuda:0") * 0.5).contiguous()
+    blobs = []
+    for graph in (False, True):
+        eng = CrowdNavEngine(cfg, "cuda:0")
+        eng.reset()
+        eng.step(acts[0])
+        if graph:
+            buf = acts[1:1 + T].clone()
+            eng.set_graph_mode(True)
+            gr = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(gr):
+                for t in range(T):
+                    eng.step(buf[t])
+            for r in range(R):
+                buf.copy_(acts[1 + r * T:1 + (r + 1) * T])
+                gr.replay()
+            torch.cuda.synchronize()
+            eng.set_graph_mode(False)
+        else:
+            for t in range(T * R):
+                eng.step(acts[1 + t])
+        blobs.append(np.asarray(eng.get_state().blob).copy())
+        eng.close()
+    np.testing.assert_array_equal(blobs[0], blobs[1])

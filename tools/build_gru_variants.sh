@@ -2,14 +2,9 @@
 #   bash tools/build_gru_variants.sh name "-DGF_WPC=3 ..." [name "-D..."] ...
 set -e
 R=$(cd "$(dirname "$0")/.." && pwd)
-V=$R/crowdnav_dsrnn_amd/lib/variants
-mkdir -p $V
-F="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wno-unused-result"
-[ -f $V/engine.o ] || hipcc $F -mllvm -disable-machine-licm -c -o $V/engine.o $R/crowdnav_dsrnn_amd/csrc/cn_engine.hip
+cd $R
 while [ $# -ge 2 ]; do
-  n=$1; d=$2; shift 2
-  hipcc $F $d -c -o $V/gru_$n.o $R/crowdnav_dsrnn_amd/csrc/cn_gru.hip -Rpass-analysis=kernel-resource-usage 2>&1 \
-    | grep -A12 "fused_kernel" | grep -E " VGPRs:|VGPRs Spill" | sed "s/.*remark: *//" | tr '\n' ' '; echo " <- $n"
-  hipcc --offload-arch=gfx950 -shared -fPIC -o $V/libcrowdnav_hip_$n.so $V/engine.o $V/gru_$n.o
-  rm -f $V/gru_$n.o
+  n=$1; d=$(for x in $2; do echo "-Dcn_gru.hip:${x#-D}"; done); shift 2
+  python -m crowdnav_dsrnn_amd.build --resources cn_gru.hip $d | grep fused_kernel | sed "s/\$/ <- $n/"
+  python -m crowdnav_dsrnn_amd.build --out $R/crowdnav_dsrnn_amd/lib/variants/libcrowdnav_hip_$n.so $d
 done

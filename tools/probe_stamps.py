@@ -1,7 +1,6 @@
 """Diagnostic: phase breakdown of the step and RNG kernels from the -DCN_STAMPS build.
 
-    hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -ffp-contract=off -DCN_STAMPS \
-        -o crowdnav_dsrnn_amd/lib/libcrowdnav_hip_stamps.so crowdnav_dsrnn_amd/csrc/cn_engine.hip crowdnav_dsrnn_amd/csrc/cn_gru.hip
+    bash tools/build_stamps.sh      (python -m crowdnav_dsrnn_amd.build -DCN_STAMPS --out .../libcrowdnav_hip_stamps.so)
 
     CN_LIB_PATH=crowdnav_dsrnn_amd/lib/libcrowdnav_hip_stamps.so python tools/probe_stamps.py [variant]
 """
