@@ -150,6 +150,12 @@ struct StepPlan {
 // multi-step launches store the caller's outputs in their last step only (0: in every step; the A/B of DESIGN.md §4)
 #define CN_SEQ_EMIT_LAST 1
 #endif
+#ifndef CN_SEQ_INFO_LAST
+// multi-step launches compute the values that only the info row reads (velocity rectangles and their intersection,
+// the not-reached count, jerk, speed, side preference) in the step that stores the row (0: in every step; the A/B
+// of DESIGN.md §4)
+#define CN_SEQ_INFO_LAST 1
+#endif
 #define CN_GRID 16
 #define CN_GRID_LDS (96 * 8 + CN_GRID * CN_GRID * 4 + 4 * 8 + 4 * 8)   // + spawn DiscGrid: agent table, masks, cover, box
 
@@ -2825,6 +2831,11 @@ __global__ void __launch_bounds__(CN_BLK, 3) cn_step_kernel(StepArgs g, cn_confi
 #endif
     const bool obs_rows = ROBOT && ((g.rollout >> 8) & CN_ROLLOUT_OBS_EVERY_STEP) != 0;
     const bool emit_obs = ROBOT ? (obs_rows || step == g.nsteps - 1) : emit;
+    // SEQ (not ROBOT, which records every step): the values only the info row reads -- the velocity rectangles and
+    // their intersection test (LF_VR), LF_NOTREACHED, R_JERK / R_SPD / R_SL / R_SR / R_SEP -- are computed in the step
+    // that stores the row (wave-uniform; folds to true as emit does). Everything the reward, done or the state
+    // depend on (sl.cd, the collision index, LF_ENDGOAL, the NaN bit, R_D2G, R_BITS, last_ax / last_ay) stays.
+    const bool info_on = (SEQ && !ROBOT && CN_SEQ_INFO_LAST) ? emit : true;
     const int64_t orw_e = ROBOT ? (int64_t)step * g.E : 0;
     const int64_t orw_o = obs_rows ? orw_e : 0;
     if constexpr (ROBOT) {
@@ -2948,13 +2959,15 @@ __global__ void __launch_bounds__(CN_BLK, 3) cn_step_kernel(StepArgs g, cn_confi
         const double vx0 = HF(sl, H_VX, hh), vy0 = HF(sl, H_VY, hh), rad = HF(sl, H_R, hh);
         const double rdx = px - RF(sl, R_PX, elh, EPB), rdy = py - RF(sl, R_PY, elh, EPB);
         sl.cd[hh] = dsqrt(rdx * rdx + rdy * rdy) - rad - RF(sl, R_RAD, elh, EPB);
-        double hcx[4], hcy[4];
-        vel_rect(px, py, vx0, vy0, rad, false, hcx, hcy);
-        for (int k = 0; k < 4; ++k) { hvr_ref(hh, k) = hcx[k]; hvr_ref(hh, 4 + k) = hcy[k]; }
-        // (the path-violation test of this rectangle against the robot's runs in human_post, phase 2: the
-        // robot's rectangle is computed beside this one, on wave 3)
         uint32_t f = 0u;
-        if (!(np_norm2(px - HF(sl, H_GX, hh), py - HF(sl, H_GY, hh)) < rad)) f |= LF_NOTREACHED;
+        if (info_on) {   // the rectangle and the not-reached flag feed the info row alone
+            double hcx[4], hcy[4];
+            vel_rect(px, py, vx0, vy0, rad, false, hcx, hcy);
+            for (int k = 0; k < 4; ++k) { hvr_ref(hh, k) = hcx[k]; hvr_ref(hh, 4 + k) = hcy[k]; }
+            // (the path-violation test of this rectangle against the robot's runs in human_post, phase 2: the
+            // robot's rectangle is computed beside this one, on wave 3)
+            if (!(np_norm2(px - HF(sl, H_GX, hh), py - HF(sl, H_GY, hh)) < rad)) f |= LF_NOTREACHED;
+        }
         sl.lf[hh] = f;
     };
     // robot VelocityRectangle (pre-move), phase 1 on wave 3
@@ -2992,7 +3005,7 @@ __global__ void __launch_bounds__(CN_BLK, 3) cn_step_kernel(StepArgs g, cn_confi
             upy = rpy + t1y - (double)(R * np_cosf(tr));
         }
         double side_l = 0, side_r = 0, sep = 0;
-        if (c.side_preference) {
+        if (c.side_preference && info_on) {
             const int eb = q * N;
             double ex, ey;
             if (holo) { ex = rpx + (double)(a0 * (float)dt); ey = rpy + (double)(a1 * (float)dt); }
@@ -3003,14 +3016,18 @@ __global__ void __launch_bounds__(CN_BLK, 3) cn_step_kernel(StepArgs g, cn_confi
         }
         {   // jerk (crowd_sim.py:1002-1009), float32 like the reference's np.float32 action
             const float ax = (float)cvx - (float)RF(sl, R_VX, q, EPB), ay = (float)cvy - (float)RF(sl, R_VY, q, EPB);
-            const float dax = ax - (float)RF(sl, R_LAX, q, EPB), day = ay - (float)RF(sl, R_LAY, q, EPB);
-            RF(sl, R_JERK, q, EPB) = (double)(dax * dax + day * day);
-            S.last_ax[gq] = ax; S.last_ay[gq] = ay;
+            if (info_on) {
+                const float dax = ax - (float)RF(sl, R_LAX, q, EPB), day = ay - (float)RF(sl, R_LAY, q, EPB);
+                RF(sl, R_JERK, q, EPB) = (double)(dax * dax + day * day);
+            }
+            S.last_ax[gq] = ax; S.last_ay[gq] = ay;   // (state: kept every step)
         }
         RF(sl, R_D2G, q, EPB) = np_norm2(rpx - rgx, rpy - rgy);
         const bool inside = inside_world(rpx, rpy, rr, c.square_width / 2);
-        { const float fx = (float)cvx, fy = (float)cvy; RF(sl, R_SPD, q, EPB) = (double)fsqrt(fx * fx + fy * fy); }
-        RF(sl, R_SL, q, EPB) = side_l; RF(sl, R_SR, q, EPB) = side_r; RF(sl, R_SEP, q, EPB) = sep;
+        if (info_on) {
+            { const float fx = (float)cvx, fy = (float)cvy; RF(sl, R_SPD, q, EPB) = (double)fsqrt(fx * fx + fy * fy); }
+            RF(sl, R_SL, q, EPB) = side_l; RF(sl, R_SR, q, EPB) = side_r; RF(sl, R_SEP, q, EPB) = sep;
+        }
         RF(sl, R_BITS, q, EPB) = (double)((reaching_goal ? 1u : 0u) | (inside ? 2u : 0u));
         RF(sl, R_CVX, q, EPB) = cvx; RF(sl, R_CVY, q, EPB) = cvy; RF(sl, R_NTH, q, EPB) = th_new;
         if (holo) {
@@ -3024,7 +3041,7 @@ __global__ void __launch_bounds__(CN_BLK, 3) cn_step_kernel(StepArgs g, cn_confi
     STAMP_T(17, 64);
     if (tid >= 128 && tid - 128 < nenv_here) robot_terms(tid - 128);
     STAMP_T(18, 128);
-    if (tid >= 192 && tid - 192 < nenv_here) robot_vr(tid - 192);
+    if (info_on && tid >= 192 && tid - 192 < nenv_here) robot_vr(tid - 192);
     const bool orca = c.human_policy == CN_POLICY_ORCA;
     uint32_t vis = 0, dm = 0;
     float my_vmax = 0.0f;
@@ -3106,8 +3123,10 @@ __global__ void __launch_bounds__(CN_BLK, 3) cn_step_kernel(StepArgs g, cn_confi
             const double cd = sl.cd[eb + k];
             if (cd < 0) { collision = true; kv = k; break; }
             else if (cd < dmin) dmin = cd;
-            const uint32_t f = sl.lf[eb + k];
-            agg += (f & LF_NOTREACHED) ? 1 : 0;
+            if (info_on) {
+                const uint32_t f = sl.lf[eb + k];
+                agg += (f & LF_NOTREACHED) ? 1 : 0;
+            }
         }
         sl.rflag[2 * EPB + re] = (uint32_t)kv;   // the path violations of humans k < kv are counted after phase 2
         // the reference tests the norm zones inside the loop once human 0 is not a collision; the penalty
@@ -3289,7 +3308,7 @@ __global__ void __launch_bounds__(CN_BLK, 3) cn_step_kernel(StepArgs g, cn_confi
                     //     lines space, unused until linearProgram3) and each slot's distSq
                     // (0) the path-violation test reads this human's velocity rectangle from Pb, which the
                     //     KdTree exchange reuses below
-                    if (hq) vr_kd = path_vr_q(h, sq);   // the whole quad
+                    if (hq && info_on) vr_kd = path_vr_q(h, sq);   // the whole quad
                     wsync();
                     const int HS = P.NH;   // LDS stride of the per-human slot / KdTree order arrays
                     float2 *XYP = (float2 *)Pb;          // [A] (x, y) in KdTree order, then the exchange space
@@ -3572,7 +3591,7 @@ __global__ void __launch_bounds__(CN_BLK, 3) cn_step_kernel(StepArgs g, cn_confi
 #endif
                     STAMP_A(9);
                     if (hq) {
-                        const bool vr = path_vr_q(h, sq);   // the whole quad
+                        const bool vr = info_on && path_vr_q(h, sq);   // the whole quad
                         if (sq == 0) human_post(h, (double)rx, (double)ry, vr);
                     }
                 } else if (hq) {
@@ -3619,7 +3638,7 @@ __global__ void __launch_bounds__(CN_BLK, 3) cn_step_kernel(StepArgs g, cn_confi
             const double n = np_norm2(nx, ny);
             if (n > vpref) { nvx = ddiv(nx, n) * vpref; nvy = ddiv(ny, n) * vpref; }
             else { nvx = nx; nvy = ny; }
-            human_post(tid, nvx, nvy, path_vr(tid));
+            human_post(tid, nvx, nvy, info_on && path_vr(tid));
         }
         STAMP_T(21, 64);
         if (rl && !ladder_done) ladder();

@@ -324,6 +324,20 @@ def run_xcd(rot=0, launches=60, warm=130, chunk=32, E=4096, N=10):
           % (resid.mean(axis=0).std(), wg_mean.std(), " ".join("%.2f" % resid[:, lab == b].mean() for b in range(8))))
     print("  spawn stats delta: %s" % {k: st1[k] - st0[k] for k in st1})
     print("  per step: kernel %.2f us" % (kern.mean() / chunk))
+    # the phases of one fused step: the per-workgroup stamps hold the last launch's last step (every step rewrites
+    # them; that step is the one that stores the state and the outputs)
+    L.cn_debug_stamps.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+    a = np.zeros(4096 * 24, np.uint64)
+    b = np.zeros(8192 * 24, np.uint64)
+    L.cn_debug_stamps(a.ctypes.data_as(ctypes.c_void_p), b.ctypes.data_as(ctypes.c_void_p))
+    A = a.reshape(-1, 24)[:nstep].astype(np.int64)
+    d = np.diff(A[:, :7], axis=1)
+    tot = A[:, 6] - A[:, 0]
+    names = ["load", "visibility", "policy+reward terms", "kinematics+stores", "-", "rng work (phase 5)"]
+    print("  last step of the last launch, cycles per workgroup: total median %d max %d" % (np.median(tot), tot.max()))
+    for k, nm in enumerate(names):
+        if nm != "-":
+            print("    %-26s median %8d  max %8d" % (nm, np.median(d[:, k]), d[:, k].max()))
     eng.close()
 
 
