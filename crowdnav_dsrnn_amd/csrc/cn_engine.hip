@@ -2573,6 +2573,36 @@ __device__ __forceinline__ void robot_sf_velocity(const cn_state_ptrs &S, int64_
     nn = np_norm2(nx, ny);
 }
 
+// cn_rollout_noisy: the executed action x = a + sigma * n of env G (global index) at step k of the caller's noise
+// sequence, n uniform in [-1, 1) from the words x, y of philox(counter k, key (seed, G)). (w >> 8) * 2^-24 and
+// 2 u - 1 are exact in float32; the product and the sum round once each (no contraction). One lane per env.
+// Shared by cn_action_noise_kernel and cn_step_kernel's rollout variant: one arithmetic, bit for bit.
+__device__ __forceinline__ void rollout_noise(float sigma, uint32_t seed, uint32_t k, uint32_t G, float ax, float ay,
+                                              float &x0, float &x1)
+{
+    const uint4 w = philox4x32_10(k, seed, G);
+    const float n0 = __fsub_rn(__fmul_rn(2.0f, __fmul_rn((float)(w.x >> 8), 0x1p-24f)), 1.0f);
+    const float n1 = __fsub_rn(__fmul_rn(2.0f, __fmul_rn((float)(w.y >> 8), 0x1p-24f)), 1.0f);
+    x0 = __fadd_rn(ax, __fmul_rn(sigma, n0));
+    x1 = __fadd_rn(ay, __fmul_rn(sigma, n1));
+}
+
+// The engine's device block of a cn_rollout_noisy call (behind the control words: cn_engine::work_count + CN_NOISE_W,
+// reached in the kernel from PendLaunch::stats), written on the stream before the call's fused launches.
+// `executed` (or null) and `actions` are the call's row 0: a launch's row of `executed` lies where its row of
+// `actions` lies.
+struct RolloutNoise {
+    float sigma;
+    uint32_t seed;
+    float *executed;
+    const float *actions;
+};
+#define CN_NOISE_W 16   // in uint32 words from work_count (PendLaunch::stats = work_count + 8)
+// StepArgs::rollout of a perturbed launch: CN_ROLLOUT_NOISY, and (uint32)k of the launch's first step above it (the
+// word stays >= 0, which is how step_launch tells a rollout launch)
+#define CN_ROLLOUT_NOISY (1ll << 16)
+#define CN_ROLLOUT_K_SHIFT 17
+
 // ------------------------------------------------------------------------------------------------
 // kernel A
 // ------------------------------------------------------------------------------------------------
@@ -2597,7 +2627,8 @@ struct StepArgs {
     union {
         uint32_t *ctl;
         int64_t action_stride;   // SEQ: step t takes the actions at actions + t * action_stride
-        // ROBOT (cn_rollout's launches; their action stride is always 2 * E): CN_ROBOT_* | cn_rollout_out::flags << 8
+        // ROBOT (cn_rollout's launches; their action stride is always 2 * E): CN_ROBOT_* | cn_rollout_out::flags << 8;
+        // cn_rollout_noisy's: | CN_ROLLOUT_NOISY | (uint32)k of the launch's first step << CN_ROLLOUT_K_SHIFT
         int64_t rollout;
     };
     uint32_t *plist_base;  // [3][E + 64][4] spawn lists: {env, reset_count, case_counter lo, hi} after the reset
@@ -2669,7 +2700,9 @@ __device__ inline float bbox_dist(float x, float y, float mnx, float mxx, float 
 // memory, with cn_robot_act's device functions (ORCA's quad path: one quad per env, EPB <= 16 envs; social force: one
 // lane per env), stores them to row `step` of g.actions and hands them to phase 0 through LDS. Every step records
 // its outputs at row `step` of [nsteps][E][..] buffers (the observation only with CN_ROLLOUT_OBS_EVERY_STEP;
-// otherwise the launch's last step stores it to a single row, as the SEQ kernels do).
+// otherwise the launch's last step stores it to a single row, as the SEQ kernels do). A launch of cn_rollout_noisy
+// (CN_ROLLOUT_NOISY in g.rollout, wave-uniform) perturbs the action on its way into LDS (rollout_noise, parameters
+// from the engine's RolloutNoise block): row `step` of g.actions keeps the clean one, `executed` gets the perturbed.
 template <bool KD, bool PHX, bool MIX, bool DEVSEQ = false, bool SEQ = false, bool ROBOT = false>
 __global__ void __launch_bounds__(CN_BLK, 3) cn_step_kernel(StepArgs g, cn_config c)
 {
@@ -2845,6 +2878,13 @@ __global__ void __launch_bounds__(CN_BLK, 3) cn_step_kernel(StepArgs g, cn_confi
         // RNG region, so SL::app behind the plan is out of reach). A quad is whole or absent (q < nenv_here).
         if ((tid >> 6) == 0) {
             float *const arow = const_cast<float *>(actions);
+            // cn_rollout_noisy's launches (wave-uniform): the step takes the perturbed action, the `actions` row keeps
+            // the clean one, the `executed` row (same place in its buffer) gets the perturbed one
+            const bool noisy = (g.rollout & CN_ROLLOUT_NOISY) != 0;
+            RolloutNoise nz = {0.0f, 0u, nullptr, nullptr};
+            if (noisy) nz = *(const RolloutNoise *)(g.pend.stats + (CN_NOISE_W - 8));
+            const uint32_t nk = (uint32_t)(g.rollout >> CN_ROLLOUT_K_SHIFT) + (uint32_t)step;
+            float *const xrow = nz.executed ? nz.executed + (arow - nz.actions) : nullptr;
             if ((int)(g.rollout & 0xff) == CN_ROBOT_SOCIAL_FORCE) {
                 if (tid < nenv_here) {
                     double nx, ny, nn, vpref;   // (the clip and the rounding of cn_robot_sf_kernel)
@@ -2853,6 +2893,10 @@ __global__ void __launch_bounds__(CN_BLK, 3) cn_step_kernel(StepArgs g, cn_confi
                     if (nn > vpref) { ax = (float)(ddiv(nx, nn) * vpref); ay = (float)(ddiv(ny, nn) * vpref); }
                     else { ax = (float)nx; ay = (float)ny; }
                     arow[2 * (int64_t)(e0 + tid)] = ax; arow[2 * (int64_t)(e0 + tid) + 1] = ay;
+                    if (noisy) {
+                        rollout_noise(nz.sigma, nz.seed, nk, (uint32_t)(c.env_offset + e0 + tid), ax, ay, ax, ay);
+                        if (xrow) { xrow[2 * (int64_t)(e0 + tid)] = ax; xrow[2 * (int64_t)(e0 + tid) + 1] = ay; }
+                    }
                     sl.act[tid] = ax; sl.act[EPB + tid] = ay;
                 }
             } else {
@@ -2870,6 +2914,10 @@ __global__ void __launch_bounds__(CN_BLK, 3) cn_step_kernel(StepArgs g, cn_confi
                     robot_orca_solve(S, e, cnt, sq, Lq, rx, ry);
                     if (sq == 0) {
                         arow[2 * e] = rx; arow[2 * e + 1] = ry;
+                        if (noisy) {
+                            rollout_noise(nz.sigma, nz.seed, nk, (uint32_t)(c.env_offset + e), rx, ry, rx, ry);
+                            if (xrow) { xrow[2 * e] = rx; xrow[2 * e + 1] = ry; }
+                        }
                         sl.act[q] = rx; sl.act[EPB + q] = ry;
                     }
                 }

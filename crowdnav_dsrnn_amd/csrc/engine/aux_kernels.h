@@ -1,8 +1,9 @@
 // aux_kernels.h -- the small stand-alone kernels: the debug / predictor kernels that expose the step kernel's
 // device functions on caller-given inputs (cn_disc_quad, cn_copy64, cn_orca, cn_orca_kd with RVO2's sequential
-// KdTree, cn_sf_predict), cn_robot_act's three kernels, and the two stream-ordered helpers of the host API
-// (cn_ctl_set_kernel, cn_keysnap_kernel). Part of cn_engine.hip's translation unit: included there after the
-// device core, whose geometry, ORCA and scripted-robot functions these kernels call.
+// KdTree, cn_sf_predict), cn_robot_act's three kernels, cn_rollout_noisy's (cn_action_noise_kernel,
+// cn_noise_set_kernel, cn_copy32_kernel), and the two stream-ordered helpers of the host API (cn_ctl_set_kernel,
+// cn_keysnap_kernel). Part of cn_engine.hip's translation unit: included there after the device core, whose
+// geometry, ORCA and scripted-robot functions these kernels call.
 #pragma once
 
 __global__ void __launch_bounds__(64) cn_disc_quad_kernel(int64_t n, int mode, const double *px, const double *py,
@@ -331,6 +332,36 @@ __global__ void __launch_bounds__(64) cn_robot_sf_kernel(cn_state_ptrs S, int E,
     robot_sf_velocity(S, e, N, A, B, KI, dt, nx, ny, nn, vpref);
     if (nn > vpref) { actions[2 * e] = (float)(ddiv(nx, nn) * vpref); actions[2 * e + 1] = (float)(ddiv(ny, nn) * vpref); }
     else { actions[2 * e] = (float)nx; actions[2 * e + 1] = (float)ny; }
+}
+
+// cn_rollout_noisy outside the fused launches: the perturbation between cn_robot_act's kernel and the step. `act` is
+// the clean row the robot kernel wrote, `x` the engine's (E, 2) scratch the step reads, `executed` the caller's row
+// or null; rollout_noise's arithmetic, one lane per env.
+__global__ void __launch_bounds__(64) cn_action_noise_kernel(const float *__restrict__ act, float *__restrict__ x,
+                                                             float *__restrict__ executed, int E, float sigma,
+                                                             uint32_t seed, uint32_t k, uint32_t G0)
+{
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= E) return;
+    float x0, x1;
+    rollout_noise(sigma, seed, k, G0 + (uint32_t)e, act[2 * (int64_t)e], act[2 * (int64_t)e + 1], x0, x1);
+    x[2 * (int64_t)e] = x0; x[2 * (int64_t)e + 1] = x1;
+    if (executed) { executed[2 * (int64_t)e] = x0; executed[2 * (int64_t)e + 1] = x1; }
+}
+
+// cn_rollout_noisy's device block for the fused launches that follow on the stream (a kernel for the reason
+// cn_ctl_set_kernel is one)
+__global__ void cn_noise_set_kernel(RolloutNoise *w, RolloutNoise v)
+{
+    if (threadIdx.x == 0) *w = v;
+}
+
+// cn_rollout_noisy at sigma == 0: `executed` is a copy of `actions` (bits, no arithmetic); n words
+__global__ void __launch_bounds__(256) cn_copy32_kernel(int64_t n, const uint32_t *__restrict__ src,
+                                                        uint32_t *__restrict__ dst)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) dst[i] = src[i];
 }
 
 // One control word of the engine set from the stream (graph mode's draw-all flag after cn_reset /

@@ -125,18 +125,19 @@ int cn_create(const cn_config *cfg, int device, cn_engine **out)
     const int64_t pend_bytes = pb_mt + 5 * pb_i + 2 * pb_cc + pb_r + pb_h;
     hipError_t e1 = hipMalloc(&g->state, g->state_bytes);
     hipError_t e2 = hipMalloc(&g->work, sizeof(uint32_t) * (g->E + 64));
-    hipError_t e3 = hipMalloc(&g->work_count, 64);
+    hipError_t e3 = hipMalloc(&g->work_count, CN_WORK_BYTES);
     hipError_t e4 = hipMalloc(&g->plist, sizeof(uint32_t) * 3 * 4 * (g->E + 64));
     hipError_t e6 = hipMalloc(&g->rlist, sizeof(uint32_t) * 3 * 4 * (2 * (int64_t)g->E + 64));
     hipError_t e5 = hipMalloc(&g->pend_mem, pend_bytes);
+    hipError_t e7 = hipMalloc(&g->act_x, sizeof(float) * 2 * (g->E + 64));
     if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess || e4 != hipSuccess || e5 != hipSuccess ||
-        e6 != hipSuccess) {
+        e6 != hipSuccess || e7 != hipSuccess) {
         (void)hipFree(g->state); (void)hipFree(g->work); (void)hipFree(g->work_count); (void)hipFree(g->plist); (void)hipFree(g->pend_mem);
-        (void)hipFree(g->rlist);
+        (void)hipFree(g->rlist); (void)hipFree(g->act_x);
         delete g;
         return set_err(CN_ENOMEM, "hipMalloc failed");
     }
-    if (hipMemset(g->state, 0, g->state_bytes) != hipSuccess || hipMemset(g->work_count, 0, 64) != hipSuccess ||
+    if (hipMemset(g->state, 0, g->state_bytes) != hipSuccess || hipMemset(g->work_count, 0, CN_WORK_BYTES) != hipSuccess ||
         hipMemset(g->pend_mem, 0, pend_bytes) != hipSuccess) {
         cn_destroy(g);
         return set_err(CN_EHIP, "hipMemset failed");
@@ -352,6 +353,7 @@ void cn_destroy(cn_engine *g)
     (void)hipFree(g->plist);
     (void)hipFree(g->rlist);
     (void)hipFree(g->pend_mem);
+    (void)hipFree(g->act_x);
     delete g;
 }
 
@@ -724,7 +726,12 @@ int cn_robot_act(cn_engine *g, void *stream, int policy, float *actions)
 // cn_robot_act + cn_step for t = 0..T-1 with every step recorded at row t. Fused (the ROBOT kernels: up to seq_chunk
 // steps per launch, the controller inside the step workgroups) where cn_step_seq's multi-step launches apply and the
 // controller fits the step workgroup; launch pairs otherwise, the first step after cn_reset / cn_set_state included.
-int cn_rollout(cn_engine *g, void *stream, int policy, int T, const cn_rollout_out *out, int32_t *num_launches)
+// nz (cn_rollout_noisy, sigma > 0; null: cn_rollout): the step takes the perturbed action. The fused launches carry
+// CN_ROLLOUT_NOISY and their first step's k in StepArgs::rollout and read the rest from the engine's RolloutNoise
+// block, written once per call on the stream before the first of them; elsewhere cn_action_noise_kernel runs between
+// the pair's two launches and the step reads the engine's scratch.
+static int rollout_run(cn_engine *g, void *stream, int policy, int T, const cn_rollout_out *out,
+                       const cn_rollout_noise *nz, int32_t *num_launches)
 {
     if (num_launches) *num_launches = 0;
     if (!g) return set_err(CN_EINVAL, "null engine");
@@ -736,11 +743,13 @@ int cn_rollout(cn_engine *g, void *stream, int policy, int T, const cn_rollout_o
     if (g->c.kinematics != CN_HOLONOMIC)
         return set_err(CN_EUNSUPPORTED, "cn_rollout: the controllers return ActionXY (holonomic engines only)");
     const int64_t E = g->E, N = g->N;
+    const hipStream_t st = (hipStream_t)stream;
     const bool every = (out->flags & CN_ROLLOUT_OBS_EVERY_STEP) != 0;
     // the controller fits the step workgroup: social force (a lane per env) always, ORCA on its quad path
     const bool fits = policy == CN_ROBOT_SOCIAL_FORCE || g->N + 1 <= 10;
     const bool fusable = fits && g->seq_chunk > 1 && !g->rows && !g->devseq && !g->plan.kd;
     const int64_t rollout = (int64_t)policy | ((int64_t)(out->flags & CN_ROLLOUT_OBS_EVERY_STEP) << 8);
+    bool block_set = false;
     int nl = 0;
     for (int t = 0; t < T;) {
         const int64_t ro = every ? t : 0;   // the observation's row
@@ -753,23 +762,72 @@ int cn_rollout(cn_engine *g, void *stream, int policy, int T, const cn_rollout_o
         float *const inf = out->info ? out->info + t * E * CN_INFO_K : nullptr;
         double *const epr = out->ep_return ? out->ep_return + t * E : nullptr;
         int32_t *const epl = out->ep_len ? out->ep_len + t * E : nullptr;
+        const uint32_t k = nz ? (uint32_t)(uint64_t)(nz->step0 + t) : 0u;   // the step's Philox counter
         int n = 1, rc;
         if (fusable && !g->pend_all) {
             n = T - t < g->seq_chunk ? T - t : g->seq_chunk;
             // (a launch never straddles the end of cn_profile's window: cn_step_seq)
             if (g->prof_on && g->prof_n < g->prof_cap && n > g->prof_cap - g->prof_n) n = g->prof_cap - g->prof_n;
-            rc = step_launch(g, stream, act, n, 2 * E, rn, te, se, rw, dn, ev, inf, epr, epl, rollout);
+            int64_t word = rollout;
+            if (nz) {
+                if (!block_set) {
+                    const RolloutNoise v = {nz->sigma, nz->seed, nz->executed, out->actions};
+                    (void)hipGetLastError();
+                    hipLaunchKernelGGL(cn_noise_set_kernel, dim3(1), dim3(64), 0, st,
+                                       (RolloutNoise *)(g->work_count + CN_NOISE_W), v);
+                    HIPCHK(hipGetLastError());
+                    block_set = true;
+                    nl += 1;
+                }
+                word |= CN_ROLLOUT_NOISY | ((int64_t)k << CN_ROLLOUT_K_SHIFT);
+            }
+            rc = step_launch(g, stream, act, n, 2 * E, rn, te, se, rw, dn, ev, inf, epr, epl, word);
             nl += 1;
         } else {
             rc = cn_robot_act(g, stream, policy, act);
             if (rc) return rc;
-            rc = cn_step(g, stream, act, rn, te, se, rw, dn, ev, inf, epr, epl);
+            const float *stepped = act;
+            if (nz) {
+                (void)hipGetLastError();
+                hipLaunchKernelGGL(cn_action_noise_kernel, dim3((unsigned)((E + 63) / 64)), dim3(64), 0, st, act, g->act_x,
+                                   nz->executed ? nz->executed + t * E * 2 : nullptr, (int)E, nz->sigma, nz->seed, k,
+                                   (uint32_t)(uint64_t)g->c.env_offset);
+                HIPCHK(hipGetLastError());
+                stepped = g->act_x;
+                nl += 1;
+            }
+            rc = cn_step(g, stream, stepped, rn, te, se, rw, dn, ev, inf, epr, epl);
             nl += 2;
         }
         if (rc) return rc;
         t += n;
         if (num_launches) *num_launches = nl;
     }
+    return CN_OK;
+}
+
+int cn_rollout(cn_engine *g, void *stream, int policy, int T, const cn_rollout_out *out, int32_t *num_launches)
+{
+    return rollout_run(g, stream, policy, T, out, nullptr, num_launches);
+}
+
+int cn_rollout_noisy(cn_engine *g, void *stream, int policy, int T, const cn_rollout_out *out,
+                     const cn_rollout_noise *noise, int32_t *num_launches)
+{
+    if (num_launches) *num_launches = 0;
+    if (!g) return set_err(CN_EINVAL, "null engine");
+    if (!noise || !(noise->sigma >= 0.0f && noise->sigma <= 3.402823466e38f))   // (NaN fails both comparisons)
+        return set_err(CN_EINVAL, "cn_rollout_noisy: noise with a finite sigma >= 0 required");
+    if (noise->sigma > 0.0f) return rollout_run(g, stream, policy, T, out, noise, num_launches);
+    // sigma == 0: cn_rollout itself; `executed` is a copy of the actions it recorded
+    const int rc = rollout_run(g, stream, policy, T, out, nullptr, num_launches);
+    if (rc || !noise->executed || T == 0) return rc;
+    const int64_t n = (int64_t)T * g->E * 2;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(cn_copy32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n,
+                       (const uint32_t *)out->actions, (uint32_t *)noise->executed);
+    HIPCHK(hipGetLastError());
+    if (num_launches) *num_launches += 1;
     return CN_OK;
 }
 

@@ -7,6 +7,10 @@
 #pragma once
 #include "aux_kernels.h"
 
+#define CN_WORK_BYTES 128
+static_assert(CN_NOISE_W * 4 + sizeof(RolloutNoise) <= CN_WORK_BYTES && (CN_NOISE_W * 4) % alignof(RolloutNoise) == 0,
+              "cn_engine::work_count: the RolloutNoise block behind the 16 control words");
+
 struct cn_engine {
     cn_config c;
     int device;
@@ -17,7 +21,9 @@ struct cn_engine {
     cn_state_ptrs s;
     uint32_t *work;       // [E]
     uint32_t *work_count; // [16]: [2..4] spawn-list counters (triple buffered), [5..7] parked-spawn counters,
-                          // [8..11] spawn statistics (PendLaunch::stats), [15] inline reset draws
+                          // [8..11] spawn statistics (PendLaunch::stats), [15] inline reset draws; behind them
+                          // (word CN_NOISE_W) cn_rollout_noisy's RolloutNoise block: CN_WORK_BYTES in all
+    float *act_x;         // [E][2] cn_rollout_noisy's launch triples: the perturbed action the step reads
     uint32_t *plist;      // [3][E + 64][4] envs whose spawn after next kernel A draws, with their counters
     uint32_t *rlist;      // [3][2E][4] spawns parked by a launch (resumed by the next); counters work_count[5..7]
     int devseq;           // graph mode (cn_set_graph_mode): the step sequence lives in work_count[12..14]

@@ -5,10 +5,43 @@ owns the output buffers (torch, on the engine's device) and passes `data_ptr()`s
 torch stream to `cn_reset` / `cn_step`. No compute happens here and there is no CPU fallback.
 """
 import ctypes
+import dataclasses
+import math
 
 import numpy as np
 
 from . import _lib, abi
+
+
+@dataclasses.dataclass(frozen=True)
+class RolloutNoise:
+    """The perturbation of a rollout with noise (cn_rollout_noise): the executed action is the scripted robot's
+    plus sigma * n, n uniform in [-1, 1) per component; step0 is the index of the call's first step in the caller's
+    noise sequence (a chunked rollout continues it: step0 += T)."""
+    sigma: float
+    seed: int = 0
+    step0: int = 0
+
+    def __post_init__(self):
+        s = float(self.sigma)
+        if not (math.isfinite(s) and s >= 0.0):
+            raise ValueError("RolloutNoise: a finite sigma >= 0 required, got %r" % (self.sigma,))
+        object.__setattr__(self, "sigma", s)
+        object.__setattr__(self, "seed", int(self.seed))
+        object.__setattr__(self, "step0", int(self.step0))
+
+    @classmethod
+    def of(cls, noise):
+        """None, a RolloutNoise, or a dict with sigma and optionally seed / step0."""
+        if noise is None or isinstance(noise, cls):
+            return noise
+        if isinstance(noise, dict):
+            extra = set(noise) - {"sigma", "seed", "step0"}
+            if extra or "sigma" not in noise:
+                raise ValueError("rollout noise: a dict with sigma and optionally seed / step0, got keys %s"
+                                 % sorted(noise))
+            return cls(**noise)
+        raise TypeError("rollout noise: None, a RolloutNoise or a dict, got %r" % type(noise).__name__)
 
 
 class CrowdNavEngine:
@@ -196,10 +229,13 @@ class CrowdNavEngine:
             _lib.check(_lib.lib().cn_robot_act(self._h, self._stream(), self.ROBOT_POLICIES[policy], out.data_ptr()))
         return out
 
-    def rollout_buffers(self, T, obs_every_step=True):
-        """Fresh device tensors for rollout(T): the `out` dict without 'num_launches'."""
+    def rollout_buffers(self, T, obs_every_step=True, executed=False):
+        """Fresh device tensors for rollout(T): the `out` dict without 'num_launches' (executed=True: with the
+        'executed' rows of a rollout with noise)."""
         t, E, N, dev = self.torch, self.E, self.N, self.device
         out = {"actions": t.zeros((T, E, 2), dtype=t.float32, device=dev)}
+        if executed:
+            out["executed"] = t.zeros((T, E, 2), dtype=t.float32, device=dev)
         if obs_every_step:
             out["robot_node"] = t.zeros((T, E, 1, 7), dtype=t.float32, device=dev)
             out["temporal_edges"] = t.zeros((T, E, 1, 2), dtype=t.float32, device=dev)
@@ -216,7 +252,7 @@ class CrowdNavEngine:
 
     _ROLLOUT_OPTIONAL = ("reward", "done", "event", "info", "ep_return", "ep_len")
 
-    def rollout(self, policy, T, obs_every_step=True, out=None):
+    def rollout(self, policy, T, obs_every_step=True, out=None, noise=None):
         """T closed-loop steps of the scripted robot (cn_rollout): robot_act(policy) -> step, every step recorded,
         with the rows of that eager loop bit for bit. Returns a dict of device tensors: actions (T, E, 2);
         robot_node / temporal_edges / spatial_edges (T, E, ...) = the observation AFTER step t (with
@@ -224,18 +260,25 @@ class CrowdNavEngine:
         info, ep_return, ep_len (T, E, ...); 'num_launches' (int). `out`: a dict from an earlier call (or
         rollout_buffers) to reuse; of the six per-step records any may be left out or None (not recorded). Where
         the engine allows it the steps run inside multi-step launches with the controller in the step kernel; no
-        host sync either way."""
+        host sync either way.
+        noise (a RolloutNoise or a dict with sigma / seed / step0; None: cn_rollout as ever) -> cn_rollout_noisy: the
+        step takes actions + sigma * n with n uniform in [-1, 1) per component, drawn per (seed, global env index,
+        step0 + t); 'actions' keeps the clean labels and the dict gains 'executed' (T, E, 2), what the step took
+        (allocated when `out` lacks it)."""
         t = self.torch
         if policy not in self.ROBOT_POLICIES:
             raise ValueError("rollout: policy %r (one of %s)" % (policy, sorted(self.ROBOT_POLICIES)))
         T = int(T)
         if T < 0:
             raise ValueError("rollout: T >= 0 required, got %d" % T)
+        noise = RolloutNoise.of(noise)
         E, N = self.E, self.N
         if out is None:
-            out = self.rollout_buffers(T, obs_every_step)
+            out = self.rollout_buffers(T, obs_every_step, executed=noise is not None)
         else:
             out = dict(out)
+            if noise is not None and out.get("executed") is None:
+                out["executed"] = t.zeros((T, E, 2), dtype=t.float32, device=self.device)
         R = 1 if not obs_every_step else T
         want = {"actions": (T * E * 2, t.float32), "robot_node": (R * E * 7, t.float32),
                 "temporal_edges": (R * E * 2, t.float32), "spatial_edges": (R * E * N * 2, t.float32),
@@ -253,13 +296,23 @@ class CrowdNavEngine:
                                  % (k, dt, n, self.device))
             setattr(ro, k, v.data_ptr())
         ro.flags = _lib.ROLLOUT_OBS_EVERY_STEP if obs_every_step else 0
+        if noise is not None:
+            x = out["executed"]
+            if x.dtype != t.float32 or x.device != self.device or not x.is_contiguous() or x.numel() != T * E * 2:
+                raise ValueError("rollout: out['executed'] must be a contiguous %s tensor of %d elements on %s"
+                                 % (t.float32, T * E * 2, self.device))
         nl = ctypes.c_int32(0)
         if T == 0:   # (empty tensors have no address to pass; cn_rollout launches nothing for T = 0 either)
             out["num_launches"] = 0
             return out
         with t.cuda.device(self.device):
-            _lib.check(_lib.lib().cn_rollout(self._h, self._stream(), self.ROBOT_POLICIES[policy], T,
-                                             ctypes.byref(ro), ctypes.byref(nl)))
+            if noise is None:
+                _lib.check(_lib.lib().cn_rollout(self._h, self._stream(), self.ROBOT_POLICIES[policy], T,
+                                                 ctypes.byref(ro), ctypes.byref(nl)))
+            else:
+                nz = _lib.RolloutNoise(noise.sigma, noise.seed & 0xFFFFFFFF, noise.step0, out["executed"].data_ptr())
+                _lib.check(_lib.lib().cn_rollout_noisy(self._h, self._stream(), self.ROBOT_POLICIES[policy], T,
+                                                       ctypes.byref(ro), ctypes.byref(nz), ctypes.byref(nl)))
         out["num_launches"] = int(nl.value)
         return out
 

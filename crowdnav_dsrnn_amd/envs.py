@@ -321,15 +321,17 @@ class CrowdNavVecEnv:
         (E, 2) float32 on the engine's GPU (CrowdNavEngine.robot_act; no host synchronisation)."""
         return self.engine.robot_act(policy)
 
-    def rollout(self, policy, T, obs_every_step=True, out=None):
+    def rollout(self, policy, T, obs_every_step=True, out=None, noise=None):
         """T closed-loop steps of the scripted robot ('orca' / 'social_force') from the state the last reset / step
         left, every step recorded (CrowdNavEngine.rollout: a dict of (T, E, ...) tensors on the engine's GPU, no
-        host synchronisation). The recorded observation is the SRNN one, so obs_mode 'srnn' only."""
+        host synchronisation). The recorded observation is the SRNN one, so obs_mode 'srnn' only. `noise`: the
+        engine's RolloutNoise (or a dict) -- the steps take perturbed actions, 'actions' keeps the clean labels and
+        'executed' holds what was taken."""
         if self.obs_mode != "srnn":
             raise UnsupportedConfig("rollout: obs_mode=%r (the rollout records the 'srnn' observation only)"
                                     % self.obs_mode)
         self._state_cache = None
-        return self.engine.rollout(policy, T, obs_every_step=obs_every_step, out=out)
+        return self.engine.rollout(policy, T, obs_every_step=obs_every_step, out=out, noise=noise)
 
     def _state(self):
         if self._state_cache is None:

@@ -29,6 +29,8 @@ Reference quirks kept on purpose:
 Multi-GPU: with torch.distributed initialised each rank evaluates its env shard (global env index
 rank*E + i, nenv = world*E) with no communication in the loop; the records are summed once at the end.
 """
+import dataclasses
+
 import numpy as np
 import torch
 
@@ -297,13 +299,16 @@ def evaluate(actor_critic, ob_rms, eval_envs, num_processes, device, config, log
 
 
 def evaluate_scripted(name, eval_envs, num_processes, device, config, logging, chunk=None, keep_traces=True,
-                      verbose=True):
+                      verbose=True, noise=None):
     """evaluate() of the scripted robot `name` ('orca' / 'social_force') on whole rollouts: after reset(), rollouts
     of `chunk` steps (default: the engine's steps per multi-step launch) through ScriptedRobot.rollout, every
     recorded row fed to the same EpisodeRecorder, the end-of-run check once per chunk, the same report. Episodes
     past test_size go to the recorder's spare slot, so the steps a chunk runs past the last counted episode do
-    not change the records: they equal evaluate(ScriptedRobot(eval_envs, name), ...)'s."""
+    not change the records: they equal evaluate(ScriptedRobot(eval_envs, name), ...)'s.
+    `noise` (engine.RolloutNoise or a dict with sigma / seed / step0): the controller's executed actions are perturbed
+    (ScriptedRobot.rollout's noise; the chunks continue step0), i.e. the report is the noisy expert's."""
     from .config import UnsupportedConfig
+    from .engine import RolloutNoise
     from .policy_factory import ScriptedRobot
 
     ScriptedRobot.check(eval_envs, name)
@@ -329,11 +334,14 @@ def evaluate_scripted(name, eval_envs, num_processes, device, config, logging, c
     C = int(chunk) if chunk is not None else int(eval_envs.engine.seq_chunk)
     if C < 1:
         raise ValueError("evaluate_scripted: chunk >= 1 required, got %d" % C)
+    noise = RolloutNoise.of(noise)
     obs = eval_envs.reset()
     rec.start(obs)
     buf = None
+    done_steps = 0
     while True:
-        buf = robot.rollout(C, out=buf)
+        buf = robot.rollout(C, out=buf, noise=noise and dataclasses.replace(noise, step0=noise.step0 + done_steps))
+        done_steps += C
         for t in range(C):
             rec.step({"robot_node": buf["robot_node"][t], "temporal_edges": buf["temporal_edges"][t]},
                      buf["reward"][t], buf["done"][t], buf["event"][t], buf["info"][t])

@@ -3,6 +3,8 @@
 Same classes and methods as the reference's pytorchBaselines/a2c_ppo_acktr/{storage.py,algo/ppo.py}, kept
 resident on the GPU; with torch.distributed initialised (one process per GPU, backend "nccl" = RCCL)
 the gradients are all-reduced per minibatch and the advantage normalisation uses global statistics.
+BehaviourCloning (imitation.py) pre-trains the same policy on noise-injected rollouts of a scripted expert.
 """
+from .imitation import BehaviourCloning  # noqa: F401
 from .ppo import PPO  # noqa: F401
 from .storage import RolloutStorage, SRNNRolloutStorage  # noqa: F401

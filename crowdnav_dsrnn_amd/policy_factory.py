@@ -283,16 +283,18 @@ class ScriptedRobot:
         the engine's state is the state `obs` came from."""
         return None, self.venv.robot_act(self.name), None, hxs
 
-    def rollout(self, T, obs_every_step=True, out=None):
+    def rollout(self, T, obs_every_step=True, out=None, noise=None):
         """T closed-loop steps of this controller from the env's current state, every step recorded
         (CrowdNavVecEnv.rollout -> cn_rollout): a dict of (T, E, ...) device tensors -- actions, the observation
         after each step, reward, done, event, info, ep_return, ep_len -- and 'num_launches'. Expert pairs are
-        (observation row t-1, actions row t), row -1 being the reset observation. 'srnn' observation only."""
+        (observation row t-1, actions row t), row -1 being the reset observation. 'srnn' observation only.
+        `noise` (engine.RolloutNoise or a dict with sigma / seed / step0): noise-injected demonstrations -- the steps
+        take actions + sigma * uniform[-1, 1) noise (returned as 'executed'), the labels in 'actions' stay clean."""
         self.check(self.venv, self.name)
         if getattr(self.venv, "obs_mode", "srnn") != "srnn":
             raise UnsupportedConfig("ScriptedRobot.rollout: obs_mode=%r (the rollout records the 'srnn' observation "
                                     "only)" % self.venv.obs_mode)
-        return self.venv.rollout(self.name, T, obs_every_step=obs_every_step, out=out)
+        return self.venv.rollout(self.name, T, obs_every_step=obs_every_step, out=out, noise=noise)
 
 
 policy_factory = {"orca": ORCA, "none": none_policy, "social_force": SOCIAL_FORCE, "srnn": SRNN, "convgru": SRNN}

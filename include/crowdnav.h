@@ -36,6 +36,8 @@
  *   cn_rollout       ⟵ the closed loop `action = robot.act(ob); ob, ... = env.step(action)` of a scripted robot
  *                   over T steps (crowd_nav test loop / expert demonstrations), every step recorded, in
  *                   multi-step launches with the controller inside the step kernel
+ *   cn_rollout_noisy ⟵ (no reference counterpart) cn_rollout whose executed action is the clean one plus uniform
+ *                   noise, the label staying clean: noise-injected expert demonstrations for behaviour cloning
  *   cn_lidar_obs     ⟵ CrowdSimDict.generate_ob's 'convgru' observation (crowd_sim_dict.py:96-101) with
  *                   LidarSensor.sensor_spin (crowd_sim/envs/utils/lidarv2.py:398-427) evaluated at reset
  *   cn_lidar_scan    ⟵ the scan CrowdSimDict.step() takes every step and discards (crowd_sim_dict.py:224-251):
@@ -527,6 +529,31 @@ typedef struct cn_rollout_out {
 } cn_rollout_out;
 #define CN_ROLLOUT_OBS_EVERY_STEP 1
 int cn_rollout(cn_engine *eng, void *stream, int policy, int T, const cn_rollout_out *out, int32_t *num_launches);
+
+/* cn_rollout with a perturbed executed action (noise injection for imitation data): the recorded label stays the
+ * controller's clean action, the step consumes the perturbed one. For env e (global index G = env_offset + e) and
+ * step t of the call, with k = step0 + t:
+ *   w   = philox4x32_10(counter (uint32)k, key (seed, (uint32)G))        (the generator of CN_RNG_PHILOX)
+ *   n_j = 2 * ((float)(w_j >> 8) * 2^-24) - 1,  j = 0, 1 (words x, y)    (exact in float32, in [-1, 1))
+ *   x_j = a_j + sigma * n_j                                              (float32: one rounded product, one rounded sum)
+ * a (cn_robot_act's action) goes to out->actions[t][e], x to executed[t][e] (if given) and into the step, whose own
+ * clip_action applies to it as to any caller's action. Every other output is cn_rollout's. A call of T steps equals
+ * calls of T1 and T - T1 steps with step0 and step0 + T1. sigma == 0 is cn_rollout itself (no arithmetic: a -0.0f
+ * action keeps its sign) followed by a copy of actions into executed.
+ *   Fused path (cn_rollout's conditions): the rollout launches perturb the action between their controller and their
+ * step; one small launch before them hands sigma / seed / executed to the engine's device block. Elsewhere a step
+ * is three launches: cn_robot_act, the perturbation (into an engine-owned (E, 2) scratch), cn_step.
+ * Stream-ordered; no allocation, no synchronisation, no memset. *num_launches counts every kernel launch.
+ * CN_EINVAL: noise NULL, sigma < 0 or not finite, and cn_rollout's; CN_EUNSUPPORTED: cn_rollout's. All are checked
+ * before any launch (*num_launches = 0). */
+typedef struct cn_rollout_noise {
+    float    sigma;     /* half-width of the uniform perturbation per action component (m/s); finite, >= 0 */
+    uint32_t seed;
+    int64_t  step0;     /* index of this call's first step in the caller's noise sequence (chunked calls continue it) */
+    float   *executed;  /* [T][E][2] optional: the action the step actually took */
+} cn_rollout_noise;
+int cn_rollout_noisy(cn_engine *eng, void *stream, int policy, int T, const cn_rollout_out *out,
+                     const cn_rollout_noise *noise, int32_t *num_launches);
 
 /* Test hooks of the kd-tree path's resumable spawns (the spawn waves that draw upcoming episodes park a
  * crowded spawn between two humans once a wave has worked `cycles` clock cycles in a launch, and a later

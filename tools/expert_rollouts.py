@@ -8,18 +8,22 @@ trip). The file holds
   robot_node      (T + 1, E, 1, 7)   observation rows: row 0 is the reset observation, row t + 1 the observation
   temporal_edges  (T + 1, E, 1, 2)   after step t (the new episode's first one where `done[t]`)
   spatial_edges   (T + 1, E, N, 2)
-  actions         (T, E, 2)          the controller's action of step t
+  actions         (T, E, 2)          the controller's action of step t (with --noise-sigma: the clean label)
+  executed        (T, E, 2)          with --noise-sigma only: the perturbed action the step took
   reward, done, event  (T, E)        of step t
   pairing         'obs[t] -> actions[t]'
 
 i.e. with the reset observation stored in front, the imitation pair of step t is (observation row t, actions row
 t): the action was computed from the state that observation shows (in cn_rollout's own row numbering, where row -1
 is the reset observation: obs[t-1] -> actions[t]). The controller reads the engine's state, not the float32
-observation: its belief of the humans (the spatial edges) and its own full state. A behaviour-cloning trainer is
-not part of the project.
+observation: its belief of the humans (the spatial edges) and its own full state. learner.BehaviourCloning trains on
+the same rollouts straight from the device buffers (tools/imitation_pretrain.py); this file is for other consumers.
+
+--noise-sigma S (m/s) injects noise: the steps take actions + S * uniform[-1, 1) per component (cn_rollout_noisy, seed
+--noise-seed), the labels stay clean; the chunks continue one noise sequence (step0 = steps done so far).
 
 Usage: python tools/expert_rollouts.py --out demos.npz [--robot orca] [--envs 256] [--steps 512] [--humans 5]
-                                       [--seed 0] [--chunk-steps 128]
+                                       [--seed 0] [--chunk-steps 128] [--noise-sigma S] [--noise-seed K]
 """
 import argparse
 import os
@@ -47,6 +51,8 @@ def main():
     ap.add_argument("--humans", type=int, default=5)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--chunk-steps", type=int, default=128, help="steps per rollout call (bounds the device buffers)")
+    ap.add_argument("--noise-sigma", type=float, default=None, help="perturb the executed action (labels stay clean)")
+    ap.add_argument("--noise-seed", type=int, default=0)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("expert_rollouts: needs a GPU")
@@ -58,19 +64,25 @@ def main():
     robot = ScriptedRobot(envs, args.robot)
     obs0 = envs.reset()
     rows = {k: [obs0[k].reshape((1,) + tuple(obs0[k].shape)).cpu().numpy()] for k in OBS}
-    rows.update({k: [] for k in STEP})
+    step_keys = STEP + (("executed",) if args.noise_sigma is not None else ())
+    rows.update({k: [] for k in step_keys})
     launches, t = 0, 0
     while t < T:
         n = min(args.chunk_steps, T - t)
-        out = robot.rollout(n)
+        if args.noise_sigma is None:
+            out = robot.rollout(n)
+        else:
+            out = robot.rollout(n, noise={"sigma": args.noise_sigma, "seed": args.noise_seed, "step0": t})
         launches += out["num_launches"]
         torch.cuda.synchronize()
-        for k in OBS + STEP:
+        for k in OBS + step_keys:
             rows[k].append(out[k].cpu().numpy())
         t += n
     data = {k: np.concatenate(v, axis=0) for k, v in rows.items()}
     data["pairing"] = np.array("obs[t] -> actions[t]")
     data["robot"] = np.array(args.robot)
+    if args.noise_sigma is not None:
+        data["noise_sigma"], data["noise_seed"] = np.array(args.noise_sigma), np.array(args.noise_seed)
     np.savez_compressed(args.out, **data)
     print("%s: %d envs x %d steps of %r, %d episodes ended, %d kernel launches"
           % (args.out, E, T, args.robot, int(data["done"].sum()), launches))

@@ -1,0 +1,138 @@
+#!/usr/bin/env python
+"""Behaviour-cloning pre-training of the DSRNN policy from a scripted expert, with the evaluation rows next to it.
+
+For every --sigma-frac f (the noise half-width as a fraction of robot.v_pref; 0 = plain behaviour cloning) a fresh
+DSRNN policy (same initial weights) is cloned from the expert for --updates chunks with learner.BehaviourCloning
+(noise-injected expert rollouts, labels clean) and then run through evaluate() on the default test set
+(--test-size episodes, the four default test scenarios). The untrained policy and the expert itself
+(evaluate_scripted) are evaluated the same way. One JSON line per row: success / collision / timeout rates, updates,
+env steps, the last update's losses and the wall time of the training. --out saves the state_dict of the LAST
+sigma's policy (keys as the reference checkpoints'), ready for RolloutTrainer / train.py to continue with PPO.
+Needs a GPU.
+
+Usage: python tools/imitation_pretrain.py [--expert orca] [--updates 3000] [--envs 1024] [--steps 32] [--epochs 1]
+           [--mini-batch 2] [--lr 1e-3] [--value-coef 0.5] [--sigma-frac 0 0.1 0.3] [--humans 5] [--seed 0]
+           [--eval-envs 100] [--test-size 500] [--out policy.pt] [--json FILE]
+"""
+import argparse
+import json
+import logging
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import torch  # noqa: E402
+
+from crowdnav_dsrnn_amd.config import Config, clone_config  # noqa: E402
+from crowdnav_dsrnn_amd.envs import CrowdNavVecEnv  # noqa: E402
+from crowdnav_dsrnn_amd.evaluation import evaluate, evaluate_scripted  # noqa: E402
+from crowdnav_dsrnn_amd.learner import BehaviourCloning  # noqa: E402
+from crowdnav_dsrnn_amd.policy import Policy  # noqa: E402
+from crowdnav_dsrnn_amd.policy_factory import ScriptedRobot  # noqa: E402
+
+DEV = "cuda:0"
+
+
+def rates(row):
+    last = evaluate.last
+    row.update({"success_rate": round(last["success_rate"], 3), "collision_rate": round(last["collision_rate"], 3),
+                "timeout_rate": round(last["timeout_rate"], 3)})
+    return row
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--expert", default="orca", choices=ScriptedRobot.NAMES)
+    ap.add_argument("--updates", type=int, default=3000)
+    ap.add_argument("--envs", type=int, default=1024)
+    ap.add_argument("--steps", type=int, default=32)
+    ap.add_argument("--epochs", type=int, default=1)
+    ap.add_argument("--mini-batch", type=int, default=2)
+    ap.add_argument("--lr", type=float, default=1e-3)
+    ap.add_argument("--value-coef", type=float, default=0.5)
+    ap.add_argument("--sigma-frac", type=float, nargs="+", default=[0.0, 0.1, 0.3])
+    ap.add_argument("--humans", type=int, default=5)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--eval-envs", type=int, default=100)
+    ap.add_argument("--test-size", type=int, default=500)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--json", default=None)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("imitation_pretrain: needs a GPU")
+    log = logging.getLogger("imitation_pretrain")
+    log.addHandler(logging.NullHandler())
+    log.propagate = False
+    c = clone_config(Config())
+    c.sim.human_num = args.humans
+    c.action_space.kinematics = "holonomic"
+    c.env.test_size = args.test_size
+    c.training.num_processes = args.envs
+    c.ppo.num_steps = args.steps
+    c.ppo.num_mini_batch = args.mini_batch
+    E, EE = args.envs, args.eval_envs
+    lines = []
+
+    def emit(row):
+        lines.append(json.dumps(row))
+        print(lines[-1], flush=True)
+
+    def test_envs():
+        return CrowdNavVecEnv(c, EE, c.env.seed, DEV, allow_early_resets=True, nenv=EE, phase="test")
+
+    def evaluate_policy(pol):
+        envs = test_envs()
+        keep = pol.base.nenv
+        pol.base.nenv = EE
+        try:
+            evaluate(pol, None, envs, EE, DEV, c, log, keep_traces=False, verbose=False)
+        finally:
+            pol.base.nenv = keep
+            envs.close()
+
+    def fresh_policy(spaces, action_space):
+        torch.manual_seed(args.seed)
+        return Policy(spaces, action_space, base="srnn", base_kwargs=c).to(DEV)
+
+    envs = test_envs()
+    evaluate_scripted(args.expert, envs, EE, DEV, c, log, keep_traces=False, verbose=False)
+    emit(rates({"row": "expert", "expert": args.expert, "episodes": args.test_size}))
+    spaces, action_space = envs.observation_space.spaces, envs.action_space
+    envs.close()
+    pol = fresh_policy(spaces, action_space)
+    evaluate_policy(pol)
+    emit(rates({"row": "untrained", "episodes": args.test_size}))
+    for frac in args.sigma_frac:
+        pol = fresh_policy(spaces, action_space)
+        envs = CrowdNavVecEnv(c, E, args.seed, DEV, allow_early_resets=True, nenv=E, phase="train")
+        bc = BehaviourCloning(c, envs, pol, expert=args.expert, sigma=frac * float(c.robot.v_pref), seed=args.seed,
+                              epochs=args.epochs, lr=args.lr, value_coef=args.value_coef)
+        torch.cuda.synchronize()
+        t0 = time.time()
+        gpu_roll = gpu_upd = 0.0
+        first = st = None
+        for _ in range(args.updates):
+            st = bc.update()
+            first = first or st
+            gpu_roll += st["rollout_s"]
+            gpu_upd += st["update_s"]
+        wall = time.time() - t0
+        envs.close()
+        evaluate_policy(pol)
+        emit(rates({"row": "bc", "expert": args.expert, "sigma_frac": frac, "sigma": frac * float(c.robot.v_pref),
+                    "updates": args.updates, "envs": E, "steps": args.steps, "epochs": args.epochs, "lr": args.lr,
+                    "env_steps": bc.env_steps, "nll_first": round(first["nll"], 4), "nll_last": round(st["nll"], 4),
+                    "value_loss_last": round(st["value_loss"], 4), "train_wall_s": round(wall, 2),
+                    "rollout_gpu_s": round(gpu_roll, 3), "update_gpu_s": round(gpu_upd, 3),
+                    "episodes": args.test_size}))
+    if args.out:
+        torch.save(pol.state_dict(), args.out)
+    if args.json:
+        with open(args.json, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()

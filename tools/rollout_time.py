@@ -2,15 +2,18 @@
 """HIP-event timings of closed-loop scripted rollouts (cn_rollout) against the launch pairs they replace.
 
 Per configuration (4096 envs, T = 256 steps, holonomic, ORCA humans): (a) 5 humans, ORCA robot; (b) 9 humans, ORCA
-robot; (c) 10 humans, social-force robot. Three paths over the same T steps, every step recorded:
+robot; (c) 10 humans, social-force robot; (d) 5 humans, social-force robot. Three paths over the same T steps, every
+step recorded:
   fused         cn_rollout at the default chunk: the controller inside the multi-step launches
   native_pairs  cn_rollout at chunk 1: cn_robot_act + cn_step launch pairs issued from native code
   python_pairs  the Python loop of robot_act() + step() (what the library offered before cn_rollout; its outputs are
                 not kept per step, so it does strictly less)
 between two events on the current stream after one warm-up rollout, three alternating rounds; the median round
 is reported (us per step) with the rounds' spread. Needs a GPU; prints one JSON line per configuration.
+--noise-sigma S runs the two cn_rollout paths through cn_rollout_noisy with that sigma (0: its cn_rollout path plus the
+copy into `executed`); the Python loop stays the clean one.
 
-Usage: python tools/rollout_time.py [--envs 4096] [--steps 256] [--out FILE]
+Usage: python tools/rollout_time.py [--envs 4096] [--steps 256] [--noise-sigma S] [--out FILE]
 """
 import argparse
 import json
@@ -39,13 +42,16 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=4096)
     ap.add_argument("--steps", type=int, default=256)
+    ap.add_argument("--noise-sigma", type=float, default=None)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("rollout_time: needs a GPU")
     E, T = args.envs, args.steps
     lines = []
-    for tag, N, name in (("a", 5, "orca"), ("b", 9, "orca"), ("c", 10, "social_force")):
+    noise = None if args.noise_sigma is None else {"sigma": args.noise_sigma, "seed": 1, "step0": 0}
+    kw = {} if noise is None else {"noise": noise}
+    for tag, N, name in (("a", 5, "orca"), ("b", 9, "orca"), ("c", 10, "social_force"), ("d", 5, "social_force")):
         c = clone_config(Config())
         c.sim.human_num = N
         c.action_space.kinematics = "holonomic"
@@ -54,16 +60,16 @@ def main():
         chunk = eng.seq_chunk
         eng.reset()
         eng.step(eng.robot_act(name))   # (the first step after cn_reset is a pair on every path)
-        buf = eng.rollout_buffers(T)
+        buf = eng.rollout_buffers(T, **({} if noise is None else {"executed": True}))
         launches = {}
 
         def fused():
             eng.set_seq_chunk(chunk)
-            launches["fused"] = eng.rollout(name, T, out=buf)["num_launches"]
+            launches["fused"] = eng.rollout(name, T, out=buf, **kw)["num_launches"]
 
         def native_pairs():
             eng.set_seq_chunk(1)
-            launches["native_pairs"] = eng.rollout(name, T, out=buf)["num_launches"]
+            launches["native_pairs"] = eng.rollout(name, T, out=buf, **kw)["num_launches"]
 
         def python_pairs():
             for _ in range(T):
@@ -76,6 +82,7 @@ def main():
             for k, fn in fns.items():
                 rounds[k].append(timed(fn, T))
         rec = {"config": tag, "envs": E, "humans": N, "robot": name, "steps": T, "chunk": chunk,
+               "noise_sigma": args.noise_sigma,
                "unit": "us per step (HIP events)", "device": torch.cuda.get_device_name(0), "launches": launches}
         for k, v in rounds.items():
             v = sorted(v)
