@@ -2603,6 +2603,60 @@ struct RolloutNoise {
 #define CN_ROLLOUT_NOISY (1ll << 16)
 #define CN_ROLLOUT_K_SHIFT 17
 
+// The engine's device block of a cn_rollout_lidar call (behind the RolloutNoise block: work_count + CN_ROWS_W),
+// written on the stream before the call's fused launches. The state rows are field-major over the call's `rows`
+// steps: robot_state [9][rows][E] (r_px, r_py, r_vx, r_vy, r_radius, r_gx, r_gy, r_vpref, r_theta), human_state
+// [3][rows][E][N] (h_px, h_py, h_r) -- the twelve fields cn_lidar_scan_kernel reads, so a cn_state_ptrs aimed into
+// them makes the scan run over rows * E "envs". `actions` is the call's row 0: a launch finds its row from its own.
+struct RolloutRows {
+    double *robot_state;
+    double *human_state;
+    const float *actions;
+    int64_t rows;
+};
+#define CN_ROWS_W 22   // in uint32 words from work_count
+
+// field f of the state rows: its array in the blob
+__device__ __forceinline__ const double *state_row_robot_field(const cn_state_ptrs &S, int f)
+{
+    switch (f) {
+    case 0: return S.r_px;
+    case 1: return S.r_py;
+    case 2: return S.r_vx;
+    case 3: return S.r_vy;
+    case 4: return S.r_radius;
+    case 5: return S.r_gx;
+    case 6: return S.r_gy;
+    case 7: return S.r_vpref;
+    default: return S.r_theta;
+    }
+}
+__device__ __forceinline__ const double *state_row_human_field(const cn_state_ptrs &S, int f)
+{
+    return f == 0 ? S.h_px : (f == 1 ? S.h_py : S.h_r);
+}
+
+// The blob's twelve fields of envs [e0, e0 + ne) copied to row `row_e / E` of the state rows (bits, no arithmetic), by
+// thread k of nthr. Shared by cn_state_rows_kernel and cn_step_kernel's recording rollout variant.
+__device__ __forceinline__ void state_rows_copy(const cn_state_ptrs &S, const RolloutRows &R, int64_t E, int N,
+                                                int64_t row_e, int e0, int ne, int k, int nthr)
+{
+    const int64_t RE = R.rows * E, d0 = row_e + e0;   // row_e: the row's first env, row * E
+#pragma unroll
+    for (int f = 0; f < 9; ++f) {
+        const double *const src = state_row_robot_field(S, f) + e0;
+        double *const dst = R.robot_state + (f * RE + d0);
+        for (int q = k; q < ne; q += nthr) dst[q] = src[q];
+    }
+    const int nh = ne * N;
+#pragma unroll
+    for (int f = 0; f < 3; ++f) {
+        const double *const src = state_row_human_field(S, f) + (int64_t)e0 * N;
+        double *const dst = R.human_state + (f * RE + d0) * N;
+        for (int q = k; q < nh; q += nthr) dst[q] = src[q];
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // kernel A
 // ------------------------------------------------------------------------------------------------
@@ -2703,7 +2757,12 @@ __device__ inline float bbox_dist(float x, float y, float mnx, float mxx, float 
 // otherwise the launch's last step stores it to a single row, as the SEQ kernels do). A launch of cn_rollout_noisy
 // (CN_ROLLOUT_NOISY in g.rollout, wave-uniform) perturbs the action on its way into LDS (rollout_noise, parameters
 // from the engine's RolloutNoise block): row `step` of g.actions keeps the clean one, `executed` gets the perturbed.
-template <bool KD, bool PHX, bool MIX, bool DEVSEQ = false, bool SEQ = false, bool ROBOT = false>
+// REC (ROBOT only): a launch of cn_rollout_lidar, which also records the state every step leaves (the twelve fields
+// of the engine's RolloutRows block). While wave 0 runs the controller of step s >= 1, waves 1-3 copy the state
+// step s - 1 left in global memory to its row; the launch's last step copies its own after its closing barrier.
+// (The state before a launch's step 0 is the previous launch's last row.) A flag of its own, so that cn_rollout's
+// kernels stay what they were.
+template <bool KD, bool PHX, bool MIX, bool DEVSEQ = false, bool SEQ = false, bool ROBOT = false, bool REC = false>
 __global__ void __launch_bounds__(CN_BLK, 3) cn_step_kernel(StepArgs g, cn_config c)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -2921,6 +2980,11 @@ __global__ void __launch_bounds__(CN_BLK, 3) cn_step_kernel(StepArgs g, cn_confi
                         sl.act[q] = rx; sl.act[EPB + q] = ry;
                     }
                 }
+            }
+        } else if constexpr (REC) {
+            if (step > 0) {   // (actions - rr.actions = row * 2 E: the row's first env without a division)
+                const RolloutRows rr = *(const RolloutRows *)(g.pend.stats + (CN_ROWS_W - 8));
+                state_rows_copy(S, rr, g.E, N, (actions - rr.actions) / 2 - g.E, e0, nenv_here, tid - 64, CN_BLK - 64);
             }
         }
         __syncthreads();
@@ -3885,6 +3949,12 @@ __global__ void __launch_bounds__(CN_BLK, 3) cn_step_kernel(StepArgs g, cn_confi
     // the next step's phase 0 reads the state (and the RNG streams) this step's resets and goal changes wrote
     // through other waves, and rewrites the LDS their RNG regions and agent tables use
     if constexpr (SEQ) __syncthreads();
+    if constexpr (REC) {
+        if (step == g.nsteps - 1) {
+            const RolloutRows rr = *(const RolloutRows *)(g.pend.stats + (CN_ROWS_W - 8));
+            state_rows_copy(S, rr, g.E, N, (actions - rr.actions) / 2, e0, nenv_here, tid, CN_BLK);
+        }
+    }
     } while (SEQ && ++step < g.nsteps);
 #ifdef CN_STAMPS
     __syncthreads();

@@ -1,8 +1,8 @@
 // aux_kernels.h -- the small stand-alone kernels: the debug / predictor kernels that expose the step kernel's
 // device functions on caller-given inputs (cn_disc_quad, cn_copy64, cn_orca, cn_orca_kd with RVO2's sequential
 // KdTree, cn_sf_predict), cn_robot_act's three kernels, cn_rollout_noisy's (cn_action_noise_kernel,
-// cn_noise_set_kernel, cn_copy32_kernel), and the two stream-ordered helpers of the host API (cn_ctl_set_kernel,
-// cn_keysnap_kernel). Part of cn_engine.hip's translation unit: included there after the device core, whose
+// cn_noise_set_kernel, cn_copy32_kernel), cn_rollout_lidar's (cn_rows_set_kernel, cn_state_rows_kernel), and the
+// two stream-ordered helpers of the host API (cn_ctl_set_kernel, cn_keysnap_kernel). Part of cn_engine.hip's translation unit: included there after the device core, whose
 // geometry, ORCA and scripted-robot functions these kernels call.
 #pragma once
 
@@ -354,6 +354,20 @@ __global__ void __launch_bounds__(64) cn_action_noise_kernel(const float *__rest
 __global__ void cn_noise_set_kernel(RolloutNoise *w, RolloutNoise v)
 {
     if (threadIdx.x == 0) *w = v;
+}
+
+// cn_rollout_lidar's device block for the fused launches that follow on the stream
+__global__ void cn_rows_set_kernel(RolloutRows *w, RolloutRows v)
+{
+    if (threadIdx.x == 0) *w = v;
+}
+
+// cn_rollout_lidar outside the fused launches: the state a step (a launch pair or triple) left, copied to row
+// row_e / E of the state rows. A workgroup per 64 consecutive envs, state_rows_copy as in the recording step kernel.
+__global__ void __launch_bounds__(256) cn_state_rows_kernel(cn_state_ptrs S, RolloutRows R, int E, int N, int64_t row_e)
+{
+    const int e0 = blockIdx.x * 64;
+    state_rows_copy(S, R, E, N, row_e, e0, min(64, E - e0), threadIdx.x, 256);
 }
 
 // cn_rollout_noisy at sigma == 0: `executed` is a copy of `actions` (bits, no arithmetic); n words

@@ -398,9 +398,10 @@ int cn_reset(cn_engine *g, void *stream, float *robot_node, float *temporal, flo
 // index of the spawn lists, the launch id, graph mode's hand-over); cn_profile's window counts STEPS.
 // rollout >= 0 (cn_rollout's fused launches, nsteps >= 1, same engines): StepArgs::rollout of the ROBOT kernels,
 // which compute the actions themselves and record every step at row t of the outputs (`actions` is written).
+// rec (cn_rollout_lidar's fused launches): the ROBOT kernels that record the state rows as well (RolloutRows block).
 static int step_launch(cn_engine *g, void *stream, const float *actions, int nsteps, int64_t action_stride,
                        float *robot_node, float *temporal, float *spatial, float *reward, uint8_t *done, int8_t *event,
-                       float *info, double *ep_return, int32_t *ep_len, int64_t rollout = -1)
+                       float *info, double *ep_return, int32_t *ep_len, int64_t rollout = -1, bool rec = false)
 {
     if (!g || !actions || !robot_node || !temporal || !spatial) return set_err(CN_EINVAL, "null argument");
     hipStream_t st = (hipStream_t)stream;
@@ -460,7 +461,8 @@ static int step_launch(cn_engine *g, void *stream, const float *actions, int nst
     const bool multi = nsteps > 1 || rollout >= 0;
     if (multi && (g->devseq || g->rows || g->plan.kd || a.pend.all))
         return set_err(CN_EINVAL, "multi-step launch: plain quad-path engine outside graph mode required");
-    const StepMode mode = rollout >= 0 ? STEP_ROBOT : nsteps > 1 ? STEP_SEQ : g->devseq ? STEP_DEVSEQ : STEP_SINGLE;
+    const StepMode mode = rollout >= 0 ? (rec ? STEP_ROBOT_REC : STEP_ROBOT)
+                          : nsteps > 1 ? STEP_SEQ : g->devseq ? STEP_DEVSEQ : STEP_SINGLE;
     const StepKernelFn kern = step_kernel_for(g->plan.kd, phx, g->rows != nullptr, mode);
     // (a guard only: the check above and cn_set_graph_mode's refusal of mixed engines exclude every combination
     // the table lacks, so no caller reaches this today)
@@ -672,29 +674,57 @@ int cn_lidar_obs(cn_engine *g, void *stream, const uint8_t *reset_mask, int enab
     return CN_OK;
 }
 
-int cn_lidar_scan(cn_engine *g, void *stream, int beams, double max_range, double robot_radius, float *obs)
+// cn_lidar_scan's argument check (cn_rollout_lidar's too); *npts: the samples of a beam
+static int lidar_scan_check(int beams, double max_range, const float *obs, int *npts)
 {
-    if (!g) return set_err(CN_EINVAL, "null engine");
-    if (g->ngroups) return set_err(CN_EUNSUPPORTED, "cn_lidar_scan: not on a mixed engine");
     if (beams < 2 || beams > 4096 || !(max_range > 0) || !(max_range <= 1e4) || !obs)
         return set_err(CN_EINVAL, "cn_lidar_scan: beams in [2, 4096], max_range in (0, 1e4] and obs required");
     // beam samples every 0.01 m (lidarv2.py:130-133): max_range / 0.01 of them, rounded up
     const double q = max_range / 0.01;
-    const int npts = fmod(q, 1.0) != 0.0 ? (int)q + 1 : (int)q;
-    if (npts < 2) return set_err(CN_EINVAL, "cn_lidar_scan: max_range below two 0.01 m samples");
-    // envs per workgroup: the G in [1, CN_LIDAR_G] whose G * beams beams fill whole 256-lane rounds best
+    *npts = fmod(q, 1.0) != 0.0 ? (int)q + 1 : (int)q;
+    if (*npts < 2) return set_err(CN_EINVAL, "cn_lidar_scan: max_range below two 0.01 m samples");
+    return CN_OK;
+}
+
+// The scan of `rows` state rows behind S (the engine's blob: rows = E; cn_rollout_lidar's state rows: T * E, human i
+// of row r at r * N + i) into obs [rows][7 + beams]. One launch, unless the kernel's int indices (r * N + i) would
+// overflow: then one per span of rows that fits. *launches (may be null) counts them.
+static int lidar_scan_launch(const cn_engine *g, hipStream_t st, cn_state_ptrs S, int64_t rows, int beams, int npts,
+                             double max_range, double robot_radius, float *obs, int *launches)
+{
+    // rows per workgroup: the G in [1, CN_LIDAR_G] whose G * beams beams fill whole 256-lane rounds best
     int G = 1;
     double fill = 0.0;
-    for (int k = 1; k <= CN_LIDAR_G && k <= g->E; ++k) {
+    for (int k = 1; k <= CN_LIDAR_G && k <= rows; ++k) {
         const int items = k * beams;
         const double f = (double)items / (double)(((items + 255) / 256) * 256);
         if (f > fill + 1e-9) { fill = f; G = k; }
     }
-    (void)hipGetLastError();   // a stale error of an earlier call (any library) is not this launch's
-    hipLaunchKernelGGL(cn_lidar_scan_kernel, dim3((unsigned)((g->E + G - 1) / G)), dim3(256), 0, (hipStream_t)stream,
-                       g->s, g->E, g->N, G, 0.5 * g->c.square_width, beams, npts, max_range, robot_radius, obs);
-    HIPCHK(hipGetLastError());
+    const int64_t N = g->N;
+    int64_t span = ((int64_t)0x7fffffff / (N > 0 ? N : 1) - CN_LIDAR_G) / G * G;   // (r + G) * N stays an int
+    for (int64_t r0 = 0; r0 < rows; r0 += span) {
+        const int64_t n = rows - r0 < span ? rows - r0 : span;
+        cn_state_ptrs P = S;
+        P.r_px += r0; P.r_py += r0; P.r_vx += r0; P.r_vy += r0; P.r_radius += r0; P.r_gx += r0; P.r_gy += r0;
+        P.r_vpref += r0; P.r_theta += r0;
+        P.h_px += r0 * N; P.h_py += r0 * N; P.h_r += r0 * N;
+        (void)hipGetLastError();   // a stale error of an earlier call (any library) is not this launch's
+        hipLaunchKernelGGL(cn_lidar_scan_kernel, dim3((unsigned)((n + G - 1) / G)), dim3(256), 0, st, P, (int)n, g->N, G,
+                           0.5 * g->c.square_width, beams, npts, max_range, robot_radius, obs + r0 * (7 + beams));
+        HIPCHK(hipGetLastError());
+        if (launches) *launches += 1;
+    }
     return CN_OK;
+}
+
+int cn_lidar_scan(cn_engine *g, void *stream, int beams, double max_range, double robot_radius, float *obs)
+{
+    if (!g) return set_err(CN_EINVAL, "null engine");
+    if (g->ngroups) return set_err(CN_EUNSUPPORTED, "cn_lidar_scan: not on a mixed engine");
+    int npts;
+    const int rc = lidar_scan_check(beams, max_range, obs, &npts);
+    if (rc) return rc;
+    return lidar_scan_launch(g, (hipStream_t)stream, g->s, g->E, beams, npts, max_range, robot_radius, obs, nullptr);
 }
 
 int cn_robot_act(cn_engine *g, void *stream, int policy, float *actions)
@@ -730,8 +760,12 @@ int cn_robot_act(cn_engine *g, void *stream, int policy, float *actions)
 // CN_ROLLOUT_NOISY and their first step's k in StepArgs::rollout and read the rest from the engine's RolloutNoise
 // block, written once per call on the stream before the first of them; elsewhere cn_action_noise_kernel runs between
 // the pair's two launches and the step reads the engine's scratch.
+// ld (cn_rollout_lidar; null: none): the state every step leaves goes to row t of ld's state rows -- the fused
+// launches are the recording ROBOT kernels, told where through the engine's RolloutRows block (one small launch per
+// call before the first of them); elsewhere cn_state_rows_kernel follows the step -- and one scan over the T * E rows
+// follows the last step.
 static int rollout_run(cn_engine *g, void *stream, int policy, int T, const cn_rollout_out *out,
-                       const cn_rollout_noise *nz, int32_t *num_launches)
+                       const cn_rollout_noise *nz, int32_t *num_launches, const struct cn_rollout_lidar *ld = nullptr)
 {
     if (num_launches) *num_launches = 0;
     if (!g) return set_err(CN_EINVAL, "null engine");
@@ -744,6 +778,15 @@ static int rollout_run(cn_engine *g, void *stream, int policy, int T, const cn_r
         return set_err(CN_EUNSUPPORTED, "cn_rollout: the controllers return ActionXY (holonomic engines only)");
     const int64_t E = g->E, N = g->N;
     const hipStream_t st = (hipStream_t)stream;
+    int npts = 0;
+    if (ld) {
+        if (!ld->robot_state || !ld->human_state)
+            return set_err(CN_EINVAL, "cn_rollout_lidar: lidar with obs, robot_state and human_state required");
+        const int rc = lidar_scan_check(ld->beams, ld->max_range, ld->obs, &npts);
+        if (rc) return rc;
+    }
+    const RolloutRows rows = {ld ? ld->robot_state : nullptr, ld ? ld->human_state : nullptr, out->actions, (int64_t)T};
+    bool rows_set = false;
     const bool every = (out->flags & CN_ROLLOUT_OBS_EVERY_STEP) != 0;
     // the controller fits the step workgroup: social force (a lane per env) always, ORCA on its quad path
     const bool fits = policy == CN_ROBOT_SOCIAL_FORCE || g->N + 1 <= 10;
@@ -781,7 +824,15 @@ static int rollout_run(cn_engine *g, void *stream, int policy, int T, const cn_r
                 }
                 word |= CN_ROLLOUT_NOISY | ((int64_t)k << CN_ROLLOUT_K_SHIFT);
             }
-            rc = step_launch(g, stream, act, n, 2 * E, rn, te, se, rw, dn, ev, inf, epr, epl, word);
+            if (ld && !rows_set) {
+                (void)hipGetLastError();
+                hipLaunchKernelGGL(cn_rows_set_kernel, dim3(1), dim3(64), 0, st,
+                                   (RolloutRows *)(g->work_count + CN_ROWS_W), rows);
+                HIPCHK(hipGetLastError());
+                rows_set = true;
+                nl += 1;
+            }
+            rc = step_launch(g, stream, act, n, 2 * E, rn, te, se, rw, dn, ev, inf, epr, epl, word, ld != nullptr);
             nl += 1;
         } else {
             rc = cn_robot_act(g, stream, policy, act);
@@ -798,9 +849,27 @@ static int rollout_run(cn_engine *g, void *stream, int policy, int T, const cn_r
             }
             rc = cn_step(g, stream, stepped, rn, te, se, rw, dn, ev, inf, epr, epl);
             nl += 2;
+            if (ld && !rc) {
+                (void)hipGetLastError();
+                hipLaunchKernelGGL(cn_state_rows_kernel, dim3((unsigned)((E + 63) / 64)), dim3(256), 0, st, g->s, rows,
+                                   (int)E, (int)N, t * E);
+                HIPCHK(hipGetLastError());
+                nl += 1;
+            }
         }
         if (rc) return rc;
         t += n;
+        if (num_launches) *num_launches = nl;
+    }
+    if (ld && T > 0) {   // the observations of all T * E rows: the scan over a cn_state_ptrs aimed into the state rows
+        const int64_t RE = (int64_t)T * E;
+        cn_state_ptrs P = g->s;
+        double *const r = ld->robot_state, *const h = ld->human_state;
+        P.r_px = r; P.r_py = r + RE; P.r_vx = r + 2 * RE; P.r_vy = r + 3 * RE; P.r_radius = r + 4 * RE;
+        P.r_gx = r + 5 * RE; P.r_gy = r + 6 * RE; P.r_vpref = r + 7 * RE; P.r_theta = r + 8 * RE;
+        P.h_px = h; P.h_py = h + RE * N; P.h_r = h + 2 * RE * N;
+        const int rc = lidar_scan_launch(g, st, P, RE, ld->beams, npts, ld->max_range, ld->robot_radius, ld->obs, &nl);
+        if (rc) return rc;
         if (num_launches) *num_launches = nl;
     }
     return CN_OK;
@@ -822,6 +891,27 @@ int cn_rollout_noisy(cn_engine *g, void *stream, int policy, int T, const cn_rol
     // sigma == 0: cn_rollout itself; `executed` is a copy of the actions it recorded
     const int rc = rollout_run(g, stream, policy, T, out, nullptr, num_launches);
     if (rc || !noise->executed || T == 0) return rc;
+    const int64_t n = (int64_t)T * g->E * 2;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(cn_copy32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n,
+                       (const uint32_t *)out->actions, (uint32_t *)noise->executed);
+    HIPCHK(hipGetLastError());
+    if (num_launches) *num_launches += 1;
+    return CN_OK;
+}
+
+int cn_rollout_lidar(cn_engine *g, void *stream, int policy, int T, const cn_rollout_out *out,
+                     const cn_rollout_noise *noise, const struct cn_rollout_lidar *lidar, int32_t *num_launches)
+{
+    if (num_launches) *num_launches = 0;
+    if (!g) return set_err(CN_EINVAL, "null engine");
+    if (!lidar) return set_err(CN_EINVAL, "cn_rollout_lidar: lidar required");
+    if (noise && !(noise->sigma >= 0.0f && noise->sigma <= 3.402823466e38f))   // (NaN fails both comparisons)
+        return set_err(CN_EINVAL, "cn_rollout_lidar: noise with a finite sigma >= 0 required");
+    const bool noisy = noise && noise->sigma > 0.0f;
+    const int rc = rollout_run(g, stream, policy, T, out, noisy ? noise : nullptr, num_launches, lidar);
+    if (rc || noisy || !noise || !noise->executed || T == 0) return rc;
+    // sigma == 0: cn_rollout_noisy's copy of the actions into `executed`
     const int64_t n = (int64_t)T * g->E * 2;
     (void)hipGetLastError();
     hipLaunchKernelGGL(cn_copy32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n,

@@ -10,6 +10,9 @@
 #define CN_WORK_BYTES 128
 static_assert(CN_NOISE_W * 4 + sizeof(RolloutNoise) <= CN_WORK_BYTES && (CN_NOISE_W * 4) % alignof(RolloutNoise) == 0,
               "cn_engine::work_count: the RolloutNoise block behind the 16 control words");
+static_assert(CN_ROWS_W * 4 >= CN_NOISE_W * 4 + sizeof(RolloutNoise) && CN_ROWS_W * 4 + sizeof(RolloutRows) <= CN_WORK_BYTES &&
+                  (CN_ROWS_W * 4) % alignof(RolloutRows) == 0,
+              "cn_engine::work_count: the RolloutRows block behind the RolloutNoise block");
 
 struct cn_engine {
     cn_config c;
@@ -22,7 +25,8 @@ struct cn_engine {
     uint32_t *work;       // [E]
     uint32_t *work_count; // [16]: [2..4] spawn-list counters (triple buffered), [5..7] parked-spawn counters,
                           // [8..11] spawn statistics (PendLaunch::stats), [15] inline reset draws; behind them
-                          // (word CN_NOISE_W) cn_rollout_noisy's RolloutNoise block: CN_WORK_BYTES in all
+                          // (word CN_NOISE_W) cn_rollout_noisy's RolloutNoise block and (word CN_ROWS_W)
+                          // cn_rollout_lidar's RolloutRows block: CN_WORK_BYTES in all
     float *act_x;         // [E][2] cn_rollout_noisy's launch triples: the perturbed action the step reads
     uint32_t *plist;      // [3][E + 64][4] envs whose spawn after next kernel A draws, with their counters
     uint32_t *rlist;      // [3][2E][4] spawns parked by a launch (resumed by the next); counters work_count[5..7]
@@ -105,10 +109,11 @@ static int keysnap(const cn_engine *g, hipStream_t st)
 // Every instantiation of cn_step_kernel, listed ONCE: cn_create raises the dynamic-LDS limit of each entry and
 // step_launch picks its kernel here, so a new template flag is added in this table (and STEP_KERNEL) alone.
 // Launch modes: a single step with host-passed arguments; graph mode (DEVSEQ, plain engines); a multi-step launch
-// (SEQ, plain quad-path engines); a cn_rollout launch (SEQ + ROBOT, the same engines). A combination that is not
+// (SEQ, plain quad-path engines); a cn_rollout launch (SEQ + ROBOT, the same engines) and a cn_rollout_lidar launch
+// (SEQ + ROBOT + REC: it records the state rows as well). A combination that is not
 // listed does not exist: mixed-engine groups (mix) and the kd-tree path (kd) have no SEQ / ROBOT kernel, mix none
 // for graph mode. (The entries' order is the order in which the compiler emits the kernels into the code object.)
-enum StepMode { STEP_SINGLE, STEP_DEVSEQ, STEP_SEQ, STEP_ROBOT };
+enum StepMode { STEP_SINGLE, STEP_DEVSEQ, STEP_SEQ, STEP_ROBOT, STEP_ROBOT_REC };
 typedef void (*StepKernelFn)(StepArgs, cn_config);
 struct StepKernelEntry {
     bool kd, phx, mix;
@@ -116,7 +121,9 @@ struct StepKernelEntry {
     StepKernelFn fn;
 };
 #define STEP_KERNEL(KD, PHX, MIX, MODE) \
-    {KD, PHX, MIX, MODE, cn_step_kernel<KD, PHX, MIX, MODE == STEP_DEVSEQ, MODE == STEP_SEQ || MODE == STEP_ROBOT, MODE == STEP_ROBOT>}
+    {KD, PHX, MIX, MODE,                                                                                             \
+     cn_step_kernel<KD, PHX, MIX, MODE == STEP_DEVSEQ, MODE == STEP_SEQ || MODE == STEP_ROBOT || MODE == STEP_ROBOT_REC, \
+                    MODE == STEP_ROBOT || MODE == STEP_ROBOT_REC, MODE == STEP_ROBOT_REC>}
 static const StepKernelEntry step_kernels[] = {
     STEP_KERNEL(false, false, false, STEP_SEQ),    STEP_KERNEL(false, true, false, STEP_SEQ),
     STEP_KERNEL(true, false, false, STEP_SINGLE),  STEP_KERNEL(false, false, false, STEP_SINGLE),
@@ -125,7 +132,8 @@ static const StepKernelEntry step_kernels[] = {
     STEP_KERNEL(true, true, true, STEP_SINGLE),    STEP_KERNEL(false, true, true, STEP_SINGLE),
     STEP_KERNEL(false, false, false, STEP_DEVSEQ), STEP_KERNEL(false, true, false, STEP_DEVSEQ),
     STEP_KERNEL(true, false, false, STEP_DEVSEQ),  STEP_KERNEL(true, true, false, STEP_DEVSEQ),
-    STEP_KERNEL(false, false, false, STEP_ROBOT),  STEP_KERNEL(false, true, false, STEP_ROBOT)};
+    STEP_KERNEL(false, false, false, STEP_ROBOT),  STEP_KERNEL(false, true, false, STEP_ROBOT),
+    STEP_KERNEL(false, false, false, STEP_ROBOT_REC), STEP_KERNEL(false, true, false, STEP_ROBOT_REC)};
 #undef STEP_KERNEL
 
 // the kernel of a launch, or null where the combination does not exist

@@ -229,13 +229,27 @@ class CrowdNavEngine:
             _lib.check(_lib.lib().cn_robot_act(self._h, self._stream(), self.ROBOT_POLICIES[policy], out.data_ptr()))
         return out
 
-    def rollout_buffers(self, T, obs_every_step=True, executed=False):
+    @staticmethod
+    def _lidar_args(lidar):
+        """(beams, max_range, robot_radius) of rollout's `lidar` (a dict with those keys)."""
+        try:
+            return int(lidar["beams"]), float(lidar["max_range"]), float(lidar["robot_radius"])
+        except (KeyError, TypeError):
+            raise ValueError("rollout: lidar must be a dict with beams, max_range and robot_radius")
+
+    def rollout_buffers(self, T, obs_every_step=True, executed=False, lidar=None):
         """Fresh device tensors for rollout(T): the `out` dict without 'num_launches' (executed=True: with the
-        'executed' rows of a rollout with noise)."""
+        'executed' rows of a rollout with noise; lidar=dict(beams=, ..): with the 'lidar' rows and the state rows
+        of a rollout with lidar)."""
         t, E, N, dev = self.torch, self.E, self.N, self.device
         out = {"actions": t.zeros((T, E, 2), dtype=t.float32, device=dev)}
         if executed:
             out["executed"] = t.zeros((T, E, 2), dtype=t.float32, device=dev)
+        if lidar is not None:
+            beams = self._lidar_args(lidar)[0]
+            out["lidar"] = t.zeros((T, E, 1, 7 + beams), dtype=t.float32, device=dev)
+            out["robot_state"] = t.zeros((9, T, E), dtype=t.float64, device=dev)
+            out["human_state"] = t.zeros((3, T, E, N), dtype=t.float64, device=dev)
         if obs_every_step:
             out["robot_node"] = t.zeros((T, E, 1, 7), dtype=t.float32, device=dev)
             out["temporal_edges"] = t.zeros((T, E, 1, 2), dtype=t.float32, device=dev)
@@ -252,7 +266,7 @@ class CrowdNavEngine:
 
     _ROLLOUT_OPTIONAL = ("reward", "done", "event", "info", "ep_return", "ep_len")
 
-    def rollout(self, policy, T, obs_every_step=True, out=None, noise=None):
+    def rollout(self, policy, T, obs_every_step=True, out=None, noise=None, lidar=None):
         """T closed-loop steps of the scripted robot (cn_rollout): robot_act(policy) -> step, every step recorded,
         with the rows of that eager loop bit for bit. Returns a dict of device tensors: actions (T, E, 2);
         robot_node / temporal_edges / spatial_edges (T, E, ...) = the observation AFTER step t (with
@@ -264,7 +278,12 @@ class CrowdNavEngine:
         noise (a RolloutNoise or a dict with sigma / seed / step0; None: cn_rollout as ever) -> cn_rollout_noisy: the
         step takes actions + sigma * n with n uniform in [-1, 1) per component, drawn per (seed, global env index,
         step0 + t); 'actions' keeps the clean labels and the dict gains 'executed' (T, E, 2), what the step took
-        (allocated when `out` lacks it)."""
+        (allocated when `out` lacks it).
+        lidar (dict(beams=, max_range=, robot_radius=), lidar_scan's; None: none) -> cn_rollout_lidar: the dict gains
+        'lidar' (T, E, 1, 7 + beams) f32, the live ConvGRU observation AFTER step t (what lidar_scan writes right
+        after that step), and the state it was scanned from, 'robot_state' (9, T, E) and 'human_state' (3, T, E, N)
+        f64 (r_px, r_py, r_vx, r_vy, r_radius, r_gx, r_gy, r_vpref, r_theta; h_px, h_py, h_r). Each is taken from
+        `out` when given (a trainer aims 'lidar' at its storage) and allocated otherwise."""
         t = self.torch
         if policy not in self.ROBOT_POLICIES:
             raise ValueError("rollout: policy %r (one of %s)" % (policy, sorted(self.ROBOT_POLICIES)))
@@ -279,6 +298,23 @@ class CrowdNavEngine:
             out = dict(out)
             if noise is not None and out.get("executed") is None:
                 out["executed"] = t.zeros((T, E, 2), dtype=t.float32, device=self.device)
+        rl = None
+        if lidar is not None:
+            beams, max_range, robot_radius = self._lidar_args(lidar)
+            if not (2 <= beams <= 4096 and 0 < max_range <= 1e4):
+                raise ValueError("rollout: lidar beams in [2, 4096] and max_range in (0, 1e4] required")
+            lwant = {"lidar": ((T, E, 1, 7 + beams), t.float32), "robot_state": ((9, T, E), t.float64),
+                     "human_state": ((3, T, E, N), t.float64)}
+            for k, (shape, dt) in lwant.items():
+                v = out.get(k)
+                if v is None:
+                    v = out[k] = t.zeros(shape, dtype=dt, device=self.device)
+                n = int(np.prod(shape))
+                if v.dtype != dt or v.device != self.device or not v.is_contiguous() or v.numel() != n:
+                    raise ValueError("rollout: out[%r] must be a contiguous %s tensor of %d elements on %s"
+                                     % (k, dt, n, self.device))
+            rl = _lib.RolloutLidar(out["lidar"].data_ptr(), beams, max_range, robot_radius,
+                                   out["robot_state"].data_ptr(), out["human_state"].data_ptr())
         R = 1 if not obs_every_step else T
         want = {"actions": (T * E * 2, t.float32), "robot_node": (R * E * 7, t.float32),
                 "temporal_edges": (R * E * 2, t.float32), "spatial_edges": (R * E * N * 2, t.float32),
@@ -305,12 +341,18 @@ class CrowdNavEngine:
         if T == 0:   # (empty tensors have no address to pass; cn_rollout launches nothing for T = 0 either)
             out["num_launches"] = 0
             return out
+        nz = None
+        if noise is not None:
+            nz = _lib.RolloutNoise(noise.sigma, noise.seed & 0xFFFFFFFF, noise.step0, out["executed"].data_ptr())
         with t.cuda.device(self.device):
-            if noise is None:
+            if rl is not None:
+                _lib.check(_lib.lib().cn_rollout_lidar(self._h, self._stream(), self.ROBOT_POLICIES[policy], T,
+                                                       ctypes.byref(ro), None if nz is None else ctypes.byref(nz),
+                                                       ctypes.byref(rl), ctypes.byref(nl)))
+            elif noise is None:
                 _lib.check(_lib.lib().cn_rollout(self._h, self._stream(), self.ROBOT_POLICIES[policy], T,
                                                  ctypes.byref(ro), ctypes.byref(nl)))
             else:
-                nz = _lib.RolloutNoise(noise.sigma, noise.seed & 0xFFFFFFFF, noise.step0, out["executed"].data_ptr())
                 _lib.check(_lib.lib().cn_rollout_noisy(self._h, self._stream(), self.ROBOT_POLICIES[policy], T,
                                                        ctypes.byref(ro), ctypes.byref(nz), ctypes.byref(nl)))
         out["num_launches"] = int(nl.value)

@@ -324,14 +324,25 @@ class CrowdNavVecEnv:
     def rollout(self, policy, T, obs_every_step=True, out=None, noise=None):
         """T closed-loop steps of the scripted robot ('orca' / 'social_force') from the state the last reset / step
         left, every step recorded (CrowdNavEngine.rollout: a dict of (T, E, ...) tensors on the engine's GPU, no
-        host synchronisation). The recorded observation is the SRNN one, so obs_mode 'srnn' only. `noise`: the
-        engine's RolloutNoise (or a dict) -- the steps take perturbed actions, 'actions' keeps the clean labels and
-        'executed' holds what was taken."""
-        if self.obs_mode != "srnn":
-            raise UnsupportedConfig("rollout: obs_mode=%r (the rollout records the 'srnn' observation only)"
-                                    % self.obs_mode)
+        host synchronisation). `noise`: the engine's RolloutNoise (or a dict) -- the steps take perturbed actions,
+        'actions' keeps the clean labels and 'executed' holds what was taken.
+        obs_mode 'convgru' with lidar.live: the dict also holds 'lidar' (T, E, 1, 7 + beams), the observation
+        step_device would have returned after every step, and the state rows it was scanned from (the engine's
+        rollout with the env's LiDAR settings). Without lidar.live the observation carries the scan held since the
+        episode's reset, which is state between steps and no function of a recorded row: UnsupportedConfig."""
+        lidar = None
+        if self.obs_mode == "convgru":
+            if not self._lidar_live:
+                raise UnsupportedConfig("rollout: obs_mode='convgru' needs config.lidar.live (the held per-episode "
+                                        "scan of the parity mode is not a function of the recorded state)")
+            c = self._lidar_cfg
+            lidar = dict(beams=c["beams"], max_range=c["max_range"], robot_radius=c["robot_radius"])
+        elif self.obs_mode != "srnn":
+            raise UnsupportedConfig("rollout: obs_mode=%r" % self.obs_mode)
         self._state_cache = None
-        return self.engine.rollout(policy, T, obs_every_step=obs_every_step, out=out, noise=noise)
+        if lidar is None:
+            return self.engine.rollout(policy, T, obs_every_step=obs_every_step, out=out, noise=noise)
+        return self.engine.rollout(policy, T, obs_every_step=obs_every_step, out=out, noise=noise, lidar=lidar)
 
     def _state(self):
         if self._state_cache is None:

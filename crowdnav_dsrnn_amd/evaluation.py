@@ -261,9 +261,16 @@ def evaluate(actor_critic, ob_rms, eval_envs, num_processes, device, config, log
     dist = _dist()
     cn = eval_envs.cn_cfg
     rnn_factor = 2 if recurrent_type == "LSTM" else 1
-    hxs = {"human_node_rnn": torch.zeros(E, 1, config.SRNN.human_node_rnn_size * rnn_factor, device=device),
-           "human_human_edge_rnn": torch.zeros(E, actor_critic.base.human_num + 1,
-                                               config.SRNN.human_human_edge_rnn_size * rnn_factor, device=device)}
+    # a 'convgru' env: the policy reads the LiDAR row and carries one (E, H) state; the recorder reads the robot's
+    # position and heading from the engine's own SRNN observation of the same step
+    convgru = getattr(eval_envs, "obs_mode", "srnn") == "convgru"
+    rec_obs = (lambda o: eval_envs.engine.obs()) if convgru else (lambda o: o)
+    if convgru:
+        hxs = torch.zeros(E, actor_critic.base.recurrent_hidden_state_size, device=device)
+    else:
+        hxs = {"human_node_rnn": torch.zeros(E, 1, config.SRNN.human_node_rnn_size * rnn_factor, device=device),
+               "human_human_edge_rnn": torch.zeros(E, actor_critic.base.human_num + 1,
+                                                   config.SRNN.human_human_edge_rnn_size * rnn_factor, device=device)}
     masks = torch.zeros(E, 1, device=device)
     test_size = int(config.env.test_size)
     side = bool(config.test.side_preference)
@@ -276,7 +283,7 @@ def evaluate(actor_critic, ob_rms, eval_envs, num_processes, device, config, log
     rec = EpisodeRecorder(E, test_size, int(cn.env_offset), int(cn.nenv), eval_envs.engine.device, dt, gamma,
                           float(config.robot.v_pref), side, scenario, eval_envs.scenario_names, keep_traces)
     obs = eval_envs.reset()
-    rec.start(obs)
+    rec.start(rec_obs(obs))
     n = 0
     while True:
         with torch.no_grad():
@@ -284,7 +291,7 @@ def evaluate(actor_critic, ob_rms, eval_envs, num_processes, device, config, log
         if visualize:
             eval_envs.render()
         obs, reward, done, event, info, _, _ = eval_envs.step_device(action)
-        rec.step(obs, reward, done, event, info)
+        rec.step(rec_obs(obs), reward, done, event, info)
         masks = (1.0 - done.float()).unsqueeze(1).to(device)
         n += 1
         if n % check_every == 0 and rec.finished():
@@ -307,14 +314,10 @@ def evaluate_scripted(name, eval_envs, num_processes, device, config, logging, c
     not change the records: they equal evaluate(ScriptedRobot(eval_envs, name), ...)'s.
     `noise` (engine.RolloutNoise or a dict with sigma / seed / step0): the controller's executed actions are perturbed
     (ScriptedRobot.rollout's noise; the chunks continue step0), i.e. the report is the noisy expert's."""
-    from .config import UnsupportedConfig
     from .engine import RolloutNoise
     from .policy_factory import ScriptedRobot
 
-    ScriptedRobot.check(eval_envs, name)
-    if getattr(eval_envs, "obs_mode", "srnn") != "srnn":
-        raise UnsupportedConfig("evaluate_scripted: obs_mode=%r (the rollout records the 'srnn' observation only)"
-                                % eval_envs.obs_mode)
+    ScriptedRobot.check_rollout(eval_envs, name)   # (a 'convgru' env: with lidar.live only, as the rollout)
     E = eval_envs.num_envs
     if num_processes != E:
         raise ValueError("num_processes=%d but the VecEnv holds %d envs" % (num_processes, E))
@@ -336,6 +339,8 @@ def evaluate_scripted(name, eval_envs, num_processes, device, config, logging, c
         raise ValueError("evaluate_scripted: chunk >= 1 required, got %d" % C)
     noise = RolloutNoise.of(noise)
     obs = eval_envs.reset()
+    if getattr(eval_envs, "obs_mode", "srnn") == "convgru":   # (the recorder reads the SRNN observation of that state)
+        obs = eval_envs.engine.obs()
     rec.start(obs)
     buf = None
     done_steps = 0

@@ -1,4 +1,5 @@
-"""Device-resident behaviour cloning of a scripted robot (ORCA / social force) into the DSRNN policy.
+"""Device-resident behaviour cloning of a scripted robot (ORCA / social force) into the DSRNN policy, or into the
+ConvGRU policy on a live-LiDAR env (robot.policy 'convgru' with lidar.live).
 
     bc = BehaviourCloning(config, envs, actor_critic, expert="orca", sigma=0.1)
     stats = bc.update()      # one expert chunk of num_steps steps of every env + `epochs` passes over it
@@ -12,6 +13,10 @@ stays the clean expert action (noise injection in the style of DART, Laskey et a
 a perturbed policy reaches, labelled with what the expert does there. The loss is the negative log-likelihood of the
 label under the policy's Gaussian plus, optionally, a value regression onto the expert's discounted returns, over
 the minibatches PPO.update walks (env subsets, whole sequences, the recurrent state of the chunk's start).
+
+The ConvGRU policy sees 180 ranges where the expert sees every human's state. Its chunks come from the same rollout
+with the LiDAR rows recorded as well (cn_rollout_lidar) straight into a RolloutStorage; labels, noise, masks, returns,
+the carried recurrent state, fit() and update() are the DSRNN branch's.
 """
 import contextlib
 import time
@@ -21,7 +26,7 @@ import torch.nn as nn
 import torch.optim as optim
 
 from ..engine import RolloutNoise
-from .storage import SRNNRolloutStorage
+from .storage import RolloutStorage, SRNNRolloutStorage
 
 EVENT_COLLISION, EVENT_SUCCESS, EVENT_TIMEOUT = 2, 3, 4   # cn_step's event codes of an episode's end
 
@@ -33,8 +38,16 @@ class BehaviourCloning:
         from ..policy_factory import ScriptedRobot
 
         ScriptedRobot.check(envs, expert)   # unknown controller / unicycle: before anything touches the GPU
-        if getattr(envs, "obs_mode", "srnn") != "srnn" or not getattr(actor_critic, "srnn", False):
-            raise UnsupportedConfig("BehaviourCloning: the DSRNN policy (base='srnn') on the 'srnn' observation only")
+        mode = getattr(envs, "obs_mode", "srnn")
+        self.convgru = mode == "convgru"
+        if self.convgru:
+            lc = config.lidar
+            if not getattr(actor_critic, "convgru", False) or not (getattr(lc, "live", False) and lc.enable):
+                raise UnsupportedConfig("BehaviourCloning: a 'convgru' env needs the ConvGRU policy (base='convgru') "
+                                        "and config.lidar.live (the rollout records the live scan only)")
+        elif mode != "srnn" or not getattr(actor_critic, "srnn", False):
+            raise UnsupportedConfig("BehaviourCloning: the DSRNN policy (base='srnn') on the 'srnn' observation, or the "
+                                    "ConvGRU policy (base='convgru') on a live 'convgru' one")
         self.config = config
         self.envs = envs
         self.ac = actor_critic
@@ -53,13 +66,28 @@ class BehaviourCloning:
                                     eps=config.training.eps)
         dev = envs.engine.device
         self.device = dev
-        self.rollouts = SRNNRolloutStorage(self.num_steps, E, envs.observation_space.spaces, envs.action_space,
-                                           config.SRNN.human_node_rnn_size, config.SRNN.human_human_edge_rnn_size,
-                                           "GRU", device=dev, compact_hidden=True)
+        if self.convgru:
+            self.rollouts = RolloutStorage(self.num_steps, E, envs.observation_space.shape, envs.action_space,
+                                           actor_critic.base.recurrent_hidden_state_size, device=dev,
+                                           compact_hidden=True)
+        else:
+            self.rollouts = SRNNRolloutStorage(self.num_steps, E, envs.observation_space.spaces, envs.action_space,
+                                               config.SRNN.human_node_rnn_size, config.SRNN.human_human_edge_rnn_size,
+                                               "GRU", device=dev, compact_hidden=True)
         r, T = self.rollouts, self.num_steps
         # the rollout records into the storage itself: rows t of the observation are obs[t + 1], the labels the
         # actions, the rewards the rewards; done / event / executed are the trainer's own
-        self._buf = {k: r.obs[k][1:] for k in ("robot_node", "temporal_edges", "spatial_edges")}
+        if self.convgru:
+            # obs[1:] is contiguous: the scan of all T * E rows lands there. The SRNN observation is not read: the
+            # engine's own single-row buffers take the last step's (obs_every_step=False); the state rows are the
+            # rollout's workspace
+            N = int(config.sim.human_num)
+            self._buf = dict(envs.engine.obs())
+            self._buf["lidar"] = r.obs[1:]
+            self._buf["robot_state"] = torch.zeros((9, T, E), dtype=torch.float64, device=dev)
+            self._buf["human_state"] = torch.zeros((3, T, E, N), dtype=torch.float64, device=dev)
+        else:
+            self._buf = {k: r.obs[k][1:] for k in ("robot_node", "temporal_edges", "spatial_edges")}
         self._buf["actions"] = r.actions
         self._buf["reward"] = r.rewards.view(T, E)
         self._buf["done"] = torch.zeros((T, E), dtype=torch.uint8, device=dev)
@@ -69,13 +97,29 @@ class BehaviourCloning:
         self.env_steps = 0
         self.chunks = 0
         obs = envs.reset()
-        for k in r.obs:
-            r.obs[k][0].copy_(obs[k])
+        if self.convgru:
+            r.obs[0].copy_(obs)
+        else:
+            for k in r.obs:
+                r.obs[k][0].copy_(obs[k])
+
+    def _obs(self, fn):
+        """fn over the storage's observation: the DSRNN's dict of tensors or the ConvGRU's one tensor."""
+        o = self.rollouts.obs
+        return {k: fn(v) for k, v in o.items()} if isinstance(o, dict) else fn(o)
+
+    def _hxs(self, fn):
+        h = self.rollouts.recurrent_hidden_states
+        return {k: fn(v) for k, v in h.items()} if isinstance(h, dict) else fn(h)
 
     @contextlib.contextmanager
     def _sequence_shape(self, B):
         """SRNN.forward reads the sequence length and the envs per minibatch from its own attributes (the reference's
-        seq_length / nenv / nminibatch): set them for this trainer's chunk, put PPO's back afterwards."""
+        seq_length / nenv / nminibatch): set them for this trainer's chunk, put PPO's back afterwards. (ConvGRU
+        reads both from its arguments' shapes.)"""
+        if self.convgru:
+            yield
+            return
         b = self.ac.base
         keep = (b.seq_length, b.nenv, b.nminibatch)
         b.seq_length, b.nenv, b.nminibatch = self.num_steps, B, 1
@@ -91,7 +135,7 @@ class BehaviourCloning:
         ScriptedRobot.rollout call; no host synchronisation."""
         r, T = self.rollouts, self.num_steps
         noise = RolloutNoise(self.noise.sigma, self.noise.seed, self.noise.step0 + self.chunks * T)
-        self.last = self.robot.rollout(T, out=self._buf, noise=noise)
+        self.last = self.robot.rollout(T, obs_every_step=not self.convgru, out=self._buf, noise=noise)
         r.masks[1:].copy_(torch.rsub(self._buf["done"].unsqueeze(-1), 1.0))   # 1 - done as float32
         self.chunks += 1
         self.env_steps += T * self.envs.num_envs
@@ -107,9 +151,12 @@ class BehaviourCloning:
         B = E // self.num_mini_batch
         with self._sequence_shape(B):
             for s in range(0, E, B):
-                obs = {k: v[:-1, s:s + B].reshape(T * B, *v.shape[2:]) for k, v in r.obs.items()}
-                hxs = {k: v[0][s:s + B] for k, v in r.recurrent_hidden_states.items()}
+                obs = self._obs(lambda v: v[:-1, s:s + B].reshape(T * B, *v.shape[2:]))
+                hxs = self._hxs(lambda v: v[0][s:s + B])
                 _, _, out = self.ac.base(obs, hxs, r.masks[:-1, s:s + B].reshape(T * B, 1))
+                if self.convgru:
+                    r.recurrent_hidden_states[-1][s:s + B].copy_(out)
+                    continue
                 for k, v in r.recurrent_hidden_states.items():
                     v[-1][s:s + B].copy_(out[k].reshape(v[-1][s:s + B].shape))
 
@@ -124,8 +171,8 @@ class BehaviourCloning:
         """The stored chunk's mean negative log-likelihood under the current weights (device scalar)."""
         r, T, E = self.rollouts, self.num_steps, self.envs.num_envs
         with self._sequence_shape(E):
-            obs = {k: v[:-1].reshape(T * E, *v.shape[2:]) for k, v in r.obs.items()}
-            hxs = {k: v[0] for k, v in r.recurrent_hidden_states.items()}
+            obs = self._obs(lambda v: v[:-1].reshape(T * E, *v.shape[2:]))
+            hxs = self._hxs(lambda v: v[0])
             return self._losses(obs, hxs, r.masks[:-1].reshape(T * E, 1), r.actions.reshape(T * E, -1),
                                 r.returns[:-1].reshape(T * E, 1))[0]
 
@@ -163,7 +210,7 @@ class BehaviourCloning:
         r = self.rollouts
         self._advance_state()
         with torch.no_grad(), self._sequence_shape(self.envs.num_envs):
-            next_value = self.ac.get_value({k: v[-1] for k, v in r.obs.items()}, r.hidden(r.num_steps), r.masks[-1])
+            next_value = self.ac.get_value(self._obs(lambda v: v[-1]), r.hidden(r.num_steps), r.masks[-1])
         r.compute_returns(next_value, False, c.reward.gamma, c.ppo.gae_lambda, c.training.use_proper_time_limits)
         acc, n = self.fit()
         done, event = self._buf["done"], self._buf["event"]

@@ -271,6 +271,20 @@ class ScriptedRobot:
             raise UnsupportedConfig("ScriptedRobot: action_space.kinematics=%r (the controllers return ActionXY: "
                                     "holonomic only)" % config.action_space.kinematics)
 
+    @classmethod
+    def check_rollout(cls, venv, name):
+        """check(), and UnsupportedConfig for an env whose observation a rollout cannot record: 'convgru' without
+        lidar.live (before anything touches the GPU)."""
+        cls.check(venv, name)
+        mode = getattr(venv, "obs_mode", "srnn")
+        if mode == "convgru":
+            lc = venv.config.lidar
+            if not (getattr(lc, "live", False) and lc.enable):
+                raise UnsupportedConfig("ScriptedRobot.rollout: obs_mode='convgru' needs config.lidar.live (the held "
+                                        "per-episode scan is not a function of the recorded state)")
+        elif mode != "srnn":
+            raise UnsupportedConfig("ScriptedRobot.rollout: obs_mode=%r" % mode)
+
     def __init__(self, venv, name):
         self.check(venv, name)
         config = venv.config
@@ -287,13 +301,14 @@ class ScriptedRobot:
         """T closed-loop steps of this controller from the env's current state, every step recorded
         (CrowdNavVecEnv.rollout -> cn_rollout): a dict of (T, E, ...) device tensors -- actions, the observation
         after each step, reward, done, event, info, ep_return, ep_len -- and 'num_launches'. Expert pairs are
-        (observation row t-1, actions row t), row -1 being the reset observation. 'srnn' observation only.
+        (observation row t-1, actions row t), row -1 being the reset observation.
         `noise` (engine.RolloutNoise or a dict with sigma / seed / step0): noise-injected demonstrations -- the steps
-        take actions + sigma * uniform[-1, 1) noise (returned as 'executed'), the labels in 'actions' stay clean."""
-        self.check(self.venv, self.name)
-        if getattr(self.venv, "obs_mode", "srnn") != "srnn":
-            raise UnsupportedConfig("ScriptedRobot.rollout: obs_mode=%r (the rollout records the 'srnn' observation "
-                                    "only)" % self.venv.obs_mode)
+        take actions + sigma * uniform[-1, 1) noise (returned as 'executed'), the labels in 'actions' stay clean.
+        On a 'convgru' env with lidar.live the dict also holds 'lidar' (T, E, 1, 7 + beams), the LiDAR observation
+        after each step, with the state rows it was scanned from (cn_rollout_lidar); without lidar.live the
+        observation carries the scan held since the episode's reset, which no recorded row determines:
+        UnsupportedConfig."""
+        self.check_rollout(self.venv, self.name)
         return self.venv.rollout(self.name, T, obs_every_step=obs_every_step, out=out, noise=noise)
 
 

@@ -38,6 +38,8 @@
  *                   multi-step launches with the controller inside the step kernel
  *   cn_rollout_noisy ⟵ (no reference counterpart) cn_rollout whose executed action is the clean one plus uniform
  *                   noise, the label staying clean: noise-injected expert demonstrations for behaviour cloning
+ *   cn_rollout_lidar ⟵ (no reference counterpart) either of the two, recording the state every step leaves and,
+ *                   from it, the live ConvGRU observation (cn_lidar_scan's) of every step in one scan launch
  *   cn_lidar_obs     ⟵ CrowdSimDict.generate_ob's 'convgru' observation (crowd_sim_dict.py:96-101) with
  *                   LidarSensor.sensor_spin (crowd_sim/envs/utils/lidarv2.py:398-427) evaluated at reset
  *   cn_lidar_scan    ⟵ the scan CrowdSimDict.step() takes every step and discards (crowd_sim_dict.py:224-251):
@@ -554,6 +556,40 @@ typedef struct cn_rollout_noise {
 } cn_rollout_noise;
 int cn_rollout_noisy(cn_engine *eng, void *stream, int policy, int T, const cn_rollout_out *out,
                      const cn_rollout_noise *noise, int32_t *num_launches);
+
+/* cn_rollout / cn_rollout_noisy that also record the live ConvGRU observation of every step, so that the LiDAR
+ * policy can be trained from the scripted expert. For every step t and env e the call records the state step t
+ * LEAVES (after an auto-reset where one happened: the state cn_step's observation describes) -- the twelve float64
+ * fields cn_lidar_scan reads, field-major:
+ *   robot_state [9][T][E]    = r_px, r_py, r_vx, r_vy, r_radius, r_gx, r_gy, r_vpref, r_theta
+ *   human_state [3][T][E][N] = h_px, h_py, h_r      (the humans' TRUE positions, not the robot's belief)
+ * and after the last step scans all T * E rows at once: obs[t][e] is bit for bit what cn_lidar_scan(eng, stream,
+ * beams, max_range, robot_radius, ..) writes for env e when called right after step t. The three buffers are
+ * caller-owned and required; the state rows are workspace and output. `out` is cn_rollout's (without
+ * CN_ROLLOUT_OBS_EVERY_STEP the SRNN observation stays one row); noise = NULL is cn_rollout, otherwise
+ * cn_rollout_noisy (sigma == 0 included). Every row those record and the state blob afterwards are theirs bit for
+ * bit; a call of T steps equals calls of T1 and T - T1 steps (each with buffers of its own length).
+ * Stream-ordered; no allocation, no synchronisation, no memset. *num_launches counts every kernel launch:
+ *   Fused path (cn_rollout's conditions), T' = T minus a first step after cn_reset / cn_set_state:
+ *       [1 if sigma > 0: the noise block] + 1 (the row block) + ceil(T' / C) + S       (T' > 0)
+ *     the rollout launches record the rows themselves: while the controller of step s >= 1 runs on one wave, the
+ *     other waves of the workgroup copy the state step s - 1 left; the launch's last step copies its own.
+ *   Elsewhere (chunk 1, graph mode, that first step, ORCA at N + 1 > 10, the kd-tree step path), per step:
+ *       cn_robot_act, [the perturbation if sigma > 0], cn_step, the row copy: 3 or 4 launches, then + S.
+ *   S = the scan: 1 launch, unless T * E * N (or T * E) reaches 2^31, where it is split into spans of rows whose
+ *     indices stay in int range. + 1 for the copy into `executed` when noise is given with sigma == 0.
+ * CN_EINVAL: lidar NULL, a NULL buffer in it, cn_lidar_scan's (beams in [2, 4096], max_range in (0, 1e4] and at
+ * least two 0.01 m samples), cn_rollout_noisy's for a non-NULL noise, cn_rollout's. CN_EUNSUPPORTED: cn_rollout's
+ * (a unicycle or a mixed engine). All are checked before any launch (*num_launches = 0). T = 0 launches nothing. */
+struct cn_rollout_lidar {   /* (no typedef: the function below has the name, as stat() and struct stat) */
+    float  *obs;           /* [T][E][7 + beams]: the ConvGRU observation AFTER step t, what cn_lidar_scan writes for that state */
+    int32_t beams;  double max_range, robot_radius;      /* cn_lidar_scan's, same ranges */
+    double *robot_state;   /* [9][T][E]    */
+    double *human_state;   /* [3][T][E][N] */
+};
+int cn_rollout_lidar(cn_engine *eng, void *stream, int policy, int T, const cn_rollout_out *out,
+                     const cn_rollout_noise *noise /* NULL: no noise */, const struct cn_rollout_lidar *lidar,
+                     int32_t *num_launches);
 
 /* Test hooks of the kd-tree path's resumable spawns (the spawn waves that draw upcoming episodes park a
  * crowded spawn between two humans once a wave has worked `cycles` clock cycles in a launch, and a later

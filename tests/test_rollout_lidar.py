@@ -1,0 +1,539 @@
+"""Scripted rollouts that record the live LiDAR observation (cn_rollout_lidar, rollout(..., lidar=)).
+
+The rollout records the state every step leaves (the twelve float64 fields cn_lidar_scan reads) and scans all T * E
+rows in one launch afterwards. The scan is a pure function of those fields, and copying them is no arithmetic, so every
+GPU comparison is exact: `lidar`, `robot_state`, `human_state`, every cn_rollout row and the final blob against an
+eager loop robot_act -> (the restatement's noise) -> step -> lidar_scan of a second engine of the same config, with the
+blob's twelve fields read after every step. Shapes are tests/test_rollout_noise.py's: 13 envs at env_offset 3 of 20,
+37 steps, time_limit 2.0 at time_step 0.25 (every env auto-resets at least four times), robot.FOV 2.0. FOV counts in
+units of pi (config.py: robot_fov = pi * robot.FOV), so 2.0 is the full circle and the robot's belief of a visible
+human IS its position: at those four cases a scan taken from the belief could not be told from one taken from the
+true positions. A fifth case therefore runs ORCA at 5 humans with robot.FOV 0.5 (a quarter circle), where the belief
+of most humans is stale or the dummy far away, and the premise "belief != position" is asserted there. Two LiDAR
+settings: 180 beams / range 5 (one row per
+workgroup) and 65 beams / range 11 (seven rows per workgroup: the groups straddle the 13-env steps)."""
+import ctypes
+import os
+import re
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import lidar_live_ref as R  # noqa: E402
+import rollout_noise_ref as ref_noise  # noqa: E402
+
+from crowdnav_dsrnn_amd.config import Config, UnsupportedConfig, clone_config, make_cn_config  # noqa: E402
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+OBS = ("robot_node", "temporal_edges", "spatial_edges")
+RECORDS = ("reward", "done", "event", "info", "ep_return", "ep_len")
+ROWS = ("actions", "executed") + OBS + RECORDS
+STATE_ROWS = ("robot_state", "human_state")
+ROBOT_FIELDS = ("r_px", "r_py", "r_vx", "r_vy", "r_radius", "r_gx", "r_gy", "r_vpref", "r_theta")
+HUMAN_FIELDS = ("h_px", "h_py", "h_r")
+EINVAL, EUNSUPPORTED = -1, -2
+E, OFFSET, NENV, T, SIGMA, SEED, STEP0 = 13, 3, 20, 37, 0.2, 20240607, 5
+CASES = [("orca", 5, 2.0), ("orca", 9, 2.0), ("orca", 10, 2.0), ("social_force", 5, 2.0), ("orca", 5, 0.5)]
+LIDARS = {"b180_r5": dict(beams=180, max_range=5.0, robot_radius=0.3),
+          "b65_r11": dict(beams=65, max_range=11.0, robot_radius=0.3)}
+CAP = 0.005   # tests/test_lidar_live.py's share of unstable beams
+
+
+def _config(N, kin="holonomic", policy="srnn", live=None, fov=2.0):
+    c = clone_config(Config())
+    c.sim.human_num = N
+    c.robot.FOV = fov
+    c.robot.policy = policy
+    c.action_space.kinematics = kin
+    c.sim.train_val_sim = c.sim.test_sim = ["circle_crossing"]
+    c.humans.policy = "orca"
+    c.env.time_limit = 2.0
+    c.env.time_step = 0.25
+    if live is not None:
+        c.lidar.enable = True
+        c.lidar.live = live
+    return c
+
+
+# ---- CPU ----------------------------------------------------------------------------------------
+def _header():
+    return open(os.path.join(REPO, "include", "crowdnav.h")).read()
+
+
+def test_header_binding_and_export_list_agree_on_cn_rollout_lidar():
+    from crowdnav_dsrnn_amd import _lib
+
+    txt = _header()
+    m = re.search(r"^int cn_rollout_lidar\((.*?)\);", txt, re.S | re.M)
+    assert m, "include/crowdnav.h does not declare cn_rollout_lidar"
+    params = [p.strip() for p in re.sub(r"/\*.*?\*/", "", m.group(1), flags=re.S).split(",")]
+    assert [re.sub(r"\w+$", "", p).replace(" ", "") for p in params] == [
+        "cn_engine*", "void*", "int", "int", "constcn_rollout_out*", "constcn_rollout_noise*",
+        "conststructcn_rollout_lidar*", "int32_t*"]
+    # (a struct tag without a typedef: C has one namespace for typedef names and functions)
+    m = re.search(r"^struct cn_rollout_lidar \{(.*?)^\};", txt, re.S | re.M)
+    assert m, "include/crowdnav.h does not define struct cn_rollout_lidar"
+    body = re.sub(r"/\*.*?\*/", "", m.group(1), flags=re.S)
+    fields = []
+    for decl in body.split(";"):
+        if not decl.strip():
+            continue
+        ty, names = re.match(r"^\s*(\w+)\s+(.*)$", decl.strip(), re.S).groups()
+        for n in names.split(","):
+            n = n.strip()
+            fields.append((ty, "*" if n.startswith("*") else "", n.lstrip("* ")))
+    assert fields == [("float", "*", "obs"), ("int32_t", "", "beams"), ("double", "", "max_range"),
+                      ("double", "", "robot_radius"), ("double", "*", "robot_state"), ("double", "*", "human_state")]
+    assert [f[0] for f in _lib.RolloutLidar._fields_] == [f[2] for f in fields]
+    ctype = {("float", "*"): ctypes.c_void_p, ("double", "*"): ctypes.c_void_p, ("int32_t", ""): ctypes.c_int32,
+             ("double", ""): ctypes.c_double}
+    assert [f[1] for f in _lib.RolloutLidar._fields_] == [ctype[f[:2]] for f in fields]
+    assert ctypes.sizeof(_lib.RolloutLidar) == 48
+    assert [getattr(_lib.RolloutLidar, f[2]).offset for f in fields] == [0, 8, 16, 24, 32, 40]
+    assert "cn_rollout_lidar" in _lib.EXPORTED
+
+
+def test_built_library_exports_cn_rollout_lidar():
+    from crowdnav_dsrnn_amd import _lib, build
+
+    build.build()
+    L = _lib.lib()
+    assert hasattr(L, "cn_rollout_lidar") and len(L.cn_rollout_lidar.argtypes) == 8
+
+
+def test_null_arguments_are_einval():
+    from crowdnav_dsrnn_amd import _lib, build
+
+    build.build()
+    L = _lib.lib()
+    nl = ctypes.c_int32(7)
+    ld = _lib.RolloutLidar(None, 180, 5.0, 0.3, None, None)
+    assert L.cn_rollout_lidar(None, None, 0, 4, None, None, ctypes.byref(ld), ctypes.byref(nl)) == EINVAL
+    assert nl.value == 0 and b"null engine" in L.cn_last_error()
+    nl = ctypes.c_int32(7)
+    assert L.cn_rollout_lidar(None, None, 0, 4, None, None, None, ctypes.byref(nl)) == EINVAL and nl.value == 0
+
+
+class _VenvStub:
+    """What ScriptedRobot / CrowdNavVecEnv.rollout read before they touch the engine (no GPU behind it)."""
+
+    num_envs = 8
+
+    def __init__(self, config, obs_mode="srnn", live=False):
+        self.config = config
+        self.obs_mode = obs_mode
+        self._lidar_live = live
+
+    def __getattr__(self, name):
+        raise AssertionError("the check must come before the engine is touched (%s)" % name)
+
+
+def test_unsupported_configs_are_refused_without_a_gpu():
+    from crowdnav_dsrnn_amd.envs import CrowdNavVecEnv
+    from crowdnav_dsrnn_amd.policy_factory import ScriptedRobot
+
+    # the held per-episode scan (parity mode) is no function of a recorded row
+    parity = _VenvStub(_config(5, policy="convgru", live=False), obs_mode="convgru", live=False)
+    with pytest.raises(UnsupportedConfig, match="lidar.live"):
+        CrowdNavVecEnv.rollout(parity, "orca", 4)
+    with pytest.raises(UnsupportedConfig, match="lidar.live"):
+        ScriptedRobot(parity, "orca").rollout(4)
+    # unicycle: the controllers return ActionXY (CN_EUNSUPPORTED in the library: the GPU error-code test below)
+    uni = _VenvStub(_config(5, kin="unicycle", policy="convgru", live=True), obs_mode="convgru", live=True)
+    robot = ScriptedRobot(parity, "orca")
+    robot.venv = uni
+    with pytest.raises(UnsupportedConfig, match="holonomic"):
+        robot.rollout(4)
+
+
+# ---- GPU ----------------------------------------------------------------------------------------
+def _engine(c, chunk=None):
+    from crowdnav_dsrnn_amd.engine import CrowdNavEngine
+
+    eng = CrowdNavEngine(make_cn_config(c, num_envs=E, env_offset=OFFSET, nenv=NENV, phase="train"), "cuda:0")
+    if chunk is not None:
+        eng.set_seq_chunk(chunk)
+    return eng
+
+
+def _blob(eng):
+    return np.asarray(eng.get_state().blob).view(np.uint8).copy()
+
+
+def _host(out):
+    import torch
+
+    torch.cuda.synchronize()
+    return {k: out[k].cpu().numpy() for k in ROWS + STATE_ROWS + ("lidar",) if out.get(k) is not None}
+
+
+def _same(got, ref, what, keys):
+    for k in keys:
+        g, r = np.ascontiguousarray(got[k]), np.ascontiguousarray(ref[k])
+        assert g.dtype == r.dtype and g.shape == r.shape, (what, k, g.dtype, r.dtype, g.shape, r.shape)
+        if g.tobytes() != r.tobytes():
+            ax = 1 if k in STATE_ROWS else 0   # the step axis
+            gm, rm = np.moveaxis(g, ax, 0), np.moveaxis(r, ax, 0)
+            bad = np.flatnonzero((gm.reshape(gm.shape[0], -1).view(np.uint8) !=
+                                  rm.reshape(rm.shape[0], -1).view(np.uint8)).any(1))
+            raise AssertionError("%s: %s differs at steps %s" % (what, k, bad[:8].tolist()))
+
+
+def _keys(noisy):
+    return tuple(k for k in ROWS if noisy or k != "executed") + STATE_ROWS + ("lidar", "state")
+
+
+def _rollout(name, N, fov, lk, noisy, calls=((T, STEP0),), chunk=None, graph=False):
+    """A fresh engine from cn_reset, then rollout(Tk, lidar=) per call: host rows (concatenated along the step
+    axis), the launches per call and the state blob."""
+    from crowdnav_dsrnn_amd.engine import RolloutNoise
+
+    eng = _engine(_config(N, fov=fov), chunk=chunk)
+    eng.reset()
+    if graph:
+        eng.set_graph_mode(True)
+    parts, nls = [], []
+    for Tk, s0 in calls:
+        out = eng.rollout(name, Tk, noise=RolloutNoise(SIGMA, SEED, s0) if noisy else None, lidar=LIDARS[lk])
+        assert out["lidar"].shape == (Tk, E, 1, 7 + LIDARS[lk]["beams"])
+        assert out["robot_state"].shape == (9, Tk, E) and out["human_state"].shape == (3, Tk, E, N)
+        parts.append(_host(out))
+        nls.append(out["num_launches"])
+    if graph:
+        eng.set_graph_mode(False)
+    got = {k: np.concatenate([p[k] for p in parts], axis=1 if k in STATE_ROWS else 0) for k in parts[0]}
+    got["state"] = _blob(eng)
+    eng.close()
+    return got, nls
+
+
+def _eager(name, N, fov, noisy):
+    """The reference: a = robot_act(); x = restatement(a) (noisy) or a; step(x); lidar_scan at both settings into a
+    row of its own; the blob's twelve fields read after the step. Also the belief (for the premise)."""
+    import torch
+
+    eng = _engine(_config(N, fov=fov))
+    eng.reset()
+    rows = {k: [] for k in ROWS if noisy or k != "executed"}
+    scans = {lk: [] for lk in LIDARS}
+    fields = {f: [] for f in ROBOT_FIELDS + HUMAN_FIELDS + ("b_px", "b_py")}
+    for t in range(T):
+        a = eng.robot_act(name).clone()
+        xd = a
+        if noisy:
+            x = ref_noise.perturb(a.cpu().numpy()[None], SIGMA, SEED, STEP0 + t, OFFSET)[0]
+            xd = torch.from_numpy(x).to("cuda:0")
+            rows["executed"].append(xd)
+        obs, rew, done, ev, info, epr, epl = eng.step(xd)
+        rows["actions"].append(a)
+        for k in OBS:
+            rows[k].append(obs[k].clone())
+        for k, v in zip(RECORDS, (rew, done, ev, info, epr, epl)):
+            rows[k].append(v.clone())
+        for lk, kw in LIDARS.items():
+            row = torch.full((E, 1, 7 + kw["beams"]), -1.0, device="cuda:0")
+            scans[lk].append(eng.lidar_scan(row, **kw))
+        sv = eng.get_state()
+        for f in fields:
+            fields[f].append(np.array(getattr(sv, f), np.float64))
+    torch.cuda.synchronize()
+    out = {k: torch.stack(v).cpu().numpy() for k, v in rows.items()}
+    out["lidar"] = {lk: torch.stack(v).cpu().numpy() for lk, v in scans.items()}
+    out["robot_state"] = np.stack([np.stack(fields[f]) for f in ROBOT_FIELDS])
+    out["human_state"] = np.stack([np.stack(fields[f]) for f in HUMAN_FIELDS])
+    out["belief"] = np.stack([np.stack(fields[f]) for f in ("b_px", "b_py")])
+    out["state"] = _blob(eng)
+    out["half_world"] = eng.cfg.square_width / 2
+    eng.close()
+    return out
+
+
+_CACHE = {}
+
+
+def _cached(key, make):
+    if key not in _CACHE:
+        _CACHE[key] = make()
+    return _CACHE[key]
+
+
+def _eager_cached(name, N, fov, noisy):
+    return _cached(("eager", name, N, fov, noisy), lambda: _eager(name, N, fov, noisy))
+
+
+def _ref(name, N, fov, lk, noisy):
+    """The eager reference with `lidar` of one setting (one eager loop serves both settings)."""
+    ref = dict(_eager_cached(name, N, fov, noisy))
+    ref["lidar"] = ref["lidar"][lk]
+    return ref
+
+
+def _fused(name, N, fov, lk, noisy=True):
+    return _cached(("fused", name, N, fov, lk, noisy), lambda: _rollout(name, N, fov, lk, noisy))
+
+
+def _launches(name, N, T1, noisy, first_after_reset=True, chunk=32, graph=False):
+    """include/crowdnav.h's formula for cn_rollout_lidar (T1 * E * N is far below 2^31: one scan launch)."""
+    per_step = 3 + (1 if noisy else 0)   # cn_robot_act, [the perturbation], cn_step, the row copy
+    if (name == "orca" and N + 1 > 10) or chunk == 1 or graph:
+        return per_step * T1 + 1
+    rest = T1 - 1 if first_after_reset else T1
+    fused = (1 if noisy else 0) + 1 + -(-rest // chunk) if rest > 0 else 0
+    return (per_step if first_after_reset else 0) + fused + 1
+
+
+def _walls_only_differs(ref, lk):
+    """(T, E) bool: some beam of the row's scan differs from the walls-only scan of the same robot pose
+    (tests/lidar_live_ref.py with no humans). Where no wall is within max_range of the robot the walls-only scan is
+    rel_dist 1 on every beam (observation 0), which needs no beam-by-beam restatement."""
+    kw, half = LIDARS[lk], ref["half_world"]
+    rs, lidar = ref["robot_state"], ref["lidar"][lk][:, :, 0, 7:]
+    out = np.zeros((T, E), bool)
+    none = np.empty((0, 3))
+    for t in range(T):
+        for e in range(E):
+            x, y = rs[0, t, e], rs[1, t, e]
+            if half - max(abs(x), abs(y)) > kw["max_range"] + 1e-9:
+                walls = np.zeros(kw["beams"])
+            else:
+                walls = R.to_obs(R.scan((x, y), np.arctan2(rs[3, t, e], rs[2, t, e]), none, half_world=half, **kw))
+            out[t, e] = bool((np.abs(lidar[t, e] - walls) > 1e-6).any())
+    return out
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,N,fov", CASES)
+def test_gpu_premises_hold_on_the_reference_run(name, N, fov):
+    """No case is vacuous: every env auto-resets at least four times, humans are in sight in at least half of the rows,
+    and the robot's belief differs from the humans' positions."""
+    for noisy in (False, True):
+        ref = _eager_cached(name, N, fov, noisy)
+        assert (ref["done"].sum(0) >= 4).all(), ref["done"].sum(0)
+        differs = (ref["belief"] != ref["human_state"][:2]).any(0)   # (T, E, N)
+        print(name, N, fov, "humans whose belief is not their position: %.3f of the rows" % differs.mean())
+        if fov < 2.0:
+            assert differs.any()   # some human in some row
+        else:
+            assert not differs.any()   # the full circle: what the module docstring says of these cases
+    ref = _eager_cached(name, N, fov, True)
+    for lk in LIDARS:
+        share = _walls_only_differs(ref, lk).mean()
+        print(name, N, lk, "rows with a human in the scan: %.3f" % share)
+        assert share >= 0.5, (lk, share)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("lk", sorted(LIDARS))
+@pytest.mark.parametrize("noisy", [False, True])
+@pytest.mark.parametrize("name,N,fov", CASES)
+def test_gpu_rows_equal_the_eager_loop(name, N, fov, noisy, lk):
+    got, nls = _fused(name, N, fov, lk, noisy)
+    assert nls == [_launches(name, N, T, noisy)], nls
+    if not (name == "orca" and N + 1 > 10):
+        assert nls[0] < T   # (the eager triple robot_act -> step -> lidar_scan issues 3 T)
+    ref = _ref(name, N, fov, lk, noisy)
+    _same(got, ref, "%s N=%d %s vs robot_act -> step -> lidar_scan" % (name, N, lk), _keys(noisy))
+    assert ("executed" in got) == noisy
+    if fov < 2.0:   # a scan taken from the belief would differ: the humans' true positions are recorded
+        assert (got["human_state"][:2] != ref["belief"]).any()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,N,fov", CASES)
+def test_gpu_rollout_rows_are_cn_rollouts(name, N, fov):
+    """Every row cn_rollout / cn_rollout_noisy record, and the blob afterwards, with and without the lidar option."""
+    from crowdnav_dsrnn_amd.engine import RolloutNoise
+
+    for noisy in (False, True):
+        got, _ = _fused(name, N, fov, "b180_r5", noisy)
+        eng = _engine(_config(N, fov=fov))
+        eng.reset()
+        plain = eng.rollout(name, T, noise=RolloutNoise(SIGMA, SEED, STEP0) if noisy else None)
+        assert "lidar" not in plain and "robot_state" not in plain
+        ref = _host(plain)
+        ref["state"] = _blob(eng)
+        eng.close()
+        _same(got, ref, "%s N=%d lidar vs no lidar" % (name, N), tuple(k for k in _keys(noisy) if k in ref))
+
+
+@pytest.mark.gpu
+def test_gpu_sigma_zero_is_the_clean_rollout_plus_the_copy():
+    """noise given with sigma 0: cn_rollout's rows, `executed` a copy of the actions, one launch more."""
+    from crowdnav_dsrnn_amd.engine import RolloutNoise
+
+    name, N, fov, lk = "orca", 5, 0.5, "b65_r11"
+    clean, nls = _fused(name, N, fov, lk, False)
+    eng = _engine(_config(N, fov=fov))
+    eng.reset()
+    out = eng.rollout(name, T, noise=RolloutNoise(0.0, SEED, STEP0), lidar=LIDARS[lk])
+    zero = _host(out)
+    zero["state"] = _blob(eng)
+    eng.close()
+    assert out["num_launches"] == nls[0] + 1
+    _same(zero, clean, "sigma 0 vs no noise", _keys(False))
+    assert zero["executed"].tobytes() == zero["actions"].tobytes()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("lk", sorted(LIDARS))
+@pytest.mark.parametrize("name,N,fov", CASES)
+def test_gpu_fused_equals_chunk_one_equals_chunk_five(name, N, fov, lk):
+    got, _ = _fused(name, N, fov, lk)
+    one, nls = _rollout(name, N, fov, lk, True, chunk=1)
+    assert nls == [_launches(name, N, T, True, chunk=1)], nls
+    _same(got, one, "%s N=%d %s fused vs chunk 1" % (name, N, lk), _keys(True))
+    five, nls = _rollout(name, N, fov, lk, True, chunk=5)
+    assert nls == [_launches(name, N, T, True, chunk=5)], nls
+    _same(got, five, "%s N=%d %s fused vs chunk 5" % (name, N, lk), _keys(True))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("lk", sorted(LIDARS))
+@pytest.mark.parametrize("name,N,fov", CASES)
+def test_gpu_two_calls_equal_one(name, N, fov, lk):
+    got, _ = _fused(name, N, fov, lk)
+    two, nls = _rollout(name, N, fov, lk, True, calls=((17, STEP0), (20, STEP0 + 17)))
+    assert nls == [_launches(name, N, 17, True), _launches(name, N, 20, True, first_after_reset=False)], nls
+    _same(got, two, "%s N=%d %s one call vs 17 + 20" % (name, N, lk), _keys(True))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,N,fov", CASES)
+def test_gpu_graph_mode_gives_the_same_rows(name, N, fov):
+    got, _ = _fused(name, N, fov, "b65_r11")
+    gm, nls = _rollout(name, N, fov, "b65_r11", True, graph=True)
+    assert nls == [_launches(name, N, T, True, graph=True)], nls
+    _same(got, gm, "%s N=%d graph mode" % (name, N), _keys(True))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,N,fov", CASES)
+def test_gpu_done_rows_show_the_new_episode(name, N, fov):
+    """Where an env finished in step t, row t holds the state after its auto-reset: the robot at rest at the new
+    episode's start, which is also what the SRNN observation of that row (the new episode's first) shows."""
+    got, _ = _fused(name, N, fov, "b180_r5")
+    done = got["done"].astype(bool)
+    rs = got["robot_state"]
+    assert done.any() and (rs[2][done] == 0).all() and (rs[3][done] == 0).all()
+    assert (rs[2][~done] != 0).any()
+    node = got["robot_node"][:, :, 0, :]   # (px, py, radius, gx, gy, v_pref, theta) float32
+    for f, k in ((0, 0), (1, 1), (4, 2), (5, 3), (6, 4), (7, 5)):
+        assert (rs[f].astype(np.float32)[done] == node[..., k][done]).all(), ROBOT_FIELDS[f]
+    # and the scan row is the observation of that state: the robot part is the clipped, scaled state
+    want = np.clip(np.stack([rs[0], rs[1], rs[4], rs[5], rs[6], rs[7], rs[8]], -1) / 5.0, 0, 1).astype(np.float32)
+    assert got["lidar"][:, :, 0, :7].tobytes() == want.tobytes()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("lk", sorted(LIDARS))
+def test_gpu_recorded_rows_reproduce_the_scan_in_the_restatement(lk):
+    """tests/lidar_live_ref.py fed from the recorded state rows reproduces `lidar`, by tests/test_lidar_live.py's
+    criterion: stable beams within 1e-6, unstable ones at most 0.5 %. Three rows: right after an auto-reset (heading
+    0), mid-episode, and the last row of the call."""
+    name, N, fov = "orca", 5, 0.5
+    got, _ = _fused(name, N, fov, lk)
+    ref = _ref(name, N, fov, lk, True)
+    kw, half = LIDARS[lk], ref["half_world"]
+    done = got["done"].astype(bool)
+    t_done, e_done = [int(v[0]) for v in np.nonzero(done)]
+    picks = [(t_done, e_done), (T // 2, int(np.flatnonzero(~done[T // 2])[0])), (T - 1, E - 1)]
+    rng = np.random.RandomState(7)
+    un_all, n = 0, 0
+    for t, e in picks:
+        rs, hs = got["robot_state"][:, t, e], got["human_state"][:, t, e]
+        args = ((rs[0], rs[1]), np.arctan2(rs[3], rs[2]), np.stack([hs[0], hs[1], hs[2]], 1))
+        fn = lambda s, h, x: R.scan(s, float(h), x, half_world=half, **kw)  # noqa: E731
+        want, un = R.to_obs(fn(*args)), R.unstable_mask(fn, args, rng)
+        err = np.abs(got["lidar"][t, e, 0, 7:].astype(np.float64) - want)
+        print(lk, (t, e), "max err on stable beams %.3g, unstable %d" % (err[~un].max(), int(un.sum())))
+        assert (err[~un] <= 1e-6).all(), ((t, e), err[~un].max())
+        un_all, n = un_all + int(un.sum()), n + un.size
+    assert un_all / n <= CAP, un_all / n
+
+
+@pytest.mark.gpu
+def test_gpu_vecenv_rollout_is_step_device_step_by_step():
+    """CrowdNavVecEnv.rollout on a live convgru env passes the env's LiDAR settings: the `lidar` rows are what
+    step_device returns when the same executed actions are fed step by step."""
+    import torch
+
+    from crowdnav_dsrnn_amd.envs import CrowdNavVecEnv
+    from crowdnav_dsrnn_amd.policy_factory import ScriptedRobot
+
+    def make():
+        c = _config(5, policy="convgru", live=True)
+        envs = CrowdNavVecEnv(c, E, c.env.seed, "cuda:0", allow_early_resets=True, env_offset=OFFSET, nenv=NENV,
+                              phase="train")
+        envs.reset()
+        return envs
+
+    a, b = make(), make()
+    out = ScriptedRobot(a, "orca").rollout(T, obs_every_step=False, noise={"sigma": SIGMA, "seed": SEED, "step0": 0})
+    beams = int(a.config.lidar.cfg["num_beams"])
+    assert out["lidar"].shape == (T, E, 1, 7 + beams) and out["robot_node"].shape[0] == E
+    for t in range(T):
+        o, rew, done, *_ = b.step_device(out["executed"][t])
+        assert torch.equal(o, out["lidar"][t]), t
+        assert torch.equal(done, out["done"][t]) and torch.equal(rew, out["reward"][t]), t
+    assert _blob(a.engine).tobytes() == _blob(b.engine).tobytes()
+    a.close()
+    b.close()
+
+
+@pytest.mark.gpu
+def test_gpu_rollout_lidar_error_codes():
+    import torch
+
+    from crowdnav_dsrnn_amd import _lib
+    from crowdnav_dsrnn_amd.config import make_mixed_cn_configs
+    from crowdnav_dsrnn_amd.engine import CrowdNavEngine
+
+    L = _lib.lib()
+    E8, T4, B = 8, 4, 180
+    z = lambda *s, **k: torch.zeros(s, device="cuda:0", **k)  # noqa: E731
+    bufs = {"actions": z(T4, E8, 2), "robot_node": z(T4, E8, 7), "temporal_edges": z(T4, E8, 2),
+            "spatial_edges": z(T4, E8, 5, 2)}
+    lid = {"obs": z(T4, E8, 7 + B), "robot_state": z(9, T4, E8, dtype=torch.float64),
+           "human_state": z(3, T4, E8, 5, dtype=torch.float64)}
+    ro = _lib.RolloutOut()
+    for k, v in bufs.items():
+        setattr(ro, k, v.data_ptr())
+    ro.flags = 1
+
+    def call(eng, beams=B, max_range=5.0, null=None, sigma=None):
+        nl = ctypes.c_int32(9)
+        ld = _lib.RolloutLidar(*(None if null == k else lid[k].data_ptr() for k in ("obs",)), beams, max_range, 0.3,
+                               *(None if null == k else lid[k].data_ptr() for k in ("robot_state", "human_state")))
+        nz = None if sigma is None else ctypes.byref(_lib.RolloutNoise(sigma, 1, 0, None))
+        rc = L.cn_rollout_lidar(eng._h, None, 0, T4, ctypes.byref(ro), nz, None if null == "lidar" else ctypes.byref(ld),
+                                ctypes.byref(nl))
+        assert nl.value == 0
+        return rc
+
+    uni = CrowdNavEngine(make_cn_config(_config(5, kin="unicycle"), num_envs=E8), "cuda:0")
+    uni.reset()
+    before = _blob(uni)
+    assert call(uni) == EUNSUPPORTED and b"holonomic" in L.cn_last_error()
+    assert _blob(uni).tobytes() == before.tobytes()
+    uni.close()
+    sc = ["parallel_traffic", "perpendicular_traffic"]
+    ca, cb = _config(5), _config(3)
+    ca.sim.train_val_sim = ca.sim.test_sim = cb.sim.train_val_sim = cb.sim.test_sim = sc
+    cfgs, eg = make_mixed_cn_configs({sc[0]: ca, sc[1]: cb}, sc, E8)
+    mixed = CrowdNavEngine.mixed(cfgs, eg, "cuda:0")
+    mixed.reset()
+    assert call(mixed) == EUNSUPPORTED and b"mixed" in L.cn_last_error()
+    mixed.close()
+    eng = CrowdNavEngine(make_cn_config(_config(5), num_envs=E8), "cuda:0")
+    eng.reset()
+    before = _blob(eng)
+    for kw in (dict(null="lidar"), dict(null="obs"), dict(null="robot_state"), dict(null="human_state"),
+               dict(beams=1), dict(beams=4097), dict(max_range=0.0), dict(max_range=2e4), dict(max_range=0.005),
+               dict(sigma=-1.0), dict(sigma=float("nan"))):
+        assert call(eng, **kw) == EINVAL, kw
+        assert _blob(eng).tobytes() == before.tobytes(), kw
+    torch.cuda.synchronize()
+    assert float(bufs["actions"].abs().max()) == 0.0 and float(lid["obs"].abs().max()) == 0.0   # nothing was launched
+    eng.close()

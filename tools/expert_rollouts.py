@@ -19,11 +19,19 @@ is the reset observation: obs[t-1] -> actions[t]). The controller reads the engi
 observation: its belief of the humans (the spatial edges) and its own full state. learner.BehaviourCloning trains on
 the same rollouts straight from the device buffers (tools/imitation_pretrain.py); this file is for other consumers.
 
+--lidar records LiDAR demonstrations for the ConvGRU policy: the env runs with robot.policy 'convgru', lidar.enable and
+lidar.live, and the file also holds (cn_rollout_lidar)
+
+  lidar           (T + 1, E, 1, 7 + beams)   the live LiDAR observation, rows as above (pair: lidar[t] -> actions[t])
+  robot_state     (9, T, E)          the state step t left, float64: r_px, r_py, r_vx, r_vy, r_radius, r_gx, r_gy,
+  human_state     (3, T, E, N)       r_vpref, r_theta and h_px, h_py, h_r -- what the scan of row t + 1 was taken from
+  lidar_beams, lidar_max_range, lidar_robot_radius
+
 --noise-sigma S (m/s) injects noise: the steps take actions + S * uniform[-1, 1) per component (cn_rollout_noisy, seed
 --noise-seed), the labels stay clean; the chunks continue one noise sequence (step0 = steps done so far).
 
 Usage: python tools/expert_rollouts.py --out demos.npz [--robot orca] [--envs 256] [--steps 512] [--humans 5]
-                                       [--seed 0] [--chunk-steps 128] [--noise-sigma S] [--noise-seed K]
+                                       [--seed 0] [--chunk-steps 128] [--noise-sigma S] [--noise-seed K] [--lidar]
 """
 import argparse
 import os
@@ -53,19 +61,30 @@ def main():
     ap.add_argument("--chunk-steps", type=int, default=128, help="steps per rollout call (bounds the device buffers)")
     ap.add_argument("--noise-sigma", type=float, default=None, help="perturb the executed action (labels stay clean)")
     ap.add_argument("--noise-seed", type=int, default=0)
+    ap.add_argument("--lidar", action="store_true", help="record the live LiDAR observation and the state rows as well")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("expert_rollouts: needs a GPU")
     c = clone_config(Config())
     c.sim.human_num = args.humans
     c.action_space.kinematics = "holonomic"
+    if args.lidar:
+        c.robot.policy = "convgru"
+        c.lidar.enable = True
+        c.lidar.live = True
     E, T = args.envs, args.steps
     envs = CrowdNavVecEnv(c, E, args.seed, "cuda:0", allow_early_resets=True, nenv=E, phase="train")
     robot = ScriptedRobot(envs, args.robot)
     obs0 = envs.reset()
-    rows = {k: [obs0[k].reshape((1,) + tuple(obs0[k].shape)).cpu().numpy()] for k in OBS}
+    if args.lidar:   # (the env's observation is the LiDAR row; the SRNN one of the same state is the engine's own)
+        rows = {"lidar": [obs0.reshape((1,) + tuple(obs0.shape)).cpu().numpy()]}
+        obs0 = envs.engine.obs()
+    else:
+        rows = {}
+    rows.update({k: [obs0[k].reshape((1,) + tuple(obs0[k].shape)).cpu().numpy()] for k in OBS})
     step_keys = STEP + (("executed",) if args.noise_sigma is not None else ())
-    rows.update({k: [] for k in step_keys})
+    state_keys = ("robot_state", "human_state") if args.lidar else ()
+    rows.update({k: [] for k in step_keys + state_keys})
     launches, t = 0, 0
     while t < T:
         n = min(args.chunk_steps, T - t)
@@ -75,10 +94,14 @@ def main():
             out = robot.rollout(n, noise={"sigma": args.noise_sigma, "seed": args.noise_seed, "step0": t})
         launches += out["num_launches"]
         torch.cuda.synchronize()
-        for k in OBS + step_keys:
+        for k in OBS + step_keys + state_keys + (("lidar",) if args.lidar else ()):
             rows[k].append(out[k].cpu().numpy())
         t += n
-    data = {k: np.concatenate(v, axis=0) for k, v in rows.items()}
+    data = {k: np.concatenate(v, axis=1 if k in state_keys else 0) for k, v in rows.items()}
+    if args.lidar:
+        lc = c.lidar.cfg
+        data["lidar_beams"], data["lidar_max_range"] = np.array(int(lc["num_beams"])), np.array(float(lc["max_range"]))
+        data["lidar_robot_radius"] = np.array(float(lc["robot_radius"]))
     data["pairing"] = np.array("obs[t] -> actions[t]")
     data["robot"] = np.array(args.robot)
     if args.noise_sigma is not None:

@@ -1,18 +1,21 @@
 #!/usr/bin/env python
-"""Behaviour-cloning pre-training of the DSRNN policy from a scripted expert, with the evaluation rows next to it.
+"""Behaviour-cloning pre-training of the DSRNN policy (or, with --policy convgru, of the ConvGRU policy on the live
+LiDAR observation) from a scripted expert, with the evaluation rows next to it.
 
 For every --sigma-frac f (the noise half-width as a fraction of robot.v_pref; 0 = plain behaviour cloning) a fresh
 DSRNN policy (same initial weights) is cloned from the expert for --updates chunks with learner.BehaviourCloning
 (noise-injected expert rollouts, labels clean) and then run through evaluate() on the default test set
 (--test-size episodes, the four default test scenarios). The untrained policy and the expert itself
 (evaluate_scripted) are evaluated the same way. One JSON line per row: success / collision / timeout rates, updates,
-env steps, the last update's losses and the wall time of the training. --out saves the state_dict of the LAST
+env steps, the last update's losses and the wall time of the training. --policy convgru runs all of it on an env with
+robot.policy 'convgru', lidar.enable and lidar.live: the expert still acts on the full state, the cloned policy sees
+the 180 ranges (the rollouts record them: cn_rollout_lidar), and the same three kinds of row are printed. --out saves the state_dict of the LAST
 sigma's policy (keys as the reference checkpoints'), ready for RolloutTrainer / train.py to continue with PPO.
 Needs a GPU.
 
-Usage: python tools/imitation_pretrain.py [--expert orca] [--updates 3000] [--envs 1024] [--steps 32] [--epochs 1]
+Usage: python tools/imitation_pretrain.py [--policy srnn|convgru] [--expert orca] [--updates 3000] [--envs 1024] [--steps 32] [--epochs 1]
            [--mini-batch 2] [--lr 1e-3] [--value-coef 0.5] [--sigma-frac 0 0.1 0.3] [--humans 5] [--seed 0]
-           [--eval-envs 100] [--test-size 500] [--out policy.pt] [--json FILE]
+           [--eval-envs 100] [--test-size 500] [--log-every K] [--out policy.pt] [--json FILE]
 """
 import argparse
 import json
@@ -44,6 +47,7 @@ def rates(row):
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--policy", default="srnn", choices=("srnn", "convgru"))
     ap.add_argument("--expert", default="orca", choices=ScriptedRobot.NAMES)
     ap.add_argument("--updates", type=int, default=3000)
     ap.add_argument("--envs", type=int, default=1024)
@@ -57,6 +61,7 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--eval-envs", type=int, default=100)
     ap.add_argument("--test-size", type=int, default=500)
+    ap.add_argument("--log-every", type=int, default=0, help="print a progress line to stderr every K updates")
     ap.add_argument("--out", default=None)
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
@@ -68,6 +73,10 @@ def main():
     c = clone_config(Config())
     c.sim.human_num = args.humans
     c.action_space.kinematics = "holonomic"
+    if args.policy == "convgru":
+        c.robot.policy = "convgru"
+        c.lidar.enable = True
+        c.lidar.live = True
     c.env.test_size = args.test_size
     c.training.num_processes = args.envs
     c.ppo.num_steps = args.steps
@@ -84,26 +93,29 @@ def main():
 
     def evaluate_policy(pol):
         envs = test_envs()
-        keep = pol.base.nenv
-        pol.base.nenv = EE
+        keep = getattr(pol.base, "nenv", None)   # (the DSRNN reads its batch shape from attributes)
+        if keep is not None:
+            pol.base.nenv = EE
         try:
             evaluate(pol, None, envs, EE, DEV, c, log, keep_traces=False, verbose=False)
         finally:
-            pol.base.nenv = keep
+            if keep is not None:
+                pol.base.nenv = keep
             envs.close()
 
     def fresh_policy(spaces, action_space):
         torch.manual_seed(args.seed)
-        return Policy(spaces, action_space, base="srnn", base_kwargs=c).to(DEV)
+        return Policy(spaces, action_space, base=args.policy, base_kwargs=c).to(DEV)
 
     envs = test_envs()
     evaluate_scripted(args.expert, envs, EE, DEV, c, log, keep_traces=False, verbose=False)
-    emit(rates({"row": "expert", "expert": args.expert, "episodes": args.test_size}))
-    spaces, action_space = envs.observation_space.spaces, envs.action_space
+    emit(rates({"row": "expert", "policy": args.policy, "expert": args.expert, "episodes": args.test_size}))
+    spaces = envs.observation_space if args.policy == "convgru" else envs.observation_space.spaces
+    action_space = envs.action_space
     envs.close()
     pol = fresh_policy(spaces, action_space)
     evaluate_policy(pol)
-    emit(rates({"row": "untrained", "episodes": args.test_size}))
+    emit(rates({"row": "untrained", "policy": args.policy, "episodes": args.test_size}))
     for frac in args.sigma_frac:
         pol = fresh_policy(spaces, action_space)
         envs = CrowdNavVecEnv(c, E, args.seed, DEV, allow_early_resets=True, nenv=E, phase="train")
@@ -113,15 +125,18 @@ def main():
         t0 = time.time()
         gpu_roll = gpu_upd = 0.0
         first = st = None
-        for _ in range(args.updates):
+        for u in range(args.updates):
             st = bc.update()
             first = first or st
+            if args.log_every and (u + 1) % args.log_every == 0:
+                print("sigma_frac %g update %d nll %.4f value_loss %.4f" % (frac, u + 1, st["nll"], st["value_loss"]),
+                      file=sys.stderr, flush=True)
             gpu_roll += st["rollout_s"]
             gpu_upd += st["update_s"]
         wall = time.time() - t0
         envs.close()
         evaluate_policy(pol)
-        emit(rates({"row": "bc", "expert": args.expert, "sigma_frac": frac, "sigma": frac * float(c.robot.v_pref),
+        emit(rates({"row": "bc", "policy": args.policy, "expert": args.expert, "sigma_frac": frac, "sigma": frac * float(c.robot.v_pref),
                     "updates": args.updates, "envs": E, "steps": args.steps, "epochs": args.epochs, "lr": args.lr,
                     "env_steps": bc.env_steps, "nll_first": round(first["nll"], 4), "nll_last": round(st["nll"], 4),
                     "value_loss_last": round(st["value_loss"], 4), "train_wall_s": round(wall, 2),
