@@ -30,6 +30,10 @@ class Config(object):
     sim.circle_radius = 6 if not test.social_metrics and not test.side_preference else 4
     sim.human_num = 5 if not test.side_preference else 1
     sim.group_human = False
+    # human_nums (this project's opt-in, not a reference option): a list of human counts, e.g. [5, 10] -- the env
+    # with global index g runs human_nums[g % len] humans in ONE mixed engine (make_varied_cn_configs), the
+    # observation is padded to the largest count and carries 'detected_human_num'. None: sim.human_num for all
+    sim.human_nums = None
 
     env = BaseConfig()
     env.env_name = "CrowdSimDict-v0"
@@ -308,4 +312,55 @@ def make_mixed_cn_configs(scenario_configs, scenarios, num_envs, env_offset=0, n
     cfgs = [make_cn_config(c, num_envs=int((env_group == g).sum()), env_offset=env_offset, nenv=nenv, phase=phase,
                            scenarios=list(scenarios), scenario_mode=abi.SCMODE_ROUND_ROBIN, rng=rng)
             for g, c in enumerate(groups)]
+    return cfgs, env_group
+
+
+MAX_VARIED_HUMANS = 31   # the engine's largest human count per env
+
+
+def varied_human_nums(config):
+    """config.sim.human_nums as a list of ints, or None when the opt-in is absent. UnsupportedConfig for an empty
+    list, an entry outside 1..31, or robot.policy 'convgru' (the LiDAR scan does not run on a mixed engine)."""
+    nums = getattr(config.sim, "human_nums", None)
+    if nums is None:
+        return None
+    if isinstance(nums, (str, bytes)) or not hasattr(nums, "__len__"):
+        raise UnsupportedConfig("sim.human_nums=%r (a list of human counts)" % (nums,))
+    nums = list(nums)
+    if not nums:
+        raise UnsupportedConfig("sim.human_nums is empty")
+    for n in nums:
+        if isinstance(n, bool) or int(n) != n or not 1 <= int(n) <= MAX_VARIED_HUMANS:
+            raise UnsupportedConfig("sim.human_nums entry %r (1..%d humans per env)" % (n, MAX_VARIED_HUMANS))
+    if getattr(config.robot, "policy", "srnn") == "convgru":
+        raise UnsupportedConfig("sim.human_nums with robot.policy='convgru' (the LiDAR observation is not served on a "
+                                "mixed engine)")
+    if getattr(config.test, "social_metrics", False):
+        raise UnsupportedConfig("sim.human_nums with test.social_metrics (the mixed engine dispatches scenarios "
+                                "round-robin only)")
+    return [int(n) for n in nums]
+
+
+def make_varied_cn_configs(config, human_nums, num_envs, env_offset=0, nenv=None, phase=None, seed=None, rng=None):
+    """Envs of varying human count for CrowdNavEngine.mixed: one group per distinct count, identical except
+    human_num and each with the full scenario list; the env with global index g = env_offset + r runs
+    human_nums[g % len(human_nums)] humans (shards agree with an unsharded run). Returns (list of cn_config in
+    the order the counts first appear in human_nums, env_group int32 [num_envs]). `config` is not modified."""
+    probe = clone_config(config)
+    probe.sim.human_nums = human_nums
+    nums = varied_human_nums(probe)
+    if nums is None:
+        raise UnsupportedConfig("make_varied_cn_configs: human_nums is None")
+    nenv = num_envs if nenv is None else nenv
+    distinct = []
+    for n in nums:
+        if n not in distinct:
+            distinct.append(n)
+    env_group = np.array([distinct.index(nums[(env_offset + r) % len(nums)]) for r in range(num_envs)], np.int32)
+    cfgs = []
+    for g, n in enumerate(distinct):
+        c = clone_config(config)
+        c.sim.human_num = n
+        cfgs.append(make_cn_config(c, num_envs=int((env_group == g).sum()), env_offset=env_offset, nenv=nenv,
+                                   phase=phase, seed=seed, rng=rng))
     return cfgs, env_group

@@ -13,6 +13,9 @@ VecPyTorch's return types:
     step(action) -> obs dict on `device`, reward (E,1) float32 CPU tensor, done np.ndarray bool (E,),
                     infos: a tuple-like of E dicts {'info': step_info[, 'episode': {r, l, t}]}, built lazily
                     on access from the engine's event codes and metrics (events are info.py instances)
+With config.sim.human_nums (a list of human counts; this project's opt-in) the envs differ in crowd size inside one
+mixed engine: spatial_edges is padded to the largest count and the dict gains 'detected_human_num' (E,1), each env's
+own count; `venv.config` is then a clone of the caller's config whose sim.human_num is that largest count.
 All env work runs on the GPU in one cn_step launch pair; there is no per-env Python and no CPU fallback.
 `step_device(actions)` is the zero-copy variant for on-device rollouts (no host sync).
 
@@ -26,7 +29,7 @@ import time
 import numpy as np
 
 from . import abi, info as info_mod, spaces
-from .config import UnsupportedConfig, make_cn_config
+from .config import UnsupportedConfig, clone_config, make_cn_config, make_varied_cn_configs, varied_human_nums
 
 _REGISTRY = {}
 
@@ -90,6 +93,13 @@ def make_vec_envs(env_name, seed, num_processes, gamma, log_dir, device, allow_e
     E = num_processes // world
     return env_cls(config, E, seed, device, allow_early_resets=allow_early_resets,
                    env_offset=rank * E, nenv=num_processes, engine_device=engine_device)
+
+
+def _no_varied(config, what):
+    """UnsupportedConfig for what an env of varying human count does not serve (read from the config alone)."""
+    if getattr(config.sim, "human_nums", None) is not None:
+        raise UnsupportedConfig("%s: not served on an env of varying human count (config.sim.human_nums: "
+                                "cn_robot_act / cn_rollout do not run on a mixed engine)" % what)
 
 
 class _LazyInfos:
@@ -176,7 +186,7 @@ class _EnvView:
     global_time = property(lambda self: float(self._venv._state().gtime[self._i]))
     time_step = property(lambda self: float(self._venv.config.env.time_step))
     time_limit = property(lambda self: float(self._venv.config.env.time_limit))
-    human_num = property(lambda self: int(self._venv.config.sim.human_num))
+    human_num = property(lambda self: int(self._venv.env_human_nums[self._i]))
     thisSeed = property(lambda self: int(self._venv.cn_cfg.seed + self._venv.cn_cfg.env_offset + self._i))
     nenv = property(lambda self: int(self._venv.cn_cfg.nenv))
     phase = property(lambda self: self._venv.phase)
@@ -211,13 +221,34 @@ class CrowdNavVecEnv:
         self.num_envs = int(num_envs)
         nenv = self.num_envs if nenv is None else int(nenv)
         self.phase = phase if phase is not None else ("train" if nenv > 1 else "test")
-        self.cn_cfg = make_cn_config(config, num_envs=self.num_envs, env_offset=env_offset, nenv=nenv,
-                                     phase=self.phase,
-                                     seed=seed if seed is not None else config.env.seed)
+        seed = seed if seed is not None else config.env.seed
+        # sim.human_nums: envs of varying human count in one mixed engine (UnsupportedConfig, e.g. with 'convgru',
+        # before anything touches the GPU); self.config is then a clone whose sim.human_num is the largest count
+        # (what a Policy over this env's padded observation is built with), the caller's config stays as it is
+        self.human_nums = varied_human_nums(config)
+        mixed = None
+        if self.human_nums is not None:
+            mixed = make_varied_cn_configs(config, self.human_nums, self.num_envs, env_offset=env_offset, nenv=nenv,
+                                           phase=self.phase, seed=seed)
+            self.config = clone_config(config)
+            self.config.sim.human_num = max(self.human_nums)
+            self.cn_cfg = mixed[0][0]
+            self.env_human_nums = [self.human_nums[(env_offset + r) % len(self.human_nums)]
+                                   for r in range(self.num_envs)]
+        else:
+            self.cn_cfg = make_cn_config(config, num_envs=self.num_envs, env_offset=env_offset, nenv=nenv,
+                                         phase=self.phase, seed=seed)
+            self.env_human_nums = [int(config.sim.human_num)] * self.num_envs
         self.device = torch.device(device)
         if engine_device is None and self.device.type == "cuda":
             engine_device = self.device
-        self.engine = CrowdNavEngine(self.cn_cfg, engine_device)
+        if mixed is not None:
+            self.engine = CrowdNavEngine.mixed(mixed[0], mixed[1], engine_device)
+            assert self.engine.env_humans.tolist() == self.env_human_nums
+            # the observation's 'detected_human_num': constant over the env's life, (E, 1) float32 on the engine's GPU
+            self._detected = self.engine.env_humans.to(torch.float32).reshape(self.num_envs, 1)
+        else:
+            self.engine = CrowdNavEngine(self.cn_cfg, engine_device)
         # 'convgru' observation (crowd_sim_dict.py:57-62, 96-101): robot state + the episode's LiDAR scan (or the
         # live one)
         self.obs_mode = "convgru" if getattr(config.robot, "policy", "srnn") == "convgru" else "srnn"
@@ -233,7 +264,8 @@ class CrowdNavVecEnv:
             self._lidar = torch.zeros((self.num_envs, B), dtype=torch.float32, device=self.engine.device)
             self._lidar_obs = torch.zeros((self.num_envs, 1, 7 + B), dtype=torch.float32, device=self.engine.device)
         else:
-            self.observation_space = spaces.observation_space(int(config.sim.human_num))
+            self.observation_space = spaces.observation_space(int(self.config.sim.human_num),
+                                                              detected_human_num=mixed is not None)
         self.action_space = spaces.action_space()
         self.scenario_names = list(abi.SCENARIOS)
         self.side_preference = bool(config.test.side_preference)
@@ -275,6 +307,8 @@ class CrowdNavVecEnv:
         o = self.engine.reset()
         if self.obs_mode == "convgru":
             o = self._convgru_obs(None)
+        elif self.human_nums is not None:
+            o = dict(o, detected_human_num=self._detected)
         return self._obs_out(o)
 
     def step_async(self, actions):
@@ -314,11 +348,14 @@ class CrowdNavVecEnv:
         out = self.engine.step(actions.reshape(self.num_envs, 2))
         if self.obs_mode == "convgru":
             out = (self._convgru_obs(out[2]),) + tuple(out[1:])
+        elif self.human_nums is not None:
+            out = (dict(out[0], detected_human_num=self._detected),) + tuple(out[1:])
         return out
 
     def robot_act(self, policy):
         """The scripted robot's action ('orca' / 'social_force') for the state the last reset / step returned:
         (E, 2) float32 on the engine's GPU (CrowdNavEngine.robot_act; no host synchronisation)."""
+        _no_varied(self.config, "robot_act")
         return self.engine.robot_act(policy)
 
     def rollout(self, policy, T, obs_every_step=True, out=None, noise=None):
@@ -330,6 +367,7 @@ class CrowdNavVecEnv:
         step_device would have returned after every step, and the state rows it was scanned from (the engine's
         rollout with the env's LiDAR settings). Without lidar.live the observation carries the scan held since the
         episode's reset, which is state between steps and no function of a recorded row: UnsupportedConfig."""
+        _no_varied(self.config, "rollout")
         lidar = None
         if self.obs_mode == "convgru":
             if not self._lidar_live:

@@ -24,7 +24,9 @@ class RolloutTrainer:
         # HIP-graph rollouts (collect); CN_NO_GRAPHS=1 or graphs=False: every rollout eager
         if graphs is None:
             graphs = envs.engine.device.type == "cuda" and os.environ.get("CN_NO_GRAPHS", "") in ("", "0")
-        self.graphs = bool(graphs)
+        # graph mode is the plain engine's: an env over a mixed engine (config.sim.human_nums) runs every rollout
+        # eagerly, chosen here and not by a failed capture
+        self.graphs = bool(graphs) and getattr(envs.engine, "groups", None) is None
         self._graph, self._warm = None, False
         self.graph_audit = None   # node census of the captured rollout graph (collect)
         self._ones = self._ep_ret = None

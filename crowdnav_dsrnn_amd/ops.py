@@ -6,12 +6,15 @@ edge_features(...)  — the fused DSRNN input layers (cn_edge_features, include/
 linear(...)         — nn.Linear with a split-K weight gradient (library GEMMs; for the layers applied to
                       T*B or T*B*N rows in training, where dW = dY^T X has a tiny output and K ~ 10^6).
 attention_pool(...) — EdgeAttention's weighted sum of the spatial edge states (cn_attn_pool_*).
+spatial_attention(...) / spatial_attention_var(...) — EdgeAttention's whole spatial branch in one pass
+                      (cn_spatial_attn_*); _var: rows padded to N slots, each with its own human count.
 masked_gru(...)     — the mask-segmented GRU of the three DSRNN RNNs over a (T, B) sequence
                       (cn_gru_fwd_fused: recurrent GEMM on the f32 matrix cores + gates in one launch per
                       step; cn_gru_bwd_step + library GEMMs backward), with its own backward.
 gru_infer_step(...) — one no-autograd step of the same GRU for act(): reads the state through strided views
                       and writes the new state straight into the (B, N + 1, H) layout (cn_gru_fwd_fused).
 """
+import numpy as np
 import torch
 
 from . import _lib
@@ -615,3 +618,78 @@ def spatial_attention(hs, te, ws, bs, scale):
         raise EdgeFeaturesUnavailable("the DSRNN spatial attention runs only as the HIP kernel (cn_spatial_attn_*); "
                                       "tensors are on %s" % hs.device)
     return _SpatialAttn.apply(hs, te, ws, bs, scale)
+
+
+_ROW_SCALE = {}
+
+
+def row_scale_table(N, attention_size, device):
+    """table[n] = float32(n / sqrt(attention_size)) for n = 0..N: the temperature EdgeAttention passes for a
+    whole batch of n humans, so a row of count n gets the value a plain human_num = n policy uses. Kept per
+    (N, attention_size, device): one upload, none per call."""
+    key = (int(N), attention_size, str(device))
+    if key not in _ROW_SCALE:
+        t = np.array([np.float32(n / np.sqrt(attention_size)) for n in range(int(N) + 1)], np.float32)
+        _ROW_SCALE[key] = torch.from_numpy(t).to(device)
+    return _ROW_SCALE[key]
+
+
+class _SpatialAttnVar(torch.autograd.Function):
+    """_SpatialAttn with a per-row human count and temperature (cn_spatial_attn_var_fwd / _bwd): row r attends
+    to its first count[r] slots with row_scale[r]; attn and d hs of the padded slots are zeros and their hs is
+    never read. The host GEMMs (u, c, d te, dWs, dbs) are _SpatialAttn's."""
+
+    @staticmethod
+    def forward(ctx, hs, te, ws, bs, count, row_scale):
+        R, N, H = hs.shape
+        hs, te = _c(hs), _c(te)
+        u = torch.mm(te, ws)                 # (R, H)
+        c = torch.mv(te, bs)                 # (R,)
+        out = torch.empty((R, H), dtype=torch.float32, device=hs.device)
+        attn = torch.empty((R, N), dtype=torch.float32, device=hs.device)
+        with torch.cuda.device(hs.device):
+            _lib.check(_lib.lib().cn_spatial_attn_var_fwd(_stream(hs.device), R, N, H, count.data_ptr(),
+                                                          row_scale.data_ptr(), hs.data_ptr(), u.data_ptr(),
+                                                          c.data_ptr(), out.data_ptr(), attn.data_ptr()))
+        ctx.save_for_backward(hs, te, ws, bs, u, attn, count, row_scale)
+        return out, attn.reshape(R, N, 1)
+
+    @staticmethod
+    def backward(ctx, dout, dattn):
+        hs, te, ws, bs, u, attn, count, row_scale = ctx.saved_tensors
+        R, N, H = hs.shape
+        dev = hs.device
+        dout = _c(dout) if dout is not None else torch.zeros((R, H), dtype=torch.float32, device=dev)
+        da = _c(dattn).reshape(R, N) if dattn is not None else None
+        dhs = torch.empty_like(hs)
+        ld = H + 4                           # [du | dc | pad] rows: dWs and dbs from one split-K GEMM
+        due = torch.empty((R, ld), dtype=torch.float32, device=dev)
+        du, dc = due[:, :H], due[:, H]
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().cn_spatial_attn_var_bwd(_stream(dev), R, N, H, count.data_ptr(),
+                                                          row_scale.data_ptr(), hs.data_ptr(), u.data_ptr(),
+                                                          attn.data_ptr(), dout.data_ptr(),
+                                                          da.data_ptr() if da is not None else None, dhs.data_ptr(),
+                                                          due.data_ptr(), ld, due.data_ptr() + 4 * H, ld))
+        dte = torch.addmm(torch.outer(dc, bs), du, ws.t()) if ctx.needs_input_grad[1] else None
+        dws = dbs = None
+        if ctx.needs_input_grad[2] or ctx.needs_input_grad[3]:
+            g = wgrad(te, due)               # (A, H + 4) = te^T [du | dc | pad]; the pad columns are dropped
+            dws, dbs = g[:, :H].contiguous(), g[:, H].contiguous()
+        return dhs, dte, dws, dbs, None, None
+
+
+def spatial_attention_var(hs, te, ws, bs, count, attention_size):
+    """spatial_attention over rows of varying human count: hs (R, N, H) padded to N slots, count (R,) int32 on
+    the device with 1 <= count[r] <= N (the caller's contract). Row r is the row of a plain N = count[r] batch:
+    its first count[r] slots, the temperature count[r] / sqrt(attention_size); attn (R, N, 1) is 0 in the
+    padded slots, which are never read (cn_spatial_attn_var_*)."""
+    if not hs.is_cuda:
+        raise EdgeFeaturesUnavailable("the DSRNN spatial attention runs only as the HIP kernel "
+                                      "(cn_spatial_attn_var_*); tensors are on %s" % hs.device)
+    R, N, _ = hs.shape
+    if count.dtype != torch.int32 or count.device != hs.device or count.numel() != R:
+        raise ValueError("spatial_attention_var: count must be an int32 (R,) tensor on %s" % hs.device)
+    count = count.reshape(R).contiguous()
+    row_scale = row_scale_table(N, attention_size, hs.device).index_select(0, count.long())
+    return _SpatialAttnVar.apply(hs, te, ws, bs, count, row_scale)

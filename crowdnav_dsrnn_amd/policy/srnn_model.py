@@ -113,10 +113,15 @@ class EdgeAttention(nn.Module):
         self.agent_num = 1
         self.num_attention_head = 1
 
-    def forward(self, h_temporal, h_spatials):
-        """h_temporal (T,B,256), h_spatials (T,B,N,256) -> weighted (T,B,256), attn (T*B,N,1)."""
+    def forward(self, h_temporal, h_spatials, count=None):
+        """h_temporal (T,B,256), h_spatials (T,B,N,256) -> weighted (T,B,256), attn (T*B,N,1).
+        count (T*B,) int32 (optional): the humans of each row, its other slots being padding -- the row attends
+        to its first count slots at the temperature count / sqrt(d) (attn 0 elsewhere), as a policy built at
+        that human_num does."""
         T, B, N, H = h_spatials.shape
         temporal_embed = self.temporal_edge_layer[0](h_temporal)          # (T,B,64)
+        if count is not None:
+            return self._forward_var(temporal_embed, h_spatials, count)
         scale = N / np.sqrt(self.attention_size)                          # temperature = num_edges / sqrt(d)
         if h_spatials.is_cuda and H in (64, 128, 256) and N <= 64:
             # spatial_edge_layer, scores, softmax and pooling in one pass over h_spatials (ops.spatial_attention)
@@ -130,6 +135,32 @@ class EdgeAttention(nn.Module):
         attn = torch.softmax(attn, dim=-1).reshape(T * B, N, 1)
         weighted = ops.attention_pool(h_spatials.reshape(T * B, N, H), attn)  # bmm(hs^T, attn): (T*B, H)
         return weighted.reshape(T, B, H), attn
+
+    def _forward_var(self, temporal_embed, h_spatials, count):
+        T, B, N, H = h_spatials.shape
+        sl = self.spatial_edge_layer[0]
+        if h_spatials.is_cuda and H in (64, 128, 256) and N <= 64:
+            weighted, attn = ops.spatial_attention_var(h_spatials.reshape(T * B, N, H),
+                                                       temporal_embed.reshape(T * B, -1), sl.weight, sl.bias, count,
+                                                       self.attention_size)
+            return weighted.reshape(T, B, H), attn
+        # other sizes: the padded slots are masked out of the softmax (and zeroed, so that nothing they hold
+        # reaches the pooling), the temperature is the row's own
+        real = torch.arange(N, device=h_spatials.device)[None, :] < count.reshape(T * B, 1)      # (T*B,N)
+        hs = h_spatials.reshape(T * B, N, H)
+        hs = torch.where(real.unsqueeze(-1), hs, torch.zeros_like(hs))
+        scale = ops.row_scale_table(N, self.attention_size, h_spatials.device).index_select(0, count.long())
+        attn = (sl(hs) * temporal_embed.reshape(T * B, 1, -1)).sum(-1) * scale.unsqueeze(-1)
+        attn = torch.softmax(attn.masked_fill(~real, float("-inf")), dim=-1).reshape(T * B, N, 1)
+        weighted = ops.attention_pool(hs, attn)
+        return weighted.reshape(T, B, H), attn
+
+    @staticmethod
+    def counts(inputs, rows):
+        """The per-row human counts of an observation dict ('detected_human_num', (..., 1) float32: the key
+        CrowdNav++ uses) as the attention's (rows,) int32; None without the key."""
+        n = inputs.get("detected_human_num") if isinstance(inputs, dict) else None
+        return None if n is None else n.reshape(rows).to(torch.int32)
 
 
 class SRNN(nn.Module):
@@ -203,7 +234,7 @@ class SRNN(nn.Module):
             out_t, h_t = self.humanhumanEdgeRNN_temporal(x_t, h0_t, m)
             out_s, h_s = self.humanhumanEdgeRNN_spatial(x_s, h0_s, m_s)
         out_s = out_s.reshape(T, B, N, H)
-        weighted, _ = self.attn(out_t, out_s)
+        weighted, _ = self.attn(out_t, out_s, EdgeAttention.counts(inputs, T * B))
         outputs, h_n = self.humanNodeRNN(ne.reshape(T, B, 64), out_t, weighted, h_node, m)
 
         rnn_hxs["human_node_rnn"] = h_n.reshape(B, 1, -1)
@@ -250,7 +281,7 @@ class SRNN(nn.Module):
                                                                d_edge[:, 0:1, :])
             out_s = self.humanhumanEdgeRNN_spatial.infer_step(se.reshape(B * N, 64), h_edge[:, 1:, :], m,
                                                               d_edge[:, 1:, :])
-        weighted, _ = self.attn(out_t.view(1, B, H), out_s.view(1, B, N, H))
+        weighted, _ = self.attn(out_t.view(1, B, H), out_s.view(1, B, N, H), EdgeAttention.counts(inputs, B))
         outputs, _ = self.humanNodeRNN(ne.reshape(1, B, 64), out_t.view(1, B, H), weighted, h_node, m, dest=d_node)
         rnn_hxs["human_node_rnn"] = d_node
         rnn_hxs["human_human_edge_rnn"] = d_edge

@@ -263,13 +263,17 @@ class ScriptedRobot:
 
     @classmethod
     def check(cls, venv, name):
-        """UnsupportedConfig for an unknown controller or a unicycle config (before anything touches the GPU)."""
+        """UnsupportedConfig for an unknown controller, a unicycle config or an env of varying human count (before
+        anything touches the GPU)."""
         if name not in cls.NAMES:
             raise UnsupportedConfig("ScriptedRobot: %r (one of %s)" % (name, ", ".join(cls.NAMES)))
         config = venv.config
         if config.action_space.kinematics != "holonomic":
             raise UnsupportedConfig("ScriptedRobot: action_space.kinematics=%r (the controllers return ActionXY: "
                                     "holonomic only)" % config.action_space.kinematics)
+        if getattr(config.sim, "human_nums", None) is not None:
+            raise UnsupportedConfig("ScriptedRobot: an env of varying human count (config.sim.human_nums): "
+                                    "cn_robot_act / cn_rollout do not run on a mixed engine")
 
     @classmethod
     def check_rollout(cls, venv, name):

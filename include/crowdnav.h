@@ -50,6 +50,9 @@
  *   cn_spatial_attn_fwd / cn_spatial_attn_bwd ⟵ EdgeAttention's whole spatial branch (spatial_edge_layer,
  *                   att_func's scores and softmax, the pooling: srnn_model.py:256-333) in one pass over
  *                   h_spatials, and its gradient (the training and act() paths use these)
+ *   cn_spatial_attn_var_fwd / cn_spatial_attn_var_bwd ⟵ (no reference counterpart) the same with a per-row
+ *                   human count and temperature: the rows of envs with different crowd sizes, padded to the
+ *                   largest, in one launch (observation key 'detected_human_num')
  *
  * Conventions
  *   - All array arguments are DEVICE pointers (torch tensors' data_ptr()), row-major, caller-owned.
@@ -638,6 +641,18 @@ int cn_spatial_attn_fwd(void *stream, int64_t R, int N, int H, float scale, cons
 int cn_spatial_attn_bwd(void *stream, int64_t R, int N, int H, float scale, const float *hs, const float *u,
                         const float *attn, const float *dout, const float *dattn, float *dhs, float *du, int64_t ldu,
                         float *dc, int64_t ldc);
+
+/* cn_spatial_attn_fwd / _bwd with a per-row human count (rows padded to N slots: a policy over crowds of
+ * varying size): row r attends to its first count[r] slots only (1 <= count[r] <= N, int32 [R]; the caller's
+ * contract, not validated on the device) with its own temperature row_scale[r] (float [R]), and is computed as
+ * the pair above computes a row at N = count[r], scale = row_scale[r] (same operation order). attn[r][n] and
+ * dhs[r][n][:] for n >= count[r] are written as zeros; hs[r][n] and dattn[r][n] are never read there.
+ * Shapes, alignment and strides as above; count and row_scale non-null. No allocation, sync or memset. */
+int cn_spatial_attn_var_fwd(void *stream, int64_t R, int N, int H, const int32_t *count, const float *row_scale,
+                            const float *hs, const float *u, const float *c, float *out, float *attn);
+int cn_spatial_attn_var_bwd(void *stream, int64_t R, int N, int H, const int32_t *count, const float *row_scale,
+                            const float *hs, const float *u, const float *attn, const float *dout, const float *dattn,
+                            float *dhs, float *du, int64_t ldu, float *dc, int64_t ldc);
 
 /* Weight gradient of a Linear layer over K rows with a tiny side (ops.linear / the fused input layers'
  * backward, replacing torch's dy^T x in the reference's autograd of srnn_model.py:160-161,210-211,466 and
