@@ -34,6 +34,10 @@ class Config(object):
     # with global index g runs human_nums[g % len] humans in ONE mixed engine (make_varied_cn_configs), the
     # observation is padded to the largest count and carries 'detected_human_num'. None: sim.human_num for all
     sim.human_nums = None
+    # human_nums_scripted (with human_nums; holonomic): the env also serves the scripted controllers -- robot_act,
+    # rollout, ScriptedRobot, evaluate_scripted, BehaviourCloning (the mixed engine's cn_mixed_scripted opt-in).
+    # Off, the default, those refuse an env of varying human count with UnsupportedConfig, as before.
+    sim.human_nums_scripted = False
 
     env = BaseConfig()
     env.env_name = "CrowdSimDict-v0"

@@ -2615,6 +2615,10 @@ struct RolloutRows {
     int64_t rows;
 };
 #define CN_ROWS_W 22   // in uint32 words from work_count
+// A group of a mixed engine: the envs of the whole engine, i.e. the rows of one step in the (T, E, ..) buffers of a
+// rollout launch (word CN_ER_W of the group's work_count, behind the RolloutRows block; written once by
+// cn_create_mixed). A plain engine's rows are its own E and the word is not read.
+#define CN_ER_W 30
 
 // field f of the state rows: its array in the blob
 __device__ __forceinline__ const double *state_row_robot_field(const cn_state_ptrs &S, int f)
@@ -2910,7 +2914,9 @@ __global__ void __launch_bounds__(CN_BLK, 3) cn_step_kernel(StepArgs g, cn_confi
     const double dt = c.time_step;
 
     const float *actions = g.actions;
-    if constexpr (ROBOT) actions += (int64_t)step * (2 * (int64_t)g.E);
+    // rows of one step in the caller's (T, E, ..) buffers: a group of a mixed engine records into the mixed engine's
+    const int64_t erow = (MIX && ROBOT) ? (int64_t)((const int32_t *)g.pend.stats)[CN_ER_W - 8] : (int64_t)g.E;
+    if constexpr (ROBOT) actions += (int64_t)step * (2 * erow);
     else if constexpr (SEQ) actions += (int64_t)step * g.action_stride;
     // SEQ: the caller reads the outputs of the launch's last step only (every step would overwrite them), so the
     // earlier steps neither convert nor store them (wave-uniform; state writes are not outputs and stay)
@@ -2928,7 +2934,7 @@ __global__ void __launch_bounds__(CN_BLK, 3) cn_step_kernel(StepArgs g, cn_confi
     // that stores the row (wave-uniform; folds to true as emit does). Everything the reward, done or the state
     // depend on (sl.cd, the collision index, LF_ENDGOAL, the NaN bit, R_D2G, R_BITS, last_ax / last_ay) stays.
     const bool info_on = (SEQ && !ROBOT && CN_SEQ_INFO_LAST) ? emit : true;
-    const int64_t orw_e = ROBOT ? (int64_t)step * g.E : 0;
+    const int64_t orw_e = ROBOT ? (int64_t)step * erow : 0;
     const int64_t orw_o = obs_rows ? orw_e : 0;
     if constexpr (ROBOT) {
         // ---- the scripted robot: wave 0, from the global state (this workgroup's own envs; its previous step's
@@ -2951,10 +2957,11 @@ __global__ void __launch_bounds__(CN_BLK, 3) cn_step_kernel(StepArgs g, cn_confi
                     float ax, ay;
                     if (nn > vpref) { ax = (float)(ddiv(nx, nn) * vpref); ay = (float)(ddiv(ny, nn) * vpref); }
                     else { ax = (float)nx; ay = (float)ny; }
-                    arow[2 * (int64_t)(e0 + tid)] = ax; arow[2 * (int64_t)(e0 + tid) + 1] = ay;
+                    const int64_t oa = orow(ov, e0 + tid);   // the env's row in the caller's buffers (and noise key)
+                    arow[2 * oa] = ax; arow[2 * oa + 1] = ay;
                     if (noisy) {
-                        rollout_noise(nz.sigma, nz.seed, nk, (uint32_t)(c.env_offset + e0 + tid), ax, ay, ax, ay);
-                        if (xrow) { xrow[2 * (int64_t)(e0 + tid)] = ax; xrow[2 * (int64_t)(e0 + tid) + 1] = ay; }
+                        rollout_noise(nz.sigma, nz.seed, nk, (uint32_t)(c.env_offset + oa), ax, ay, ax, ay);
+                        if (xrow) { xrow[2 * oa] = ax; xrow[2 * oa + 1] = ay; }
                     }
                     sl.act[tid] = ax; sl.act[EPB + tid] = ay;
                 }
@@ -2972,10 +2979,11 @@ __global__ void __launch_bounds__(CN_BLK, 3) cn_step_kernel(StepArgs g, cn_confi
                     float rx, ry;
                     robot_orca_solve(S, e, cnt, sq, Lq, rx, ry);
                     if (sq == 0) {
-                        arow[2 * e] = rx; arow[2 * e + 1] = ry;
+                        const int64_t oa = orow(ov, e);   // (addresses only: the quad's lanes and flow are as ever)
+                        arow[2 * oa] = rx; arow[2 * oa + 1] = ry;
                         if (noisy) {
-                            rollout_noise(nz.sigma, nz.seed, nk, (uint32_t)(c.env_offset + e), rx, ry, rx, ry);
-                            if (xrow) { xrow[2 * e] = rx; xrow[2 * e + 1] = ry; }
+                            rollout_noise(nz.sigma, nz.seed, nk, (uint32_t)(c.env_offset + oa), rx, ry, rx, ry);
+                            if (xrow) { xrow[2 * oa] = rx; xrow[2 * oa + 1] = ry; }
                         }
                         sl.act[q] = rx; sl.act[EPB + q] = ry;
                     }

@@ -248,7 +248,10 @@ __global__ void __launch_bounds__(64) cn_sf_predict_kernel(int64_t n, int M, con
 // cn_robot_act: the scripted robot (ORCA / social force) on the engine's CURRENT state, read straight from
 // the blob: policy_factory[name](config).predict(JointState(robot FullState, [ObservableState(b_px, b_py,
 // b_vx, b_vy, b_r) of the N humans in index order])) of a fresh policy object per env, rounded to float32.
-// Pure functions of the state (nothing held between calls), one launch each.
+// Pure functions of the state (nothing held between calls), one launch each (a mixed engine: one per group).
+// Each has a twin for a group of a mixed engine (cn_robot_*_mix_kernel: the same body with MIX), where env e's action
+// goes to row rows[e] of `actions`. The map changes that address alone, never which lanes run; the plain kernels
+// carry no argument for it and compile as before.
 // ------------------------------------------------------------------------------------------------
 // (robot_sim_agent, robot_pref_velocity, robot_orca_lines / robot_orca_solve and robot_sf_velocity are defined above
 // cn_step_kernel, whose rollout variant computes the same actions inside its multi-step launches)
@@ -271,11 +274,34 @@ __global__ void __launch_bounds__(64) cn_robot_orca_kernel(cn_state_ptrs S, int 
         if (sq == 0) { actions[2 * e] = rx; actions[2 * e + 1] = ry; }
     }
 }
+// (the twin restates the dozen lines above: as a shared body the plain kernel came out with other registers)
+__global__ void __launch_bounds__(64) cn_robot_orca_mix_kernel(cn_state_ptrs S, int E, int N, double safety, float nd,
+                                                               float th, float ts, float *__restrict__ actions,
+                                                               const int32_t *__restrict__ rows)
+{
+    __shared__ float4 Ls[16][9];
+    const int q = threadIdx.x >> 2, sq = threadIdx.x & 3;
+    const int64_t e = (int64_t)blockIdx.x * 16 + q;
+    const bool act = e < E;
+    int cnt = 0;
+    if (act) cnt = robot_orca_lines(S, safety, e, N, sq, nd, th, ts, Ls[q]);
+    wsync();
+    if (act) {
+        float rx, ry;
+        robot_orca_solve(S, e, cnt, sq, Ls[q], rx, ry);
+        if (sq == 0) {
+            const int64_t o = rows[e];
+            actions[2 * o] = rx; actions[2 * o + 1] = ry;
+        }
+    }
+}
 
 // ORCA, N + 1 > 10 agents: cn_orca_kd_kernel's path with a fresh simulator's identity agent order (LDS sized by
 // A = N + 1: orca_kd_lds)
-__global__ void __launch_bounds__(64) cn_robot_orca_kd_kernel(cn_state_ptrs S, int E, int N, double safety, float nd,
-                                                              float th, float ts, float *__restrict__ actions)
+template <bool MIX>
+__device__ __forceinline__ void robot_orca_kd_body(const cn_state_ptrs &S, int E, int N, double safety, float nd,
+                                                   float th, float ts, float *__restrict__ actions,
+                                                   const int32_t *__restrict__ rows)
 {
     extern __shared__ __attribute__((aligned(16))) char kd_smem[];
     const int A = N + 1;
@@ -317,36 +343,67 @@ __global__ void __launch_bounds__(64) cn_robot_orca_kd_kernel(cn_state_ptrs S, i
         robot_pref_velocity(S, e, vmax, ox, oy);
         const int fail_at = lp2_q<uint64_t>(Lq, cnt, vmax, ox, oy, sq, rx, ry);
         if (fail_at < cnt) lp3_q<uint64_t>(Lq, Pq, cnt, fail_at, vmax, sq, rx, ry);
-        if (sq == 0) { actions[2 * e] = rx; actions[2 * e + 1] = ry; }
+        if (sq == 0) {
+            const int64_t o = MIX ? (int64_t)rows[e] : e;
+            actions[2 * o] = rx; actions[2 * o + 1] = ry;
+        }
     }
+}
+__global__ void __launch_bounds__(64) cn_robot_orca_kd_kernel(cn_state_ptrs S, int E, int N, double safety, float nd,
+                                                              float th, float ts, float *__restrict__ actions)
+{
+    robot_orca_kd_body<false>(S, E, N, safety, nd, th, ts, actions, nullptr);
+}
+__global__ void __launch_bounds__(64) cn_robot_orca_kd_mix_kernel(cn_state_ptrs S, int E, int N, double safety, float nd,
+                                                                  float th, float ts, float *__restrict__ actions,
+                                                                  const int32_t *__restrict__ rows)
+{
+    robot_orca_kd_body<true>(S, E, N, safety, nd, th, ts, actions, rows);
 }
 
 // Social force: cn_sf_predict_kernel's float64 arithmetic on the robot's FullState and the N belief humans,
 // one lane per env; the ActionXY rounded to float32
-__global__ void __launch_bounds__(64) cn_robot_sf_kernel(cn_state_ptrs S, int E, int N, double A, double B, double KI,
-                                                         double dt, float *__restrict__ actions)
+template <bool MIX>
+__device__ __forceinline__ void robot_sf_body(const cn_state_ptrs &S, int E, int N, double A, double B, double KI,
+                                              double dt, float *__restrict__ actions, const int32_t *__restrict__ rows)
 {
     const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= E) return;
     double nx, ny, nn, vpref;
     robot_sf_velocity(S, e, N, A, B, KI, dt, nx, ny, nn, vpref);
-    if (nn > vpref) { actions[2 * e] = (float)(ddiv(nx, nn) * vpref); actions[2 * e + 1] = (float)(ddiv(ny, nn) * vpref); }
-    else { actions[2 * e] = (float)nx; actions[2 * e + 1] = (float)ny; }
+    const int64_t o = MIX ? (int64_t)rows[e] : e;
+    if (nn > vpref) { actions[2 * o] = (float)(ddiv(nx, nn) * vpref); actions[2 * o + 1] = (float)(ddiv(ny, nn) * vpref); }
+    else { actions[2 * o] = (float)nx; actions[2 * o + 1] = (float)ny; }
+}
+__global__ void __launch_bounds__(64) cn_robot_sf_kernel(cn_state_ptrs S, int E, int N, double A, double B, double KI,
+                                                         double dt, float *__restrict__ actions)
+{
+    robot_sf_body<false>(S, E, N, A, B, KI, dt, actions, nullptr);
+}
+__global__ void __launch_bounds__(64) cn_robot_sf_mix_kernel(cn_state_ptrs S, int E, int N, double A, double B, double KI,
+                                                             double dt, float *__restrict__ actions,
+                                                             const int32_t *__restrict__ rows)
+{
+    robot_sf_body<true>(S, E, N, A, B, KI, dt, actions, rows);
 }
 
 // cn_rollout_noisy outside the fused launches: the perturbation between cn_robot_act's kernel and the step. `act` is
 // the clean row the robot kernel wrote, `x` the engine's (E, 2) scratch the step reads, `executed` the caller's row
-// or null; rollout_noise's arithmetic, one lane per env.
+// or null; rollout_noise's arithmetic, one lane per env. A group of a mixed engine (`rows`; null: the identity)
+// works on its envs' rows of the three buffers, all of the mixed engine's E rows, and keys the noise by the row: the
+// global env index, as the fused launches do.
 __global__ void __launch_bounds__(64) cn_action_noise_kernel(const float *__restrict__ act, float *__restrict__ x,
                                                              float *__restrict__ executed, int E, float sigma,
-                                                             uint32_t seed, uint32_t k, uint32_t G0)
+                                                             uint32_t seed, uint32_t k, uint32_t G0,
+                                                             const int32_t *__restrict__ rows)
 {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= E) return;
+    const int64_t o = rows ? (int64_t)rows[e] : (int64_t)e;
     float x0, x1;
-    rollout_noise(sigma, seed, k, G0 + (uint32_t)e, act[2 * (int64_t)e], act[2 * (int64_t)e + 1], x0, x1);
-    x[2 * (int64_t)e] = x0; x[2 * (int64_t)e + 1] = x1;
-    if (executed) { executed[2 * (int64_t)e] = x0; executed[2 * (int64_t)e + 1] = x1; }
+    rollout_noise(sigma, seed, k, G0 + (uint32_t)o, act[2 * o], act[2 * o + 1], x0, x1);
+    x[2 * o] = x0; x[2 * o + 1] = x1;
+    if (executed) { executed[2 * o] = x0; executed[2 * o + 1] = x1; }
 }
 
 // cn_rollout_noisy's device block for the fused launches that follow on the stream (a kernel for the reason

@@ -108,6 +108,7 @@ int cn_create(const cn_config *cfg, int device, cn_engine **out)
     g->E = cfg->num_envs;
     g->N = cfg->human_num;
     g->NS = g->N;
+    g->ER = g->E;
     g->A = cn_sim_agents(g->N, cfg->robot_visible);
     g->plan = cn_step_plan(g->N, cfg->robot_visible);
     g->state_bytes = cn_state_layout(g->E, g->N, cfg->robot_visible, nullptr);
@@ -233,7 +234,7 @@ int cn_create_mixed(const cn_config *groups, int num_groups, const int32_t *env_
     m->c.num_envs = (int32_t)num_envs;
     m->c.human_num = NS;
     m->device = device;
-    m->E = (int)num_envs;
+    m->E = m->ER = (int)num_envs;
     m->N = m->NS = NS;
     m->grp = new cn_engine *[num_groups]();
     for (int k = 0; k < num_groups; ++k) {
@@ -242,6 +243,18 @@ int cn_create_mixed(const cn_config *groups, int num_groups, const int32_t *env_
         if (rc) { cn_destroy(m); return rc; }
         cn_engine *g = m->grp[m->ngroups++];
         g->NS = NS;
+        g->ER = (int)num_envs;
+        if (hipMemcpy(g->work_count + CN_ER_W, &g->ER, sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) {
+            cn_destroy(m);
+            return set_err(CN_EHIP, "hipMemcpy failed");
+        }
+        // the perturbed actions of a launch triple lie at the envs' rows, like every buffer a group's step reads
+        (void)hipFree(g->act_x);
+        g->act_x = nullptr;
+        if (hipMalloc(&g->act_x, sizeof(float) * 2 * (num_envs + 64)) != hipSuccess) {
+            cn_destroy(m);
+            return set_err(CN_ENOMEM, "hipMalloc failed");
+        }
         if (hipMalloc(&g->rows, sizeof(int32_t) * rows[k].size()) != hipSuccess) {
             cn_destroy(m);
             return set_err(CN_ENOMEM, "hipMalloc failed");
@@ -357,6 +370,39 @@ void cn_destroy(cn_engine *g)
     delete g;
 }
 
+// A mixed engine's groups work side by side on disjoint envs and rows: group 0 on the caller's stream, group
+// k > 0 on its own, which waits for the caller's prior work (mix_fork) and which the caller's next work waits for
+// (mix_join). One fork and one join bracket everything a call launches for the groups.
+static hipStream_t mix_stream(const cn_engine *m, int k, hipStream_t st) { return k > 0 ? m->gstream[k] : st; }
+
+static int mix_fork(cn_engine *m, hipStream_t st)
+{
+    if (m->ngroups < 2) return CN_OK;
+    HIPCHK(hipEventRecord(m->gev[0], st));
+    for (int k = 1; k < m->ngroups; ++k) HIPCHK(hipStreamWaitEvent(m->gstream[k], m->gev[0], 0));
+    return CN_OK;
+}
+
+// (also after a failed launch, so that no side-stream work outlives the caller's order)
+static int mix_join(cn_engine *m, hipStream_t st)
+{
+    hipError_t e = hipSuccess;
+    for (int k = 1; k < m->ngroups; ++k) {
+        const hipError_t e1 = hipEventRecord(m->gev[k], m->gstream[k]);
+        const hipError_t e2 = hipStreamWaitEvent(st, m->gev[k], 0);
+        if (e == hipSuccess) e = e1 != hipSuccess ? e1 : e2;
+    }
+    return e == hipSuccess ? CN_OK : set_err(CN_EHIP, "HIP error: %s", hipGetErrorString(e));
+}
+
+// every env holonomic (the scripted controllers return ActionXY)
+static bool all_holonomic(const cn_engine *g)
+{
+    for (int k = 0; k < g->ngroups; ++k)
+        if (g->grp[k]->c.kinematics != CN_HOLONOMIC) return false;
+    return g->ngroups || g->c.kinematics == CN_HOLONOMIC;
+}
+
 int cn_reset(cn_engine *g, void *stream, float *robot_node, float *temporal, float *spatial)
 {
     if (!g || !robot_node || !temporal || !spatial) return set_err(CN_EINVAL, "null argument");
@@ -393,7 +439,7 @@ int cn_reset(cn_engine *g, void *stream, float *robot_node, float *temporal, flo
 }
 
 // One step launch. nsteps == 1: cn_step's launch (every engine, graph mode). nsteps > 1: a multi-step launch of
-// cn_step_seq (a plain quad-path engine outside graph mode, pend_all == 0: seq_fusable), whose step workgroups
+// cn_step_seq (a quad-path engine or group outside graph mode, pend_all == 0: seq_fusable), whose step workgroups
 // run nsteps steps with the actions at actions + t * action_stride. g->nstep counts LAUNCHES (the triple-buffer
 // index of the spawn lists, the launch id, graph mode's hand-over); cn_profile's window counts STEPS.
 // rollout >= 0 (cn_rollout's fused launches, nsteps >= 1, same engines): StepArgs::rollout of the ROBOT kernels,
@@ -459,8 +505,8 @@ static int step_launch(cn_engine *g, void *stream, const float *actions, int nst
     const bool phx = g->c.rng_mode == CN_RNG_PHILOX;
     (void)hipGetLastError();   // a stale error of an earlier call (any library) is not this launch's
     const bool multi = nsteps > 1 || rollout >= 0;
-    if (multi && (g->devseq || g->rows || g->plan.kd || a.pend.all))
-        return set_err(CN_EINVAL, "multi-step launch: plain quad-path engine outside graph mode required");
+    if (multi && (g->devseq || g->plan.kd || a.pend.all || (rec && g->rows)))
+        return set_err(CN_EINVAL, "multi-step launch: quad-path engine outside graph mode required");
     const StepMode mode = rollout >= 0 ? (rec ? STEP_ROBOT_REC : STEP_ROBOT)
                           : nsteps > 1 ? STEP_SEQ : g->devseq ? STEP_DEVSEQ : STEP_SINGLE;
     const StepKernelFn kern = step_kernel_for(g->plan.kd, phx, g->rows != nullptr, mode);
@@ -482,17 +528,15 @@ int cn_step(cn_engine *g, void *stream, const float *actions, float *robot_node,
 
 // T steps as ceil(T / C) multi-step launches of up to C = seq_chunk steps (the last one of the remainder), with
 // the results of T cn_step launches bit for bit. A launch per step where the multi-step kernels do not apply:
-// C == 1, mixed engines, graph mode, the kd-tree path (> 10 agents per simulator), and the first launch after
+// C == 1, graph mode, the kd-tree path (> 10 agents per simulator), and the first launch after
 // cn_reset / cn_set_state (pend_all != 0: its spawn waves redraw or ignore the pending lists; the chunks start
-// after it).
-int cn_step_seq(cn_engine *g, void *stream, int T, const float *actions, int64_t action_stride, float *robot_node,
-                float *temporal, float *spatial, float *reward, uint8_t *done, int8_t *event, float *info,
-                double *ep_return, int32_t *ep_len)
+// after it). g: a plain engine, a group of a mixed engine on its own stream (the rule applies to the group's
+// own count), or a mixed engine stepped as a whole (fuse false: a launch per group and step, cn_step's).
+static int step_seq_run(cn_engine *g, void *stream, bool fuse, int T, const float *actions, int64_t action_stride,
+                        float *robot_node, float *temporal, float *spatial, float *reward, uint8_t *done, int8_t *event,
+                        float *info, double *ep_return, int32_t *ep_len)
 {
-    if (!g || !actions) return set_err(CN_EINVAL, "null argument");
-    if (T < 0 || (T > 1 && action_stride < 2 * g->E))
-        return set_err(CN_EINVAL, "cn_step_seq: T >= 0 and action_stride >= 2 * E required");
-    const bool fusable = g->seq_chunk > 1 && !g->ngroups && !g->rows && !g->devseq && !g->plan.kd;
+    const bool fusable = fuse && g->seq_chunk > 1 && !g->ngroups && !g->devseq && !g->plan.kd;
     for (int t = 0; t < T;) {
         int n = 1;
         if (fusable && !g->pend_all) {
@@ -507,6 +551,32 @@ int cn_step_seq(cn_engine *g, void *stream, int T, const float *actions, int64_t
         t += n;
     }
     return CN_OK;
+}
+
+// A mixed engine: every group runs its whole T-step sequence on its own stream (the groups never read each
+// other's rows), one fork before the first and one join after the last launch of the call. While a cn_profile
+// window is open the mixed engine steps as a whole, a step at a time, so that the window counts steps.
+int cn_step_seq(cn_engine *g, void *stream, int T, const float *actions, int64_t action_stride, float *robot_node,
+                float *temporal, float *spatial, float *reward, uint8_t *done, int8_t *event, float *info,
+                double *ep_return, int32_t *ep_len)
+{
+    if (!g || !actions) return set_err(CN_EINVAL, "null argument");
+    if (T < 0 || (T > 1 && action_stride < 2 * g->E))
+        return set_err(CN_EINVAL, "cn_step_seq: T >= 0 and action_stride >= 2 * E required");
+    if (!g->ngroups || (g->prof_on && g->prof_n < g->prof_cap) || T == 0) {
+        if (T > 0 && (!robot_node || !temporal || !spatial)) return set_err(CN_EINVAL, "null argument");
+        return step_seq_run(g, stream, !g->ngroups, T, actions, action_stride, robot_node, temporal, spatial, reward,
+                            done, event, info, ep_return, ep_len);
+    }
+    if (!robot_node || !temporal || !spatial) return set_err(CN_EINVAL, "null argument");
+    const hipStream_t st = (hipStream_t)stream;
+    int rc = mix_fork(g, st);
+    if (rc) return rc;
+    for (int k = 0; k < g->ngroups && !rc; ++k)
+        rc = step_seq_run(g->grp[k], (void *)mix_stream(g, k, st), true, T, actions, action_stride, robot_node,
+                          temporal, spatial, reward, done, event, info, ep_return, ep_len);
+    const int rj = mix_join(g, st);
+    return rc ? rc : rj;
 }
 
 int cn_set_graph_mode(cn_engine *g, void *stream, int on)
@@ -635,7 +705,7 @@ int cn_debug_set_spawn_budget(cn_engine *g, long long cycles)
 int cn_debug_set_seq_chunk(cn_engine *g, int n)
 {
     if (!g || n < 1) return set_err(CN_EINVAL, "cn_debug_set_seq_chunk: engine and n >= 1 required");
-    for (int k = 0; k < g->ngroups; ++k) cn_debug_set_seq_chunk(g->grp[k], n);   // (mixed engines step per launch)
+    for (int k = 0; k < g->ngroups; ++k) cn_debug_set_seq_chunk(g->grp[k], n);   // (each group chunks its own steps)
     g->seq_chunk = n;
     return CN_OK;
 }
@@ -727,74 +797,99 @@ int cn_lidar_scan(cn_engine *g, void *stream, int beams, double max_range, doubl
     return lidar_scan_launch(g, (hipStream_t)stream, g->s, g->E, beams, npts, max_range, robot_radius, obs, nullptr);
 }
 
+// cn_robot_act's launch for a plain engine or a group of a mixed engine (its own count picks the kernel; its envs'
+// actions go to their rows of the caller's buffer)
+static int robot_act_launch(const cn_engine *g, hipStream_t st, int policy, float *actions)
+{
+    const cn_config &c = g->c;
+    const int32_t *const rows = g->rows;   // a group: the *_mix_kernel twins (the same bodies, the actions at rows[e])
+    const dim3 quads((unsigned)((g->E + 15) / 16)), lanes((unsigned)((g->E + 63) / 64));
+    const float nd = (float)c.orca_neighbor_dist, th = (float)c.orca_time_horizon, ts = (float)c.time_step;
+    (void)hipGetLastError();   // a stale error of an earlier call (any library) is not this launch's
+    if (policy == CN_ROBOT_SOCIAL_FORCE) {
+        if (rows)
+            hipLaunchKernelGGL(cn_robot_sf_mix_kernel, lanes, dim3(64), 0, st, g->s, g->E, g->N, c.sf_A, c.sf_B, c.sf_KI,
+                               c.time_step, actions, rows);
+        else
+            hipLaunchKernelGGL(cn_robot_sf_kernel, lanes, dim3(64), 0, st, g->s, g->E, g->N, c.sf_A, c.sf_B, c.sf_KI,
+                               c.time_step, actions);
+    } else if (g->N + 1 > 10) {
+        if (rows)
+            hipLaunchKernelGGL(cn_robot_orca_kd_mix_kernel, quads, dim3(64), orca_kd_lds(g->N + 1), st, g->s, g->E, g->N,
+                               c.orca_safety_space, nd, th, ts, actions, rows);
+        else
+            hipLaunchKernelGGL(cn_robot_orca_kd_kernel, quads, dim3(64), orca_kd_lds(g->N + 1), st, g->s, g->E, g->N,
+                               c.orca_safety_space, nd, th, ts, actions);
+    } else {
+        if (rows)
+            hipLaunchKernelGGL(cn_robot_orca_mix_kernel, quads, dim3(64), 0, st, g->s, g->E, g->N, c.orca_safety_space, nd,
+                               th, ts, actions, rows);
+        else
+            hipLaunchKernelGGL(cn_robot_orca_kernel, quads, dim3(64), 0, st, g->s, g->E, g->N, c.orca_safety_space, nd, th,
+                               ts, actions);
+    }
+    HIPCHK(hipGetLastError());
+    return CN_OK;
+}
+
+// The scripted calls on a mixed engine are an opt-in of the engine (off: they refuse it as they always have).
+int cn_mixed_scripted(cn_engine *g, int on)
+{
+    if (!g) return set_err(CN_EINVAL, "null engine");
+    if (!g->ngroups) return set_err(CN_EINVAL, "cn_mixed_scripted: a mixed engine (cn_create_mixed) required");
+    g->scripted = on ? 1 : 0;
+    return CN_OK;
+}
+
+// A mixed engine (after cn_mixed_scripted): one controller launch per group, side by side like the groups' step
+// launches.
 int cn_robot_act(cn_engine *g, void *stream, int policy, float *actions)
 {
     if (!g) return set_err(CN_EINVAL, "null engine");
     if ((policy != CN_ROBOT_ORCA && policy != CN_ROBOT_SOCIAL_FORCE) || !actions)
         return set_err(CN_EINVAL, "cn_robot_act: policy CN_ROBOT_ORCA / CN_ROBOT_SOCIAL_FORCE and actions required");
-    if (g->ngroups) return set_err(CN_EUNSUPPORTED, "cn_robot_act: not on a mixed engine");
-    if (g->c.kinematics != CN_HOLONOMIC)
-        return set_err(CN_EUNSUPPORTED, "cn_robot_act: the controllers return ActionXY (holonomic engines only)");
-    const cn_config &c = g->c;
+    if (g->ngroups && !g->scripted)
+        return set_err(CN_EUNSUPPORTED, "cn_robot_act: not on a mixed engine (unless cn_mixed_scripted enabled it)");
+    if (!all_holonomic(g))
+        return set_err(CN_EUNSUPPORTED, g->ngroups ? "cn_robot_act: not on a unicycle mixed engine (the controllers return ActionXY)"
+                                                   : "cn_robot_act: the controllers return ActionXY (holonomic engines only)");
     const hipStream_t st = (hipStream_t)stream;
-    (void)hipGetLastError();   // a stale error of an earlier call (any library) is not this launch's
-    if (policy == CN_ROBOT_SOCIAL_FORCE)
-        hipLaunchKernelGGL(cn_robot_sf_kernel, dim3((unsigned)((g->E + 63) / 64)), dim3(64), 0, st, g->s, g->E, g->N,
-                           c.sf_A, c.sf_B, c.sf_KI, c.time_step, actions);
-    else if (g->N + 1 > 10)
-        hipLaunchKernelGGL(cn_robot_orca_kd_kernel, dim3((unsigned)((g->E + 15) / 16)), dim3(64), orca_kd_lds(g->N + 1),
-                           st, g->s, g->E, g->N, c.orca_safety_space, (float)c.orca_neighbor_dist,
-                           (float)c.orca_time_horizon, (float)c.time_step, actions);
-    else
-        hipLaunchKernelGGL(cn_robot_orca_kernel, dim3((unsigned)((g->E + 15) / 16)), dim3(64), 0, st, g->s, g->E, g->N,
-                           c.orca_safety_space, (float)c.orca_neighbor_dist, (float)c.orca_time_horizon,
-                           (float)c.time_step, actions);
-    HIPCHK(hipGetLastError());
-    return CN_OK;
+    if (!g->ngroups) return robot_act_launch(g, st, policy, actions);
+    int rc = mix_fork(g, st);
+    if (rc) return rc;
+    for (int k = 0; k < g->ngroups && !rc; ++k) rc = robot_act_launch(g->grp[k], mix_stream(g, k, st), policy, actions);
+    const int rj = mix_join(g, st);
+    return rc ? rc : rj;
 }
 
-// cn_robot_act + cn_step for t = 0..T-1 with every step recorded at row t. Fused (the ROBOT kernels: up to seq_chunk
-// steps per launch, the controller inside the step workgroups) where cn_step_seq's multi-step launches apply and the
-// controller fits the step workgroup; launch pairs otherwise, the first step after cn_reset / cn_set_state included.
+// Steps [t0, t1) of a rollout call of T steps for g, a plain engine or a group of a mixed engine on its own stream:
+// cn_robot_act + cn_step with every step recorded at row t of the caller's (T, ER, ..) buffers (ER = NS-strided rows
+// of the whole engine; the group's envs at their own rows). Fused (the ROBOT kernels: up to seq_chunk steps per
+// launch, the controller inside the step workgroups) where `fuse` allows, cn_step_seq's multi-step launches apply and
+// the controller fits the step workgroup; launch pairs otherwise, the first step after cn_reset / cn_set_state
+// included. The rule reads g's own human count.
 // nz (cn_rollout_noisy, sigma > 0; null: cn_rollout): the step takes the perturbed action. The fused launches carry
 // CN_ROLLOUT_NOISY and their first step's k in StepArgs::rollout and read the rest from the engine's RolloutNoise
 // block, written once per call on the stream before the first of them; elsewhere cn_action_noise_kernel runs between
-// the pair's two launches and the step reads the engine's scratch.
-// ld (cn_rollout_lidar; null: none): the state every step leaves goes to row t of ld's state rows -- the fused
-// launches are the recording ROBOT kernels, told where through the engine's RolloutRows block (one small launch per
-// call before the first of them); elsewhere cn_state_rows_kernel follows the step -- and one scan over the T * E rows
-// follows the last step.
-static int rollout_run(cn_engine *g, void *stream, int policy, int T, const cn_rollout_out *out,
-                       const cn_rollout_noise *nz, int32_t *num_launches, const struct cn_rollout_lidar *ld = nullptr)
+// the pair's two launches and the step reads the engine's scratch. Both key the noise by the global env index.
+// ld (cn_rollout_lidar, plain engines; null: none): the state every step leaves goes to row t of ld's state rows -- the
+// fused launches are the recording ROBOT kernels, told where through the engine's RolloutRows block (one small launch
+// per call before the first of them); elsewhere cn_state_rows_kernel follows the step. *nl counts the launches.
+static int rollout_steps(cn_engine *g, hipStream_t st, bool fuse, int policy, int t0, int t1, int T,
+                         const cn_rollout_out *out, const cn_rollout_noise *nz, const struct cn_rollout_lidar *ld,
+                         int *nl)
 {
-    if (num_launches) *num_launches = 0;
-    if (!g) return set_err(CN_EINVAL, "null engine");
-    if ((policy != CN_ROBOT_ORCA && policy != CN_ROBOT_SOCIAL_FORCE) || T < 0 || !out || !out->actions ||
-        !out->robot_node || !out->temporal_edges || !out->spatial_edges)
-        return set_err(CN_EINVAL, "cn_rollout: policy CN_ROBOT_ORCA / CN_ROBOT_SOCIAL_FORCE, T >= 0, out with actions "
-                                  "and the observation buffers required");
-    if (g->ngroups) return set_err(CN_EUNSUPPORTED, "cn_rollout: not on a mixed engine");
-    if (g->c.kinematics != CN_HOLONOMIC)
-        return set_err(CN_EUNSUPPORTED, "cn_rollout: the controllers return ActionXY (holonomic engines only)");
-    const int64_t E = g->E, N = g->N;
-    const hipStream_t st = (hipStream_t)stream;
-    int npts = 0;
-    if (ld) {
-        if (!ld->robot_state || !ld->human_state)
-            return set_err(CN_EINVAL, "cn_rollout_lidar: lidar with obs, robot_state and human_state required");
-        const int rc = lidar_scan_check(ld->beams, ld->max_range, ld->obs, &npts);
-        if (rc) return rc;
-    }
+    void *const stream = (void *)st;
+    const int64_t E = g->ER, N = g->NS;
     const RolloutRows rows = {ld ? ld->robot_state : nullptr, ld ? ld->human_state : nullptr, out->actions, (int64_t)T};
     bool rows_set = false;
     const bool every = (out->flags & CN_ROLLOUT_OBS_EVERY_STEP) != 0;
     // the controller fits the step workgroup: social force (a lane per env) always, ORCA on its quad path
     const bool fits = policy == CN_ROBOT_SOCIAL_FORCE || g->N + 1 <= 10;
-    const bool fusable = fits && g->seq_chunk > 1 && !g->rows && !g->devseq && !g->plan.kd;
+    const bool fusable = fuse && fits && g->seq_chunk > 1 && !g->devseq && !g->plan.kd;
     const int64_t rollout = (int64_t)policy | ((int64_t)(out->flags & CN_ROLLOUT_OBS_EVERY_STEP) << 8);
     bool block_set = false;
-    int nl = 0;
-    for (int t = 0; t < T;) {
+    for (int t = t0; t < t1;) {
         const int64_t ro = every ? t : 0;   // the observation's row
         float *const act = out->actions + t * E * 2;
         float *const rn = out->robot_node + ro * E * 7, *const te = out->temporal_edges + ro * E * 2;
@@ -808,7 +903,7 @@ static int rollout_run(cn_engine *g, void *stream, int policy, int T, const cn_r
         const uint32_t k = nz ? (uint32_t)(uint64_t)(nz->step0 + t) : 0u;   // the step's Philox counter
         int n = 1, rc;
         if (fusable && !g->pend_all) {
-            n = T - t < g->seq_chunk ? T - t : g->seq_chunk;
+            n = t1 - t < g->seq_chunk ? t1 - t : g->seq_chunk;
             // (a launch never straddles the end of cn_profile's window: cn_step_seq)
             if (g->prof_on && g->prof_n < g->prof_cap && n > g->prof_cap - g->prof_n) n = g->prof_cap - g->prof_n;
             int64_t word = rollout;
@@ -820,7 +915,7 @@ static int rollout_run(cn_engine *g, void *stream, int policy, int T, const cn_r
                                        (RolloutNoise *)(g->work_count + CN_NOISE_W), v);
                     HIPCHK(hipGetLastError());
                     block_set = true;
-                    nl += 1;
+                    *nl += 1;
                 }
                 word |= CN_ROLLOUT_NOISY | ((int64_t)k << CN_ROLLOUT_K_SHIFT);
             }
@@ -830,45 +925,101 @@ static int rollout_run(cn_engine *g, void *stream, int policy, int T, const cn_r
                                    (RolloutRows *)(g->work_count + CN_ROWS_W), rows);
                 HIPCHK(hipGetLastError());
                 rows_set = true;
-                nl += 1;
+                *nl += 1;
             }
             rc = step_launch(g, stream, act, n, 2 * E, rn, te, se, rw, dn, ev, inf, epr, epl, word, ld != nullptr);
-            nl += 1;
+            *nl += 1;
         } else {
-            rc = cn_robot_act(g, stream, policy, act);
+            rc = robot_act_launch(g, st, policy, act);
             if (rc) return rc;
             const float *stepped = act;
             if (nz) {
                 (void)hipGetLastError();
-                hipLaunchKernelGGL(cn_action_noise_kernel, dim3((unsigned)((E + 63) / 64)), dim3(64), 0, st, act, g->act_x,
-                                   nz->executed ? nz->executed + t * E * 2 : nullptr, (int)E, nz->sigma, nz->seed, k,
-                                   (uint32_t)(uint64_t)g->c.env_offset);
+                hipLaunchKernelGGL(cn_action_noise_kernel, dim3((unsigned)((g->E + 63) / 64)), dim3(64), 0, st, act,
+                                   g->act_x, nz->executed ? nz->executed + t * E * 2 : nullptr, (int)g->E, nz->sigma,
+                                   nz->seed, k, (uint32_t)(uint64_t)g->c.env_offset, (const int32_t *)g->rows);
                 HIPCHK(hipGetLastError());
                 stepped = g->act_x;
-                nl += 1;
+                *nl += 1;
             }
             rc = cn_step(g, stream, stepped, rn, te, se, rw, dn, ev, inf, epr, epl);
-            nl += 2;
+            *nl += 2;
             if (ld && !rc) {
                 (void)hipGetLastError();
                 hipLaunchKernelGGL(cn_state_rows_kernel, dim3((unsigned)((E + 63) / 64)), dim3(256), 0, st, g->s, rows,
                                    (int)E, (int)N, t * E);
                 HIPCHK(hipGetLastError());
-                nl += 1;
+                *nl += 1;
             }
         }
         if (rc) return rc;
         t += n;
-        if (num_launches) *num_launches = nl;
     }
+    return CN_OK;
+}
+
+// cn_rollout / cn_rollout_noisy / cn_rollout_lidar: the checks (all of them before any launch), then rollout_steps.
+// A mixed engine: every group runs its whole T-step sequence on its own stream, fused chunks or launch pairs by its
+// own count, between one fork and one join. While a cn_profile window is open on it, the mixed engine runs a step at a
+// time instead (every group's launch pair or triple between a fork and a join per step), so the window counts steps.
+// ld: one scan over the T * E state rows follows the last step.
+static int rollout_run(cn_engine *g, void *stream, int policy, int T, const cn_rollout_out *out,
+                       const cn_rollout_noise *nz, int32_t *num_launches, const struct cn_rollout_lidar *ld = nullptr)
+{
+    if (num_launches) *num_launches = 0;
+    if (!g) return set_err(CN_EINVAL, "null engine");
+    if ((policy != CN_ROBOT_ORCA && policy != CN_ROBOT_SOCIAL_FORCE) || T < 0 || !out || !out->actions ||
+        !out->robot_node || !out->temporal_edges || !out->spatial_edges)
+        return set_err(CN_EINVAL, "cn_rollout: policy CN_ROBOT_ORCA / CN_ROBOT_SOCIAL_FORCE, T >= 0, out with actions "
+                                  "and the observation buffers required");
+    if (g->ngroups && ld) return set_err(CN_EUNSUPPORTED, "cn_rollout: not on a mixed engine");
+    if (g->ngroups && !g->scripted)
+        return set_err(CN_EUNSUPPORTED, "cn_rollout: not on a mixed engine (unless cn_mixed_scripted enabled it)");
+    if (!all_holonomic(g))
+        return set_err(CN_EUNSUPPORTED, g->ngroups ? "cn_rollout: not on a unicycle mixed engine (the controllers return ActionXY)"
+                                                   : "cn_rollout: the controllers return ActionXY (holonomic engines only)");
+    const hipStream_t st = (hipStream_t)stream;
+    int npts = 0;
+    if (ld) {
+        if (!ld->robot_state || !ld->human_state)
+            return set_err(CN_EINVAL, "cn_rollout_lidar: lidar with obs, robot_state and human_state required");
+        const int rc = lidar_scan_check(ld->beams, ld->max_range, ld->obs, &npts);
+        if (rc) return rc;
+    }
+    int nl = 0, rc = CN_OK;
+    if (!g->ngroups) {
+        rc = rollout_steps(g, st, true, policy, 0, T, T, out, nz, ld, &nl);
+    } else if (g->prof_on && g->prof_n < g->prof_cap) {
+        for (int t = 0; t < T && !rc; ++t) {
+            const bool prof = g->prof_on && g->prof_n < g->prof_cap;
+            if (prof && g->prof_n == 0) HIPCHK(hipEventRecord(g->ev[0], st));
+            rc = mix_fork(g, st);
+            if (rc) break;
+            for (int k = 0; k < g->ngroups && !rc; ++k)
+                rc = rollout_steps(g->grp[k], mix_stream(g, k, st), false, policy, t, t + 1, T, out, nz, nullptr, &nl);
+            const int rj = mix_join(g, st);
+            if (!rc) rc = rj;
+            if (!rc && prof && ++g->prof_n == g->prof_cap) HIPCHK(hipEventRecord(g->ev[1], st));
+        }
+    } else if (T > 0) {
+        rc = mix_fork(g, st);
+        if (rc) return rc;
+        for (int k = 0; k < g->ngroups && !rc; ++k)
+            rc = rollout_steps(g->grp[k], mix_stream(g, k, st), true, policy, 0, T, T, out, nz, nullptr, &nl);
+        const int rj = mix_join(g, st);
+        if (!rc) rc = rj;
+    }
+    if (num_launches) *num_launches = nl;
+    if (rc) return rc;
     if (ld && T > 0) {   // the observations of all T * E rows: the scan over a cn_state_ptrs aimed into the state rows
+        const int64_t E = g->E, N = g->N;
         const int64_t RE = (int64_t)T * E;
         cn_state_ptrs P = g->s;
         double *const r = ld->robot_state, *const h = ld->human_state;
         P.r_px = r; P.r_py = r + RE; P.r_vx = r + 2 * RE; P.r_vy = r + 3 * RE; P.r_radius = r + 4 * RE;
         P.r_gx = r + 5 * RE; P.r_gy = r + 6 * RE; P.r_vpref = r + 7 * RE; P.r_theta = r + 8 * RE;
         P.h_px = h; P.h_py = h + RE * N; P.h_r = h + 2 * RE * N;
-        const int rc = lidar_scan_launch(g, st, P, RE, ld->beams, npts, ld->max_range, ld->robot_radius, ld->obs, &nl);
+        rc = lidar_scan_launch(g, st, P, RE, ld->beams, npts, ld->max_range, ld->robot_radius, ld->obs, &nl);
         if (rc) return rc;
         if (num_launches) *num_launches = nl;
     }

@@ -13,6 +13,8 @@ static_assert(CN_NOISE_W * 4 + sizeof(RolloutNoise) <= CN_WORK_BYTES && (CN_NOIS
 static_assert(CN_ROWS_W * 4 >= CN_NOISE_W * 4 + sizeof(RolloutNoise) && CN_ROWS_W * 4 + sizeof(RolloutRows) <= CN_WORK_BYTES &&
                   (CN_ROWS_W * 4) % alignof(RolloutRows) == 0,
               "cn_engine::work_count: the RolloutRows block behind the RolloutNoise block");
+static_assert(CN_ER_W * 4 >= CN_ROWS_W * 4 + sizeof(RolloutRows) && CN_ER_W * 4 + 4 <= CN_WORK_BYTES,
+              "cn_engine::work_count: a group's row count behind the RolloutRows block");
 
 struct cn_engine {
     cn_config c;
@@ -26,7 +28,8 @@ struct cn_engine {
     uint32_t *work_count; // [16]: [2..4] spawn-list counters (triple buffered), [5..7] parked-spawn counters,
                           // [8..11] spawn statistics (PendLaunch::stats), [15] inline reset draws; behind them
                           // (word CN_NOISE_W) cn_rollout_noisy's RolloutNoise block and (word CN_ROWS_W)
-                          // cn_rollout_lidar's RolloutRows block: CN_WORK_BYTES in all
+                          // cn_rollout_lidar's RolloutRows block, and (word CN_ER_W) a mixed engine's E in its
+                          // groups: CN_WORK_BYTES in all
     float *act_x;         // [E][2] cn_rollout_noisy's launch triples: the perturbed action the step reads
     uint32_t *plist;      // [3][E + 64][4] envs whose spawn after next kernel A draws, with their counters
     uint32_t *rlist;      // [3][2E][4] spawns parked by a launch (resumed by the next); counters work_count[5..7]
@@ -50,12 +53,14 @@ struct cn_engine {
     // stride; identity / N for a plain engine)
     int32_t *rows;   // device [E] or nullptr
     int NS;
+    int ER;          // envs of the caller's buffers: the mixed engine's E for a group (work_count[CN_ER_W]), E otherwise
     // mixed engine (cn_create_mixed): the groups, each a plain engine over its envs; E = all envs,
     // N = NS = the largest human count
     int ngroups;
     cn_engine **grp;
     hipStream_t *gstream;   // [ngroups]: group k > 0 steps on gstream[k] (forked from / joined to the caller's)
     hipEvent_t *gev;        // [ngroups + 1]: fork, then one join event per forked group
+    int scripted;           // cn_mixed_scripted: cn_robot_act / cn_rollout / cn_rollout_noisy serve this mixed engine
 };
 
 // unit-circle table of GEOS's 64-gon point buffer (norm zones), per device; every entry point whose
@@ -109,10 +114,12 @@ static int keysnap(const cn_engine *g, hipStream_t st)
 // Every instantiation of cn_step_kernel, listed ONCE: cn_create raises the dynamic-LDS limit of each entry and
 // step_launch picks its kernel here, so a new template flag is added in this table (and STEP_KERNEL) alone.
 // Launch modes: a single step with host-passed arguments; graph mode (DEVSEQ, plain engines); a multi-step launch
-// (SEQ, plain quad-path engines); a cn_rollout launch (SEQ + ROBOT, the same engines) and a cn_rollout_lidar launch
-// (SEQ + ROBOT + REC: it records the state rows as well). A combination that is not
-// listed does not exist: mixed-engine groups (mix) and the kd-tree path (kd) have no SEQ / ROBOT kernel, mix none
-// for graph mode. (The entries' order is the order in which the compiler emits the kernels into the code object.)
+// (SEQ, quad-path engines and quad-path groups of a mixed engine); a cn_rollout launch (SEQ + ROBOT, the same
+// engines and groups) and a cn_rollout_lidar launch (SEQ + ROBOT + REC, plain engines: it records the state rows
+// as well). A combination that is not listed does not exist: the kd-tree path (kd) has no SEQ / ROBOT kernel,
+// mixed-engine groups (mix) none for graph mode or the recording rollout (no LiDAR on a mixed engine).
+// (The entries' order is the order in which the compiler emits the kernels into the code object: the groups'
+// multi-step kernels are appended at the end, so the earlier ones are emitted as before.)
 enum StepMode { STEP_SINGLE, STEP_DEVSEQ, STEP_SEQ, STEP_ROBOT, STEP_ROBOT_REC };
 typedef void (*StepKernelFn)(StepArgs, cn_config);
 struct StepKernelEntry {
@@ -133,7 +140,9 @@ static const StepKernelEntry step_kernels[] = {
     STEP_KERNEL(false, false, false, STEP_DEVSEQ), STEP_KERNEL(false, true, false, STEP_DEVSEQ),
     STEP_KERNEL(true, false, false, STEP_DEVSEQ),  STEP_KERNEL(true, true, false, STEP_DEVSEQ),
     STEP_KERNEL(false, false, false, STEP_ROBOT),  STEP_KERNEL(false, true, false, STEP_ROBOT),
-    STEP_KERNEL(false, false, false, STEP_ROBOT_REC), STEP_KERNEL(false, true, false, STEP_ROBOT_REC)};
+    STEP_KERNEL(false, false, false, STEP_ROBOT_REC), STEP_KERNEL(false, true, false, STEP_ROBOT_REC),
+    STEP_KERNEL(false, false, true, STEP_SEQ),     STEP_KERNEL(false, true, true, STEP_SEQ),
+    STEP_KERNEL(false, false, true, STEP_ROBOT),   STEP_KERNEL(false, true, true, STEP_ROBOT)};
 #undef STEP_KERNEL
 
 // the kernel of a launch, or null where the combination does not exist

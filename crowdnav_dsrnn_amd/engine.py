@@ -70,7 +70,7 @@ class CrowdNavEngine:
             with torch.cuda.device(self.device):
                 _lib.check(L.cn_create(ctypes.byref(self.cfg), self.device.index, ctypes.byref(h)))
         else:
-            cfgs, env_group = _mixed
+            cfgs, env_group, scripted = _mixed
             arr = (abi.CnConfig * len(cfgs))(*[c.copy() for c in cfgs])
             for c in arr:
                 if c.num_envs > 0:
@@ -80,6 +80,8 @@ class CrowdNavEngine:
             with torch.cuda.device(self.device):
                 _lib.check(L.cn_create_mixed(arr, len(cfgs), eg.ctypes.data_as(ctypes.c_void_p), self.E,
                                              self.device.index, ctypes.byref(h)))
+                if scripted:
+                    _lib.check(L.cn_mixed_scripted(h, 1))
             self.cfg = arr[0].copy()
             self.groups = [(arr[g], np.nonzero(eg == g)[0].astype(np.int32)) for g in range(len(cfgs))
                            if (eg == g).any()]
@@ -107,13 +109,16 @@ class CrowdNavEngine:
         self.seq_chunk = 32   # steps per multi-step launch (the library's CN_SEQ_CHUNK; set_seq_chunk)
 
     @classmethod
-    def mixed(cls, cfgs, env_group, device=None):
+    def mixed(cls, cfgs, env_group, device=None, scripted=False):
         """One engine over envs of several configurations (cn_create_mixed): env r runs
         cfgs[env_group[r]] (its own human count, scenarios, radius, ...). N = the largest human count;
         spatial_edges rows past an env's own count are padding (`human_mask` False): a never-seen human
         at the reference's unseen-belief position (15, 15). Build the configs with
-        config.make_mixed_cn_configs."""
-        return cls(None, device, _mixed=(list(cfgs), env_group))
+        config.make_mixed_cn_configs.
+        scripted=True (cn_mixed_scripted; holonomic groups): robot_act and rollout (with noise=) serve this engine,
+        every group on its own stream by the rule of a plain engine of its count. Off, the default, they refuse a
+        mixed engine as before. step_seq needs no opt-in; rollout(lidar=) and graph mode are never served."""
+        return cls(None, device, _mixed=(list(cfgs), env_group, bool(scripted)))
 
     # -------------------------------------------------------------------------------------------
     def _stream(self):

@@ -96,10 +96,11 @@ def make_vec_envs(env_name, seed, num_processes, gamma, log_dir, device, allow_e
 
 
 def _no_varied(config, what):
-    """UnsupportedConfig for what an env of varying human count does not serve (read from the config alone)."""
-    if getattr(config.sim, "human_nums", None) is not None:
-        raise UnsupportedConfig("%s: not served on an env of varying human count (config.sim.human_nums: "
-                                "cn_robot_act / cn_rollout do not run on a mixed engine)" % what)
+    """UnsupportedConfig for what an env of varying human count serves only with the opt-in
+    config.sim.human_nums_scripted (read from the config alone)."""
+    if getattr(config.sim, "human_nums", None) is not None and not getattr(config.sim, "human_nums_scripted", False):
+        raise UnsupportedConfig("%s: not served on an env of varying human count (config.sim.human_nums) unless "
+                                "config.sim.human_nums_scripted is set" % what)
 
 
 class _LazyInfos:
@@ -243,7 +244,8 @@ class CrowdNavVecEnv:
         if engine_device is None and self.device.type == "cuda":
             engine_device = self.device
         if mixed is not None:
-            self.engine = CrowdNavEngine.mixed(mixed[0], mixed[1], engine_device)
+            self.engine = CrowdNavEngine.mixed(mixed[0], mixed[1], engine_device,
+                                               scripted=bool(getattr(config.sim, "human_nums_scripted", False)))
             assert self.engine.env_humans.tolist() == self.env_human_nums
             # the observation's 'detected_human_num': constant over the env's life, (E, 1) float32 on the engine's GPU
             self._detected = self.engine.env_humans.to(torch.float32).reshape(self.num_envs, 1)
@@ -354,7 +356,9 @@ class CrowdNavVecEnv:
 
     def robot_act(self, policy):
         """The scripted robot's action ('orca' / 'social_force') for the state the last reset / step returned:
-        (E, 2) float32 on the engine's GPU (CrowdNavEngine.robot_act; no host synchronisation)."""
+        (E, 2) float32 on the engine's GPU (CrowdNavEngine.robot_act; no host synchronisation). An env of varying
+        human count (sim.human_nums) with sim.human_nums_scripted: every env by the controller of its own count;
+        without that opt-in: UnsupportedConfig."""
         _no_varied(self.config, "robot_act")
         return self.engine.robot_act(policy)
 
@@ -366,7 +370,10 @@ class CrowdNavVecEnv:
         obs_mode 'convgru' with lidar.live: the dict also holds 'lidar' (T, E, 1, 7 + beams), the observation
         step_device would have returned after every step, and the state rows it was scanned from (the engine's
         rollout with the env's LiDAR settings). Without lidar.live the observation carries the scan held since the
-        episode's reset, which is state between steps and no function of a recorded row: UnsupportedConfig."""
+        episode's reset, which is state between steps and no function of a recorded row: UnsupportedConfig.
+        An env of varying human count (sim.human_nums) with sim.human_nums_scripted: spatial_edges is padded as the
+        env's observation is and the dict gains 'detected_human_num' (T, E, 1), an expanded view of the env's constant
+        (E, 1) tensor; without that opt-in: UnsupportedConfig."""
         _no_varied(self.config, "rollout")
         lidar = None
         if self.obs_mode == "convgru":
@@ -379,7 +386,11 @@ class CrowdNavVecEnv:
             raise UnsupportedConfig("rollout: obs_mode=%r" % self.obs_mode)
         self._state_cache = None
         if lidar is None:
-            return self.engine.rollout(policy, T, obs_every_step=obs_every_step, out=out, noise=noise)
+            ro = self.engine.rollout(policy, T, obs_every_step=obs_every_step, out=out, noise=noise)
+            if self.human_nums is not None:
+                d = self._detected
+                ro["detected_human_num"] = d.unsqueeze(0).expand(int(T), -1, -1) if obs_every_step else d
+            return ro
         return self.engine.rollout(policy, T, obs_every_step=obs_every_step, out=out, noise=noise, lidar=lidar)
 
     def _state(self):

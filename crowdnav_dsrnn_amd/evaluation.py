@@ -26,6 +26,9 @@ Reference quirks kept on purpose:
   * the recorded time of an episode is the env time before its last step (evaluation.py:148-149);
   * the side-preference counters are never reset between episodes, only divided by the episode length
     (evaluation.py:85-86,237-239).
+An env of varying human count (config.sim.human_nums): every episode is recorded with the human count of the env that
+ran it, and the report ends with a per-count block (per_count_summary; also evaluate.last["per_count"]). On a plain
+env every count is the same and nothing is added.
 Multi-GPU: with torch.distributed initialised each rank evaluates its env shard (global env index
 rank*E + i, nenv = world*E) with no communication in the loop; the records are summed once at the end.
 """
@@ -108,7 +111,7 @@ class EpisodeRecorder:
     I32 = ("steps", "left", "right", "dcnt")
 
     def __init__(self, num_envs, test_size, env_offset, nenv, device, time_step, gamma, v_pref,
-                 side_preference=False, side_scenario=None, scenario_names=(), keep_traces=True):
+                 side_preference=False, side_scenario=None, scenario_names=(), keep_traces=True, env_humans=None):
         E = int(num_envs)
         self.E, self.test_size, self.nenv = E, int(test_size), int(nenv)
         self.dev = torch.device(device)
@@ -129,6 +132,10 @@ class EpisodeRecorder:
         self.rec["done"] = torch.zeros(n, dtype=torch.int32, device=self.dev)
         self.rec["firstx"] = torch.zeros(n, dtype=torch.float32, device=self.dev)
         self.rec["firsty"] = torch.zeros(n, dtype=torch.float32, device=self.dev)
+        # the human count of the env that ran the episode (env_humans: (E,) counts; None: not recorded, zeros)
+        self.rec["humans"] = torch.zeros(n, dtype=torch.int32, device=self.dev)
+        self.humans = (torch.zeros(E, dtype=torch.int32, device=self.dev) if env_humans is None else
+                       torch.as_tensor(env_humans).to(device=self.dev, dtype=torch.int32).reshape(E))
         self.recorded = torch.zeros((), dtype=torch.int64, device=self.dev)
         g0 = int(env_offset)
         self.target = sum(max(0, -(-(self.test_size - (g0 + i)) // self.nenv)) for i in range(E))
@@ -200,6 +207,7 @@ class EpisodeRecorder:
         self.rec["event"].scatter_(0, idx, ev)
         self.rec["scenario"].scatter_(0, idx, f[:, abi.INFO_SCENARIO].to(torch.int32))
         self.rec["done"].scatter_(0, idx, counted.to(torch.int32))
+        self.rec["humans"].scatter_(0, idx, self.humans)
         self.recorded += counted.sum()
         # global_time advances by dt per step (crowd_sim_dict.py:253) and restarts at the auto-reset
         run["gt"] += dt
@@ -281,7 +289,8 @@ def evaluate(actor_critic, ob_rms, eval_envs, num_processes, device, config, log
     gamma = 0.99
     dt = float(config.env.time_step)
     rec = EpisodeRecorder(E, test_size, int(cn.env_offset), int(cn.nenv), eval_envs.engine.device, dt, gamma,
-                          float(config.robot.v_pref), side, scenario, eval_envs.scenario_names, keep_traces)
+                          float(config.robot.v_pref), side, scenario, eval_envs.scenario_names, keep_traces,
+                          getattr(eval_envs, "env_human_nums", None))
     obs = eval_envs.reset()
     rec.start(rec_obs(obs))
     n = 0
@@ -333,7 +342,8 @@ def evaluate_scripted(name, eval_envs, num_processes, device, config, logging, c
     gamma = 0.99
     dt = float(config.env.time_step)
     rec = EpisodeRecorder(E, test_size, int(cn.env_offset), int(cn.nenv), eval_envs.engine.device, dt, gamma,
-                          float(config.robot.v_pref), side, scenario, eval_envs.scenario_names, keep_traces)
+                          float(config.robot.v_pref), side, scenario, eval_envs.scenario_names, keep_traces,
+                          getattr(eval_envs, "env_human_nums", None))
     C = int(chunk) if chunk is not None else int(eval_envs.engine.seq_chunk)
     if C < 1:
         raise ValueError("evaluate_scripted: chunk >= 1 required, got %d" % C)
@@ -359,6 +369,38 @@ def evaluate_scripted(name, eval_envs, num_processes, device, config, logging, c
         dist.all_gather_object(gathered, traces)
         traces = {k: v for d in gathered for k, v in d.items()}
     return _report(r, traces, config, logging, test_size, dt, gamma, side, scenario, eval_envs, verbose)
+
+
+def per_count_summary(records):
+    """Outcome rates per human count from per-episode records (`humans`: the count of the env that ran the episode,
+    `event`: its end): {count: {"episodes", "success_rate", "collision_rate", "timeout_rate"}} in ascending count
+    order, or None when the records carry no counts or a single distinct one (a plain env: nothing to break down)."""
+    h = records.get("humans")
+    if h is None:
+        return None
+    h, ev = np.asarray(h), np.asarray(records["event"])
+    counts = sorted(set(int(x) for x in h))
+    if len(counts) < 2:
+        return None
+    out = {}
+    for c in counts:
+        e = ev[h == c]
+        n = int(e.size)
+        out[c] = {"episodes": n, "success_rate": float((e == abi.EV_REACHGOAL).sum()) / n,
+                  "collision_rate": float((e == abi.EV_COLLISION).sum()) / n,
+                  "timeout_rate": float((e == abi.EV_TIMEOUT).sum()) / n}
+    return out
+
+
+def log_per_count(per_count, logger):
+    """The report's per-count block (after every other line; nothing for None)."""
+    if not per_count:
+        return
+    logger.info("")
+    logger.info("PER HUMAN COUNT: ")
+    for c, v in per_count.items():
+        logger.info(f"{c} humans: success rate: {v['success_rate']:.3f}, collision rate: {v['collision_rate']:.3f}, "
+                    f"timeout rate: {v['timeout_rate']:.3f}, episodes: {v['episodes']}")
 
 
 def _report(r, traces, config, logging, test_size, dt, gamma, side, scenario, eval_envs, verbose):
@@ -497,9 +539,13 @@ def _report(r, traces, config, logging, test_size, dt, gamma, side, scenario, ev
         logging.info(f"Left % = {100 * side_pref[scenario]['left'] / test_size:.3f}%")
         logging.info(f"Right % = {100 * side_pref[scenario]['right'] / test_size:.3f}%")
     metrics.log_metrics()
+    per_count = per_count_summary(r)
+    log_per_count(per_count, logging)
     eval_envs.close()
     evaluate.last = {"metrics": metrics, "num_events": num_events, "success_rate": success_rate,
                      "collision_rate": collision_rate, "timeout_rate": timeout_rate, "records": r,
                      "danger_steps": n_danger, "avg_min_dist": avg_min_dist,
                      "side_preferences": side_pref if side else None}
+    if per_count is not None:
+        evaluate.last["per_count"] = per_count
     return raw_rewards, discounted_rewards, dist_to_goal

@@ -17,6 +17,12 @@ the minibatches PPO.update walks (env subsets, whole sequences, the recurrent st
 The ConvGRU policy sees 180 ranges where the expert sees every human's state. Its chunks come from the same rollout
 with the LiDAR rows recorded as well (cn_rollout_lidar) straight into a RolloutStorage; labels, noise, masks, returns,
 the carried recurrent state, fit() and update() are the DSRNN branch's.
+
+An env of varying human count (config.sim.human_nums with sim.human_nums_scripted; the DSRNN policy built for the
+largest count): the rollout runs
+on the mixed engine and records the padded observation into the same storage tensors; the storage's
+'detected_human_num' rows, constant over the env's life, are filled once, and the policy reads them as under PPO (the
+attention of ops.spatial_attention_var).
 """
 import contextlib
 import time
@@ -102,6 +108,9 @@ class BehaviourCloning:
         else:
             for k in r.obs:
                 r.obs[k][0].copy_(obs[k])
+            if "detected_human_num" in r.obs:   # no rollout row rewrites it: every slot, once
+                r.obs["detected_human_num"].copy_(obs["detected_human_num"].unsqueeze(0).expand_as(
+                    r.obs["detected_human_num"]))
 
     def _obs(self, fn):
         """fn over the storage's observation: the DSRNN's dict of tensors or the ConvGRU's one tensor."""

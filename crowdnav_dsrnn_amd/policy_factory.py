@@ -257,23 +257,26 @@ class ScriptedRobot:
         evaluate(ScriptedRobot(venv, 'orca'), None, venv, E, device, config, logging)
 
     The env's config keeps robot.policy 'srnn' / 'convgru' (that selects the observation); holonomic only,
-    as the controllers return ActionXY."""
+    as the controllers return ActionXY. On an env of varying human count (config.sim.human_nums, with the opt-in
+    config.sim.human_nums_scripted) every env is driven by the controller of its own count; `base.human_num` is the
+    padded (largest) one."""
 
     NAMES = ("orca", "social_force")
 
     @classmethod
     def check(cls, venv, name):
-        """UnsupportedConfig for an unknown controller, a unicycle config or an env of varying human count (before
-        anything touches the GPU)."""
+        """UnsupportedConfig for an unknown controller, a unicycle config, or an env of varying human count
+        (config.sim.human_nums) without the opt-in config.sim.human_nums_scripted (before anything touches the
+        GPU)."""
         if name not in cls.NAMES:
             raise UnsupportedConfig("ScriptedRobot: %r (one of %s)" % (name, ", ".join(cls.NAMES)))
         config = venv.config
         if config.action_space.kinematics != "holonomic":
             raise UnsupportedConfig("ScriptedRobot: action_space.kinematics=%r (the controllers return ActionXY: "
                                     "holonomic only)" % config.action_space.kinematics)
-        if getattr(config.sim, "human_nums", None) is not None:
-            raise UnsupportedConfig("ScriptedRobot: an env of varying human count (config.sim.human_nums): "
-                                    "cn_robot_act / cn_rollout do not run on a mixed engine")
+        if getattr(config.sim, "human_nums", None) is not None and not getattr(config.sim, "human_nums_scripted", False):
+            raise UnsupportedConfig("ScriptedRobot: an env of varying human count (config.sim.human_nums) serves the "
+                                    "scripted controllers only with config.sim.human_nums_scripted")
 
     @classmethod
     def check_rollout(cls, venv, name):

@@ -185,13 +185,20 @@ void cn_destroy(cn_engine *eng);
  * scenarios[(env_offset + r) % num_scenarios] must be one group env_group[r] is configured for).
  * The engine then behaves as one engine of num_envs envs with N = max human_num: cn_reset / cn_step take
  * [num_envs]-row buffers; spatial_edges rows beyond an env's own human count are padding (a never-seen
- * human: belief (15, 15) relative to the robot). cn_step launches one step kernel per group.
+ * human: belief (15, 15) relative to the robot). cn_step launches one step kernel per group. cn_step_seq,
+ * and, once cn_mixed_scripted has enabled them, cn_robot_act, cn_rollout and cn_rollout_noisy run every group on a
+ * stream of its own between one fork from and one join to the caller's stream (holonomic groups for the last
+ * three), each group by the rule of a plain engine of its count.
  * cn_get_state / cn_set_state: the groups' blobs concatenated in group order; cn_state_device_ptr: NULL;
  * cn_lidar_obs / cn_lidar_scan: CN_EUNSUPPORTED. */
 int cn_create_mixed(const cn_config *groups, int num_groups, const int32_t *env_group, int64_t num_envs, int device,
                     cn_engine **out);
 /* per-env human count, into host memory [E] (a plain engine: N everywhere) */
 int cn_env_humans(const cn_engine *eng, int32_t *dst);
+/* Opt-in of a mixed engine: with on != 0, cn_robot_act, cn_rollout and cn_rollout_noisy serve it (holonomic groups)
+ * as described there; off (the default, and what an engine was before this call existed) they return
+ * CN_EUNSUPPORTED for it. Host state only, no launch. CN_EINVAL: NULL or a plain engine (which they always serve). */
+int cn_mixed_scripted(cn_engine *eng, int on);
 
 /* Reset all envs (fresh episodes, case_counter continues). obs out: robot_node [E][7], temporal [E][2],
  * spatial [E][N][2] float32. */
@@ -216,8 +223,11 @@ int cn_step(cn_engine *eng, void *stream, const float *actions,
  * (cn_debug_set_seq_chunk), so no workgroup waits for the grid's slowest one after every step. Such a launch
  * stores the outputs in its last step only (the earlier steps' values would be overwritten unread), and its
  * waves rotate their issue priority from step to step, so that the workgroups sharing a CU advance alike; every
- * other engine (mixed, graph mode, > 10 agents) and the first launch after cn_reset / cn_set_state get
- * one cn_step launch per step. Either way the results are those of the T single calls, bit for bit. */
+ * other engine (graph mode, > 10 agents) and the first launch after cn_reset / cn_set_state get
+ * one cn_step launch per step. Either way the results are those of the T single calls, bit for bit.
+ * A mixed engine: every group runs its T steps by this rule (its own count) on its own stream, one fork before the
+ * first and one join after the last launch; the actions' rows and the stride are the mixed engine's. While a
+ * cn_profile window is open on a mixed engine it steps as a whole, one cn_step per step. */
 int cn_step_seq(cn_engine *eng, void *stream, int T, const float *actions, int64_t action_stride,
                 float *robot_node, float *temporal_edges, float *spatial_edges,
                 float *reward, uint8_t *done, int8_t *event, float *info,
@@ -494,8 +504,11 @@ int cn_social_force_predict(void *stream, int64_t n, int M, const double *self, 
  *     only orders equidistant neighbours, and only when N + 1 > 10);
  *   - the radii follow the current belief instead of being frozen at the object's first predict (identical
  *     unless humans.random_radii).
- * CN_EUNSUPPORTED: a unicycle engine (the controllers return ActionXY) or a mixed engine; CN_EINVAL: an
- * unknown policy or actions = NULL. */
+ * A mixed engine after cn_mixed_scripted(eng, 1): one launch per group, side by side (group 0 on `stream`, the others
+ * forked from and joined to it), each with the kernel its own count selects; env r's action at row r of `actions`.
+ * CN_EUNSUPPORTED: a unicycle engine (the controllers return ActionXY), a mixed engine without that opt-in or with a
+ * unicycle group;
+ * CN_EINVAL: an unknown policy or actions = NULL. */
 #define CN_ROBOT_ORCA 0
 #define CN_ROBOT_SOCIAL_FORCE 1
 int cn_robot_act(cn_engine *eng, void *stream, int policy, float *actions);
@@ -517,7 +530,13 @@ int cn_robot_act(cn_engine *eng, void *stream, int policy, float *actions);
  *   Everything else cn_robot_act supports (chunk 1, graph mode, > 10 agents per simulator, ORCA at N + 1 > 10) is
  * issued as T cn_robot_act + cn_step launch pairs from native code with the output pointers advanced to row t:
  * the same rows.
- * CN_EUNSUPPORTED: a unicycle or a mixed engine. CN_EINVAL: an unknown policy, T < 0, out / actions / an
+ *   A mixed engine after cn_mixed_scripted(eng, 1): every group runs its own T-step sequence on its own stream (one
+ * fork, one join per call), fused
+ * where its own count allows and as launch pairs otherwise, its envs at their rows of the (T, E, ..) buffers
+ * (spatial_edges padded to the largest count, the padding written as cn_step writes it); *num_launches counts the
+ * launches of all groups. While a cn_profile window is open on it: launch pairs, a step at a time.
+ * CN_EUNSUPPORTED: a unicycle engine, a mixed engine without the opt-in or with a unicycle group. CN_EINVAL: an
+ * unknown policy, T < 0, out / actions / an
  * observation pointer NULL. All are checked before any launch (*num_launches = 0). T = 0 launches nothing. */
 typedef struct cn_rollout_out {
     float   *actions;        /* [T][E][2]  required: the controller's action of step t (as cn_robot_act rounds it) */
@@ -583,7 +602,8 @@ int cn_rollout_noisy(cn_engine *eng, void *stream, int policy, int T, const cn_r
  *     indices stay in int range. + 1 for the copy into `executed` when noise is given with sigma == 0.
  * CN_EINVAL: lidar NULL, a NULL buffer in it, cn_lidar_scan's (beams in [2, 4096], max_range in (0, 1e4] and at
  * least two 0.01 m samples), cn_rollout_noisy's for a non-NULL noise, cn_rollout's. CN_EUNSUPPORTED: cn_rollout's
- * (a unicycle or a mixed engine). All are checked before any launch (*num_launches = 0). T = 0 launches nothing. */
+ * (a unicycle engine), and any mixed engine (no LiDAR there). All are checked before any launch
+ * (*num_launches = 0). T = 0 launches nothing. */
 struct cn_rollout_lidar {   /* (no typedef: the function below has the name, as stat() and struct stat) */
     float  *obs;           /* [T][E][7 + beams]: the ConvGRU observation AFTER step t, what cn_lidar_scan writes for that state */
     int32_t beams;  double max_range, robot_radius;      /* cn_lidar_scan's, same ranges */

@@ -13,7 +13,12 @@ the successful episodes and the wall time of the run. Needs a GPU.
 multi-step launches, every step recorded, the end-of-run check once per chunk); the per-episode records, and so the
 rows, are the same.
 
-Usage: python tools/baseline_eval.py [--envs 100] [--test-size 500] [--humans 5] [--rollout] [--out FILE]
+--human-nums 5 10 runs it on ONE env of varying human count (config.sim.human_nums; env g has
+human_nums[g % len] humans) and prints, after each overall row, one row per distinct count from the report's
+per-count block (evaluate.last["per_count"]).
+
+Usage: python tools/baseline_eval.py [--envs 100] [--test-size 500] [--humans 5 | --human-nums 5 10] [--rollout]
+           [--out FILE]
 """
 import argparse
 import json
@@ -37,6 +42,8 @@ def main():
     ap.add_argument("--envs", type=int, default=100)
     ap.add_argument("--test-size", type=int, default=500)
     ap.add_argument("--humans", type=int, default=5)
+    ap.add_argument("--human-nums", type=int, nargs="+", default=None,
+                    help="an env of varying human count (one mixed engine); adds the per-count rows")
     ap.add_argument("--rollout", action="store_true", help="evaluate on whole rollouts (evaluate_scripted)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
@@ -50,6 +57,9 @@ def main():
         for name in ScriptedRobot.NAMES:
             c = clone_config(Config())
             c.sim.human_num = args.humans
+            if args.human_nums:
+                c.sim.human_nums = list(args.human_nums)
+                c.sim.human_nums_scripted = True
             c.env.test_size = args.test_size
             c.robot.visible = visible
             E = args.envs
@@ -62,7 +72,8 @@ def main():
             wall = time.time() - t0
             last = evaluate.last
             nav = last["metrics"]["navigation time"]
-            rec = {"robot": name, "robot_visible": visible, "humans": args.humans, "episodes": args.test_size,
+            rec = {"robot": name, "robot_visible": visible, "humans": args.human_nums or args.humans,
+                   "episodes": args.test_size,
                    "envs": E, "path": "rollout" if args.rollout else "step",
                    "counts": {k: int(v["total"]) for k, v in last["num_events"].items()},
                    "success_rate": round(last["success_rate"], 3),
@@ -71,6 +82,13 @@ def main():
                    "wall_s": round(wall, 2)}
             lines.append(json.dumps(rec))
             print(lines[-1], flush=True)
+            for n, v in (last.get("per_count") or {}).items():
+                lines.append(json.dumps({"robot": name, "robot_visible": visible, "humans": n, "of": args.human_nums,
+                                         "episodes": v["episodes"], "path": rec["path"],
+                                         "success_rate": round(v["success_rate"], 3),
+                                         "collision_rate": round(v["collision_rate"], 3),
+                                         "timeout_rate": round(v["timeout_rate"], 3)}))
+                print(lines[-1], flush=True)
     if args.out:
         with open(args.out, "w") as f:
             f.write("\n".join(lines) + "\n")

@@ -11,10 +11,15 @@ env steps, the last update's losses and the wall time of the training. --policy 
 robot.policy 'convgru', lidar.enable and lidar.live: the expert still acts on the full state, the cloned policy sees
 the 180 ranges (the rollouts record them: cn_rollout_lidar), and the same three kinds of row are printed. --out saves the state_dict of the LAST
 sigma's policy (keys as the reference checkpoints'), ready for RolloutTrainer / train.py to continue with PPO.
+--human-nums 5 10 (DSRNN only) clones the expert on ONE env of varying human count (config.sim.human_nums) into a
+policy built for the largest count, and evaluates every row per density: at each trained count and at --unseen (7),
+on a plain test VecEnv of that count with a Policy of that size loaded from the same state_dict (as
+tools/train_varied.py does); the expert row of a density is the expert on that plain env.
 Needs a GPU.
 
 Usage: python tools/imitation_pretrain.py [--policy srnn|convgru] [--expert orca] [--updates 3000] [--envs 1024] [--steps 32] [--epochs 1]
            [--mini-batch 2] [--lr 1e-3] [--value-coef 0.5] [--sigma-frac 0 0.1 0.3] [--humans 5] [--seed 0]
+           [--human-nums 5 10 [--unseen 7]]
            [--eval-envs 100] [--test-size 500] [--log-every K] [--out policy.pt] [--json FILE]
 """
 import argparse
@@ -58,6 +63,9 @@ def main():
     ap.add_argument("--value-coef", type=float, default=0.5)
     ap.add_argument("--sigma-frac", type=float, nargs="+", default=[0.0, 0.1, 0.3])
     ap.add_argument("--humans", type=int, default=5)
+    ap.add_argument("--human-nums", type=int, nargs="+", default=None,
+                    help="clone on an env of varying human count; every row per density")
+    ap.add_argument("--unseen", type=int, default=7, help="with --human-nums: a density the cloning never saw")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--eval-envs", type=int, default=100)
     ap.add_argument("--test-size", type=int, default=500)
@@ -67,6 +75,8 @@ def main():
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("imitation_pretrain: needs a GPU")
+    if args.human_nums and args.policy != "srnn":
+        raise SystemExit("imitation_pretrain: --human-nums is the DSRNN policy's (no LiDAR on a mixed engine)")
     log = logging.getLogger("imitation_pretrain")
     log.addHandler(logging.NullHandler())
     log.propagate = False
@@ -83,43 +93,68 @@ def main():
     c.ppo.num_mini_batch = args.mini_batch
     E, EE = args.envs, args.eval_envs
     lines = []
+    # the densities every row is evaluated at (one, the env's own, without --human-nums), and the training config
+    densities = sorted(set(args.human_nums) | {args.unseen}) if args.human_nums else [args.humans]
+    ct = clone_config(c)
+    if args.human_nums:
+        ct.sim.human_nums = list(args.human_nums)
+        ct.sim.human_nums_scripted = True
 
     def emit(row):
         lines.append(json.dumps(row))
         print(lines[-1], flush=True)
 
-    def test_envs():
-        return CrowdNavVecEnv(c, EE, c.env.seed, DEV, allow_early_resets=True, nenv=EE, phase="test")
+    def density_config(n):
+        cn = clone_config(c)
+        cn.sim.human_num = n
+        return cn
 
-    def evaluate_policy(pol):
-        envs = test_envs()
-        keep = getattr(pol.base, "nenv", None)   # (the DSRNN reads its batch shape from attributes)
-        if keep is not None:
-            pol.base.nenv = EE
-        try:
-            evaluate(pol, None, envs, EE, DEV, c, log, keep_traces=False, verbose=False)
-        finally:
+    def test_envs(cn):
+        return CrowdNavVecEnv(cn, EE, cn.env.seed, DEV, allow_early_resets=True, nenv=EE, phase="test")
+
+    def evaluate_policy(pol, row):
+        """One row per density: the policy itself on its own env, or (--human-nums) a Policy of that size with the
+        same state_dict on the plain test env of that count."""
+        for n in densities:
+            cn = density_config(n)
+            envs = test_envs(cn)
+            p = pol
+            if args.human_nums:
+                p = Policy(envs.observation_space.spaces, envs.action_space, base="srnn", base_kwargs=cn).to(DEV)
+                p.load_state_dict(pol.state_dict())
+                p.train(pol.training)
+            keep = getattr(p.base, "nenv", None)   # (the DSRNN reads its batch shape from attributes)
             if keep is not None:
-                pol.base.nenv = keep
-            envs.close()
+                p.base.nenv = EE
+            try:
+                evaluate(p, None, envs, EE, DEV, cn, log, keep_traces=False, verbose=False)
+            finally:
+                if keep is not None:
+                    p.base.nenv = keep
+                envs.close()
+            emit(rates(dict(row, humans=n, **({"trained_on": args.human_nums} if args.human_nums else {}))))
 
-    def fresh_policy(spaces, action_space):
+    def fresh_policy(spaces, action_space, cfg):
         torch.manual_seed(args.seed)
-        return Policy(spaces, action_space, base=args.policy, base_kwargs=c).to(DEV)
+        return Policy(spaces, action_space, base=args.policy, base_kwargs=cfg).to(DEV)
 
-    envs = test_envs()
-    evaluate_scripted(args.expert, envs, EE, DEV, c, log, keep_traces=False, verbose=False)
-    emit(rates({"row": "expert", "policy": args.policy, "expert": args.expert, "episodes": args.test_size}))
+    for n in densities:
+        envs = test_envs(density_config(n))
+        evaluate_scripted(args.expert, envs, EE, DEV, density_config(n), log, keep_traces=False, verbose=False)
+        emit(rates({"row": "expert", "policy": args.policy, "expert": args.expert, "humans": n,
+                    "episodes": args.test_size}))
+        envs.close()
+    # the policy's spaces and size: the training env's (a varied env: the padded observation, the largest count)
+    envs = CrowdNavVecEnv(ct, E, args.seed, DEV, allow_early_resets=True, nenv=E, phase="train")
     spaces = envs.observation_space if args.policy == "convgru" else envs.observation_space.spaces
-    action_space = envs.action_space
+    action_space, cpol = envs.action_space, envs.config
     envs.close()
-    pol = fresh_policy(spaces, action_space)
-    evaluate_policy(pol)
-    emit(rates({"row": "untrained", "policy": args.policy, "episodes": args.test_size}))
+    evaluate_policy(fresh_policy(spaces, action_space, cpol), {"row": "untrained", "policy": args.policy,
+                                                               "episodes": args.test_size})
     for frac in args.sigma_frac:
-        pol = fresh_policy(spaces, action_space)
-        envs = CrowdNavVecEnv(c, E, args.seed, DEV, allow_early_resets=True, nenv=E, phase="train")
-        bc = BehaviourCloning(c, envs, pol, expert=args.expert, sigma=frac * float(c.robot.v_pref), seed=args.seed,
+        pol = fresh_policy(spaces, action_space, cpol)
+        envs = CrowdNavVecEnv(ct, E, args.seed, DEV, allow_early_resets=True, nenv=E, phase="train")
+        bc = BehaviourCloning(ct, envs, pol, expert=args.expert, sigma=frac * float(c.robot.v_pref), seed=args.seed,
                               epochs=args.epochs, lr=args.lr, value_coef=args.value_coef)
         torch.cuda.synchronize()
         t0 = time.time()
@@ -135,13 +170,13 @@ def main():
             gpu_upd += st["update_s"]
         wall = time.time() - t0
         envs.close()
-        evaluate_policy(pol)
-        emit(rates({"row": "bc", "policy": args.policy, "expert": args.expert, "sigma_frac": frac, "sigma": frac * float(c.robot.v_pref),
-                    "updates": args.updates, "envs": E, "steps": args.steps, "epochs": args.epochs, "lr": args.lr,
-                    "env_steps": bc.env_steps, "nll_first": round(first["nll"], 4), "nll_last": round(st["nll"], 4),
-                    "value_loss_last": round(st["value_loss"], 4), "train_wall_s": round(wall, 2),
-                    "rollout_gpu_s": round(gpu_roll, 3), "update_gpu_s": round(gpu_upd, 3),
-                    "episodes": args.test_size}))
+        evaluate_policy(pol, {"row": "bc", "policy": args.policy, "expert": args.expert, "sigma_frac": frac,
+                              "sigma": frac * float(c.robot.v_pref),
+                              "updates": args.updates, "envs": E, "steps": args.steps, "epochs": args.epochs, "lr": args.lr,
+                              "env_steps": bc.env_steps, "nll_first": round(first["nll"], 4), "nll_last": round(st["nll"], 4),
+                              "value_loss_last": round(st["value_loss"], 4), "train_wall_s": round(wall, 2),
+                              "rollout_gpu_s": round(gpu_roll, 3), "update_gpu_s": round(gpu_upd, 3),
+                              "episodes": args.test_size})
     if args.out:
         torch.save(pol.state_dict(), args.out)
     if args.json:
