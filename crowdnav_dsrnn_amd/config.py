@@ -96,6 +96,11 @@ class Config(object):
     robot.v_pref = 1
     robot.sensor = "coordinates"
     robot.FOV = 2.0
+    # scripted_unicycle (this project's opt-in, not a reference option; with action_space.kinematics = 'unicycle'):
+    # the env also serves the scripted controllers -- robot_act, rollout, ScriptedRobot, evaluate_scripted,
+    # BehaviourCloning -- whose velocity a tracking law turns into the unicycle action (the engine's
+    # cn_scripted_unicycle). Off, the default, those refuse a unicycle env with UnsupportedConfig, as before.
+    robot.scripted_unicycle = False
 
     noise = BaseConfig()
     noise.add_noise = False

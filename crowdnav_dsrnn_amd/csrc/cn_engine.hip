@@ -2520,6 +2520,30 @@ __device__ __forceinline__ void robot_pref_velocity(const cn_state_ptrs &S, int6
     else { ox = (float)vx; oy = (float)vy; }
 }
 
+// The unicycle robot's tracking law (this project's definition: the reference has no scripted unicycle robot).
+// From a controller's ActionXY (ux, uy) -- the float32 pair the holonomic path writes -- and env e's heading
+// theta = r_theta and speed v = r_dv, the (dv, dtheta) action cn_step takes on a unicycle engine: turn towards the
+// velocity's direction by at most 0.1, and move the speed by at most 0.1 towards the velocity's projection on the
+// heading the step will then have, never backwards. The limits are phase 0's clip of the action, which is therefore
+// a no-op on the result. Float64, no contraction, one rounding to float32. One lane per env.
+// Shared by cn_robot_act's kernels and cn_step_kernel's rollout variant: one arithmetic, bit for bit.
+__device__ __forceinline__ void robot_unicycle_track(const cn_state_ptrs &S, int64_t e, float ux, float uy, float &a0,
+                                                     float &a1)
+{
+    const double theta = S.r_theta[e], v = S.r_dv[e];
+    const double s = np_norm2((double)ux, (double)uy);
+    double turn = 0.0, target = 0.0;
+    if (s != 0.0) {
+        const double delta = remainder(atan2((double)uy, (double)ux) - theta, 2 * CN_PI);   // IEEE: in [-pi, pi]
+        turn = delta < -0.1 ? -0.1 : (delta > 0.1 ? 0.1 : delta);
+        const double along = cos(delta - turn);
+        target = s * (along > 0.0 ? along : 0.0);
+    }
+    const double dv = target - v;
+    a0 = (float)(dv < -0.1 ? -0.1 : (dv > 0.1 ? 0.1 : dv));
+    a1 = (float)turn;
+}
+
 // The two halves of ORCA.predict on the quad path (N + 1 <= 10 agents), quad-cooperative, with a wave-level LDS
 // ordering point (wsync) between them at the caller: the ORCA lines of env e's robot into Lq [<= 9] (returns
 // their number), then RVO2's linear programs on them. Every lane of the quad gets the new velocity.
@@ -2941,6 +2965,8 @@ __global__ void __launch_bounds__(CN_BLK, 3) cn_step_kernel(StepArgs g, cn_confi
         // stores, an auto-reset's included, are visible after that step's closing barrier). The ORCA lines lie over
         // the step's ORCA scratch (16 envs x 9 float4 = 2304 B at o_lines, idle until phase 2 and smaller than one
         // RNG region, so SL::app behind the plan is out of reach). A quad is whole or absent (q < nenv_here).
+        // On a unicycle engine (cn_scripted_unicycle) robot_unicycle_track reads r_theta and r_dv the same way: every
+        // step stores both at its end, and an inline reset's come before the same barrier.
         if ((tid >> 6) == 0) {
             float *const arow = const_cast<float *>(actions);
             // cn_rollout_noisy's launches (wave-uniform): the step takes the perturbed action, the `actions` row keeps
@@ -2957,6 +2983,7 @@ __global__ void __launch_bounds__(CN_BLK, 3) cn_step_kernel(StepArgs g, cn_confi
                     float ax, ay;
                     if (nn > vpref) { ax = (float)(ddiv(nx, nn) * vpref); ay = (float)(ddiv(ny, nn) * vpref); }
                     else { ax = (float)nx; ay = (float)ny; }
+                    if (!holo) robot_unicycle_track(S, e0 + tid, ax, ay, ax, ay);   // (launch-uniform)
                     const int64_t oa = orow(ov, e0 + tid);   // the env's row in the caller's buffers (and noise key)
                     arow[2 * oa] = ax; arow[2 * oa + 1] = ay;
                     if (noisy) {
@@ -2979,6 +3006,9 @@ __global__ void __launch_bounds__(CN_BLK, 3) cn_step_kernel(StepArgs g, cn_confi
                     float rx, ry;
                     robot_orca_solve(S, e, cnt, sq, Lq, rx, ry);
                     if (sq == 0) {
+                        // a unicycle engine (launch-uniform): the quad's lane 0 alone turns the velocity into the
+                        // step's (dv, dtheta); no lane reads another's registers here
+                        if (!holo) robot_unicycle_track(S, e, rx, ry, rx, ry);
                         const int64_t oa = orow(ov, e);   // (addresses only: the quad's lanes and flow are as ever)
                         arow[2 * oa] = rx; arow[2 * oa + 1] = ry;
                         if (noisy) {

@@ -252,6 +252,9 @@ __global__ void __launch_bounds__(64) cn_sf_predict_kernel(int64_t n, int M, con
 // Each has a twin for a group of a mixed engine (cn_robot_*_mix_kernel: the same body with MIX), where env e's action
 // goes to row rows[e] of `actions`. The map changes that address alone, never which lanes run; the plain kernels
 // carry no argument for it and compile as before.
+// uni (launch-uniform: the engine's kinematics is unicycle, served after cn_scripted_unicycle): the lane that stores
+// the action first turns the controller's velocity into the step's (dv, dtheta) with robot_unicycle_track. Which
+// lanes run, and the quads' control flow up to that store, do not depend on it.
 // ------------------------------------------------------------------------------------------------
 // (robot_sim_agent, robot_pref_velocity, robot_orca_lines / robot_orca_solve and robot_sf_velocity are defined above
 // cn_step_kernel, whose rollout variant computes the same actions inside its multi-step launches)
@@ -259,25 +262,7 @@ __global__ void __launch_bounds__(64) cn_sf_predict_kernel(int64_t n, int M, con
 // `act` depends on the quad alone, so a quad is whole or absent and its control flow uniform (DESIGN.md §4,
 // "Cross-lane reads"): the quad's 4 lanes read the same state words.
 __global__ void __launch_bounds__(64) cn_robot_orca_kernel(cn_state_ptrs S, int E, int N, double safety, float nd,
-                                                           float th, float ts, float *__restrict__ actions)
-{
-    __shared__ float4 Ls[16][9];
-    const int q = threadIdx.x >> 2, sq = threadIdx.x & 3;
-    const int64_t e = (int64_t)blockIdx.x * 16 + q;
-    const bool act = e < E;
-    int cnt = 0;
-    if (act) cnt = robot_orca_lines(S, safety, e, N, sq, nd, th, ts, Ls[q]);
-    wsync();
-    if (act) {
-        float rx, ry;
-        robot_orca_solve(S, e, cnt, sq, Ls[q], rx, ry);
-        if (sq == 0) { actions[2 * e] = rx; actions[2 * e + 1] = ry; }
-    }
-}
-// (the twin restates the dozen lines above: as a shared body the plain kernel came out with other registers)
-__global__ void __launch_bounds__(64) cn_robot_orca_mix_kernel(cn_state_ptrs S, int E, int N, double safety, float nd,
-                                                               float th, float ts, float *__restrict__ actions,
-                                                               const int32_t *__restrict__ rows)
+                                                           float th, float ts, float *__restrict__ actions, int uni)
 {
     __shared__ float4 Ls[16][9];
     const int q = threadIdx.x >> 2, sq = threadIdx.x & 3;
@@ -290,6 +275,28 @@ __global__ void __launch_bounds__(64) cn_robot_orca_mix_kernel(cn_state_ptrs S, 
         float rx, ry;
         robot_orca_solve(S, e, cnt, sq, Ls[q], rx, ry);
         if (sq == 0) {
+            if (uni) robot_unicycle_track(S, e, rx, ry, rx, ry);   // (launch-uniform; lane 0 of the quad alone)
+            actions[2 * e] = rx; actions[2 * e + 1] = ry;
+        }
+    }
+}
+// (the twin restates the dozen lines above: as a shared body the plain kernel came out with other registers)
+__global__ void __launch_bounds__(64) cn_robot_orca_mix_kernel(cn_state_ptrs S, int E, int N, double safety, float nd,
+                                                               float th, float ts, float *__restrict__ actions,
+                                                               const int32_t *__restrict__ rows, int uni)
+{
+    __shared__ float4 Ls[16][9];
+    const int q = threadIdx.x >> 2, sq = threadIdx.x & 3;
+    const int64_t e = (int64_t)blockIdx.x * 16 + q;
+    const bool act = e < E;
+    int cnt = 0;
+    if (act) cnt = robot_orca_lines(S, safety, e, N, sq, nd, th, ts, Ls[q]);
+    wsync();
+    if (act) {
+        float rx, ry;
+        robot_orca_solve(S, e, cnt, sq, Ls[q], rx, ry);
+        if (sq == 0) {
+            if (uni) robot_unicycle_track(S, e, rx, ry, rx, ry);
             const int64_t o = rows[e];
             actions[2 * o] = rx; actions[2 * o + 1] = ry;
         }
@@ -301,7 +308,7 @@ __global__ void __launch_bounds__(64) cn_robot_orca_mix_kernel(cn_state_ptrs S, 
 template <bool MIX>
 __device__ __forceinline__ void robot_orca_kd_body(const cn_state_ptrs &S, int E, int N, double safety, float nd,
                                                    float th, float ts, float *__restrict__ actions,
-                                                   const int32_t *__restrict__ rows)
+                                                   const int32_t *__restrict__ rows, int uni)
 {
     extern __shared__ __attribute__((aligned(16))) char kd_smem[];
     const int A = N + 1;
@@ -344,47 +351,52 @@ __device__ __forceinline__ void robot_orca_kd_body(const cn_state_ptrs &S, int E
         const int fail_at = lp2_q<uint64_t>(Lq, cnt, vmax, ox, oy, sq, rx, ry);
         if (fail_at < cnt) lp3_q<uint64_t>(Lq, Pq, cnt, fail_at, vmax, sq, rx, ry);
         if (sq == 0) {
+            if (uni) robot_unicycle_track(S, e, rx, ry, rx, ry);
             const int64_t o = MIX ? (int64_t)rows[e] : e;
             actions[2 * o] = rx; actions[2 * o + 1] = ry;
         }
     }
 }
 __global__ void __launch_bounds__(64) cn_robot_orca_kd_kernel(cn_state_ptrs S, int E, int N, double safety, float nd,
-                                                              float th, float ts, float *__restrict__ actions)
+                                                              float th, float ts, float *__restrict__ actions, int uni)
 {
-    robot_orca_kd_body<false>(S, E, N, safety, nd, th, ts, actions, nullptr);
+    robot_orca_kd_body<false>(S, E, N, safety, nd, th, ts, actions, nullptr, uni);
 }
 __global__ void __launch_bounds__(64) cn_robot_orca_kd_mix_kernel(cn_state_ptrs S, int E, int N, double safety, float nd,
                                                                   float th, float ts, float *__restrict__ actions,
-                                                                  const int32_t *__restrict__ rows)
+                                                                  const int32_t *__restrict__ rows, int uni)
 {
-    robot_orca_kd_body<true>(S, E, N, safety, nd, th, ts, actions, rows);
+    robot_orca_kd_body<true>(S, E, N, safety, nd, th, ts, actions, rows, uni);
 }
 
 // Social force: cn_sf_predict_kernel's float64 arithmetic on the robot's FullState and the N belief humans,
 // one lane per env; the ActionXY rounded to float32
 template <bool MIX>
 __device__ __forceinline__ void robot_sf_body(const cn_state_ptrs &S, int E, int N, double A, double B, double KI,
-                                              double dt, float *__restrict__ actions, const int32_t *__restrict__ rows)
+                                              double dt, float *__restrict__ actions, const int32_t *__restrict__ rows,
+                                              int uni)
 {
     const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= E) return;
     double nx, ny, nn, vpref;
     robot_sf_velocity(S, e, N, A, B, KI, dt, nx, ny, nn, vpref);
     const int64_t o = MIX ? (int64_t)rows[e] : e;
-    if (nn > vpref) { actions[2 * o] = (float)(ddiv(nx, nn) * vpref); actions[2 * o + 1] = (float)(ddiv(ny, nn) * vpref); }
-    else { actions[2 * o] = (float)nx; actions[2 * o + 1] = (float)ny; }
+    float ax, ay;
+    if (nn > vpref) { ax = (float)(ddiv(nx, nn) * vpref); ay = (float)(ddiv(ny, nn) * vpref); }
+    else { ax = (float)nx; ay = (float)ny; }
+    if (uni) robot_unicycle_track(S, e, ax, ay, ax, ay);
+    actions[2 * o] = ax; actions[2 * o + 1] = ay;
 }
 __global__ void __launch_bounds__(64) cn_robot_sf_kernel(cn_state_ptrs S, int E, int N, double A, double B, double KI,
-                                                         double dt, float *__restrict__ actions)
+                                                         double dt, float *__restrict__ actions, int uni)
 {
-    robot_sf_body<false>(S, E, N, A, B, KI, dt, actions, nullptr);
+    robot_sf_body<false>(S, E, N, A, B, KI, dt, actions, nullptr, uni);
 }
 __global__ void __launch_bounds__(64) cn_robot_sf_mix_kernel(cn_state_ptrs S, int E, int N, double A, double B, double KI,
                                                              double dt, float *__restrict__ actions,
-                                                             const int32_t *__restrict__ rows)
+                                                             const int32_t *__restrict__ rows, int uni)
 {
-    robot_sf_body<true>(S, E, N, A, B, KI, dt, actions, rows);
+    robot_sf_body<true>(S, E, N, A, B, KI, dt, actions, rows, uni);
 }
 
 // cn_rollout_noisy outside the fused launches: the perturbation between cn_robot_act's kernel and the step. `act` is

@@ -803,30 +803,31 @@ static int robot_act_launch(const cn_engine *g, hipStream_t st, int policy, floa
 {
     const cn_config &c = g->c;
     const int32_t *const rows = g->rows;   // a group: the *_mix_kernel twins (the same bodies, the actions at rows[e])
+    const int uni = c.kinematics != CN_HOLONOMIC;   // (cn_scripted_unicycle let it through): robot_unicycle_track
     const dim3 quads((unsigned)((g->E + 15) / 16)), lanes((unsigned)((g->E + 63) / 64));
     const float nd = (float)c.orca_neighbor_dist, th = (float)c.orca_time_horizon, ts = (float)c.time_step;
     (void)hipGetLastError();   // a stale error of an earlier call (any library) is not this launch's
     if (policy == CN_ROBOT_SOCIAL_FORCE) {
         if (rows)
             hipLaunchKernelGGL(cn_robot_sf_mix_kernel, lanes, dim3(64), 0, st, g->s, g->E, g->N, c.sf_A, c.sf_B, c.sf_KI,
-                               c.time_step, actions, rows);
+                               c.time_step, actions, rows, uni);
         else
             hipLaunchKernelGGL(cn_robot_sf_kernel, lanes, dim3(64), 0, st, g->s, g->E, g->N, c.sf_A, c.sf_B, c.sf_KI,
-                               c.time_step, actions);
+                               c.time_step, actions, uni);
     } else if (g->N + 1 > 10) {
         if (rows)
             hipLaunchKernelGGL(cn_robot_orca_kd_mix_kernel, quads, dim3(64), orca_kd_lds(g->N + 1), st, g->s, g->E, g->N,
-                               c.orca_safety_space, nd, th, ts, actions, rows);
+                               c.orca_safety_space, nd, th, ts, actions, rows, uni);
         else
             hipLaunchKernelGGL(cn_robot_orca_kd_kernel, quads, dim3(64), orca_kd_lds(g->N + 1), st, g->s, g->E, g->N,
-                               c.orca_safety_space, nd, th, ts, actions);
+                               c.orca_safety_space, nd, th, ts, actions, uni);
     } else {
         if (rows)
             hipLaunchKernelGGL(cn_robot_orca_mix_kernel, quads, dim3(64), 0, st, g->s, g->E, g->N, c.orca_safety_space, nd,
-                               th, ts, actions, rows);
+                               th, ts, actions, rows, uni);
         else
             hipLaunchKernelGGL(cn_robot_orca_kernel, quads, dim3(64), 0, st, g->s, g->E, g->N, c.orca_safety_space, nd, th,
-                               ts, actions);
+                               ts, actions, uni);
     }
     HIPCHK(hipGetLastError());
     return CN_OK;
@@ -841,6 +842,16 @@ int cn_mixed_scripted(cn_engine *g, int on)
     return CN_OK;
 }
 
+// The scripted calls on a unicycle engine (plain, or a mixed engine with a unicycle group) are an opt-in as well: on,
+// the controllers' velocity goes through robot_unicycle_track and the calls return the step's (dv, dtheta); off, they
+// refuse the engine as they always have. A holonomic engine computes what it computed either way.
+int cn_scripted_unicycle(cn_engine *g, int on)
+{
+    if (!g) return set_err(CN_EINVAL, "null engine");
+    g->scripted_uni = on ? 1 : 0;
+    return CN_OK;
+}
+
 // A mixed engine (after cn_mixed_scripted): one controller launch per group, side by side like the groups' step
 // launches.
 int cn_robot_act(cn_engine *g, void *stream, int policy, float *actions)
@@ -850,7 +861,7 @@ int cn_robot_act(cn_engine *g, void *stream, int policy, float *actions)
         return set_err(CN_EINVAL, "cn_robot_act: policy CN_ROBOT_ORCA / CN_ROBOT_SOCIAL_FORCE and actions required");
     if (g->ngroups && !g->scripted)
         return set_err(CN_EUNSUPPORTED, "cn_robot_act: not on a mixed engine (unless cn_mixed_scripted enabled it)");
-    if (!all_holonomic(g))
+    if (!all_holonomic(g) && !g->scripted_uni)
         return set_err(CN_EUNSUPPORTED, g->ngroups ? "cn_robot_act: not on a unicycle mixed engine (the controllers return ActionXY)"
                                                    : "cn_robot_act: the controllers return ActionXY (holonomic engines only)");
     const hipStream_t st = (hipStream_t)stream;
@@ -975,7 +986,7 @@ static int rollout_run(cn_engine *g, void *stream, int policy, int T, const cn_r
     if (g->ngroups && ld) return set_err(CN_EUNSUPPORTED, "cn_rollout: not on a mixed engine");
     if (g->ngroups && !g->scripted)
         return set_err(CN_EUNSUPPORTED, "cn_rollout: not on a mixed engine (unless cn_mixed_scripted enabled it)");
-    if (!all_holonomic(g))
+    if (!all_holonomic(g) && !g->scripted_uni)
         return set_err(CN_EUNSUPPORTED, g->ngroups ? "cn_rollout: not on a unicycle mixed engine (the controllers return ActionXY)"
                                                    : "cn_rollout: the controllers return ActionXY (holonomic engines only)");
     const hipStream_t st = (hipStream_t)stream;

@@ -61,6 +61,7 @@ struct cn_engine {
     hipStream_t *gstream;   // [ngroups]: group k > 0 steps on gstream[k] (forked from / joined to the caller's)
     hipEvent_t *gev;        // [ngroups + 1]: fork, then one join event per forked group
     int scripted;           // cn_mixed_scripted: cn_robot_act / cn_rollout / cn_rollout_noisy serve this mixed engine
+    int scripted_uni;       // cn_scripted_unicycle: they (and cn_rollout_lidar) serve unicycle kinematics
 };
 
 // unit-circle table of GEOS's 64-gon point buffer (norm zones), per device; every entry point whose

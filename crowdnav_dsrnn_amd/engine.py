@@ -17,7 +17,8 @@ from . import _lib, abi
 class RolloutNoise:
     """The perturbation of a rollout with noise (cn_rollout_noise): the executed action is the scripted robot's
     plus sigma * n, n uniform in [-1, 1) per component; step0 is the index of the call's first step in the caller's
-    noise sequence (a chunked rollout continues it: step0 += T)."""
+    noise sequence (a chunked rollout continues it: step0 += T). sigma is in the units of the action: m/s on a
+    holonomic engine; on a unicycle engine (scripted_unicycle) the action is (dv, dtheta) and 0.1 is its whole range."""
     sigma: float
     seed: int = 0
     step0: int = 0
@@ -53,7 +54,9 @@ class CrowdNavEngine:
     Returned tensors are the engine's own buffers (overwritten by the next call); clone to keep them.
     """
 
-    def __init__(self, cfg, device=None, _mixed=None):
+    def __init__(self, cfg, device=None, _mixed=None, scripted_unicycle=False):
+        """scripted_unicycle=True (cn_scripted_unicycle; see scripted_unicycle()): robot_act and rollout serve this
+        engine when its kinematics is unicycle. Off, the default, they refuse a unicycle engine as before."""
         import torch
 
         self.torch = torch
@@ -86,6 +89,8 @@ class CrowdNavEngine:
             self.groups = [(arr[g], np.nonzero(eg == g)[0].astype(np.int32)) for g in range(len(cfgs))
                            if (eg == g).any()]
         self._h = h
+        if scripted_unicycle:
+            self.scripted_unicycle(True)
         nb = ctypes.c_int64()
         _lib.check(L.cn_state_bytes(h, ctypes.byref(nb)))
         self.state_bytes = nb.value
@@ -109,7 +114,7 @@ class CrowdNavEngine:
         self.seq_chunk = 32   # steps per multi-step launch (the library's CN_SEQ_CHUNK; set_seq_chunk)
 
     @classmethod
-    def mixed(cls, cfgs, env_group, device=None, scripted=False):
+    def mixed(cls, cfgs, env_group, device=None, scripted=False, scripted_unicycle=False):
         """One engine over envs of several configurations (cn_create_mixed): env r runs
         cfgs[env_group[r]] (its own human count, scenarios, radius, ...). N = the largest human count;
         spatial_edges rows past an env's own count are padding (`human_mask` False): a never-seen human
@@ -117,8 +122,17 @@ class CrowdNavEngine:
         config.make_mixed_cn_configs.
         scripted=True (cn_mixed_scripted; holonomic groups): robot_act and rollout (with noise=) serve this engine,
         every group on its own stream by the rule of a plain engine of its count. Off, the default, they refuse a
-        mixed engine as before. step_seq needs no opt-in; rollout(lidar=) and graph mode are never served."""
-        return cls(None, device, _mixed=(list(cfgs), env_group, bool(scripted)))
+        mixed engine as before. step_seq needs no opt-in; rollout(lidar=) and graph mode are never served.
+        scripted_unicycle=True (cn_scripted_unicycle) on top of scripted=True: unicycle groups are served as well."""
+        return cls(None, device, _mixed=(list(cfgs), env_group, bool(scripted)), scripted_unicycle=scripted_unicycle)
+
+    def scripted_unicycle(self, on=True):
+        """cn_scripted_unicycle: with on, robot_act and rollout (noise=, lidar= included) serve unicycle kinematics.
+        The controller's velocity (ux, uy) then goes through the tracking law of include/crowdnav.h
+        (policy_factory.unicycle_track restates it) on the device, and 'actions' holds the unicycle action
+        (dv, dtheta) that step() takes, both within [-0.1, 0.1]. A rollout's noise sigma is in those action units:
+        0.1 is the whole range. Off: a unicycle engine is refused as before. A holonomic engine is not affected."""
+        _lib.check(_lib.lib().cn_scripted_unicycle(self._h, int(bool(on))))
 
     # -------------------------------------------------------------------------------------------
     def _stream(self):

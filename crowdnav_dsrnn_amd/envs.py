@@ -243,14 +243,17 @@ class CrowdNavVecEnv:
         self.device = torch.device(device)
         if engine_device is None and self.device.type == "cuda":
             engine_device = self.device
+        # robot.scripted_unicycle: the scripted controllers serve unicycle kinematics (the engine's opt-in)
+        uni = bool(getattr(config.robot, "scripted_unicycle", False))
         if mixed is not None:
             self.engine = CrowdNavEngine.mixed(mixed[0], mixed[1], engine_device,
-                                               scripted=bool(getattr(config.sim, "human_nums_scripted", False)))
+                                               scripted=bool(getattr(config.sim, "human_nums_scripted", False)),
+                                               scripted_unicycle=uni)
             assert self.engine.env_humans.tolist() == self.env_human_nums
             # the observation's 'detected_human_num': constant over the env's life, (E, 1) float32 on the engine's GPU
             self._detected = self.engine.env_humans.to(torch.float32).reshape(self.num_envs, 1)
         else:
-            self.engine = CrowdNavEngine(self.cn_cfg, engine_device)
+            self.engine = CrowdNavEngine(self.cn_cfg, engine_device, scripted_unicycle=uni)
         # 'convgru' observation (crowd_sim_dict.py:57-62, 96-101): robot state + the episode's LiDAR scan (or the
         # live one)
         self.obs_mode = "convgru" if getattr(config.robot, "policy", "srnn") == "convgru" else "srnn"
@@ -358,7 +361,9 @@ class CrowdNavVecEnv:
         """The scripted robot's action ('orca' / 'social_force') for the state the last reset / step returned:
         (E, 2) float32 on the engine's GPU (CrowdNavEngine.robot_act; no host synchronisation). An env of varying
         human count (sim.human_nums) with sim.human_nums_scripted: every env by the controller of its own count;
-        without that opt-in: UnsupportedConfig."""
+        without that opt-in: UnsupportedConfig. A unicycle env with robot.scripted_unicycle: the unicycle action
+        (dv, dtheta) the tracking law derives from the controller's velocity, what step_device takes; without that
+        opt-in the engine refuses."""
         _no_varied(self.config, "robot_act")
         return self.engine.robot_act(policy)
 
@@ -373,7 +378,10 @@ class CrowdNavVecEnv:
         episode's reset, which is state between steps and no function of a recorded row: UnsupportedConfig.
         An env of varying human count (sim.human_nums) with sim.human_nums_scripted: spatial_edges is padded as the
         env's observation is and the dict gains 'detected_human_num' (T, E, 1), an expanded view of the env's constant
-        (E, 1) tensor; without that opt-in: UnsupportedConfig."""
+        (E, 1) tensor; without that opt-in: UnsupportedConfig.
+        A unicycle env with robot.scripted_unicycle: 'actions' holds unicycle actions (dv, dtheta), each within
+        [-0.1, 0.1], and the noise sigma is in those action units (0.1 is the whole range); without that opt-in the
+        engine refuses."""
         _no_varied(self.config, "rollout")
         lidar = None
         if self.obs_mode == "convgru":

@@ -322,7 +322,8 @@ def evaluate_scripted(name, eval_envs, num_processes, device, config, logging, c
     past test_size go to the recorder's spare slot, so the steps a chunk runs past the last counted episode do
     not change the records: they equal evaluate(ScriptedRobot(eval_envs, name), ...)'s.
     `noise` (engine.RolloutNoise or a dict with sigma / seed / step0): the controller's executed actions are perturbed
-    (ScriptedRobot.rollout's noise; the chunks continue step0), i.e. the report is the noisy expert's."""
+    (ScriptedRobot.rollout's noise; the chunks continue step0), i.e. the report is the noisy expert's. On a unicycle
+    env (config.robot.scripted_unicycle) sigma is in action units, where 0.1 is the whole range."""
     from .engine import RolloutNoise
     from .policy_factory import ScriptedRobot
 

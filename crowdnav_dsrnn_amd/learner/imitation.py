@@ -23,6 +23,11 @@ largest count): the rollout runs
 on the mixed engine and records the padded observation into the same storage tensors; the storage's
 'detected_human_num' rows, constant over the env's life, are filled once, and the policy reads them as under PPO (the
 attention of ops.spatial_attention_var).
+
+A unicycle env (action_space.kinematics 'unicycle' with the opt-in config.robot.scripted_unicycle): the expert's
+velocity goes through the tracking law on the device (policy_factory.unicycle_track) and the labels are the unicycle
+actions (dv, dtheta), each within [-0.1, 0.1]. `sigma` is then in those action units -- 0.1 is the whole range, so
+0.03 there is a large perturbation -- and the step clips the perturbed action.
 """
 import contextlib
 import time
@@ -43,7 +48,7 @@ class BehaviourCloning:
         from ..config import UnsupportedConfig
         from ..policy_factory import ScriptedRobot
 
-        ScriptedRobot.check(envs, expert)   # unknown controller / unicycle: before anything touches the GPU
+        ScriptedRobot.check(envs, expert)   # unknown controller / unicycle without its opt-in: before anything touches the GPU
         mode = getattr(envs, "obs_mode", "srnn")
         self.convgru = mode == "convgru"
         if self.convgru:

@@ -22,6 +22,7 @@ CrowdNavVecEnv with 'orca' / 'social_force' computed on the device from the engi
 """
 import collections
 import ctypes
+import math
 
 import numpy as np
 
@@ -241,6 +242,39 @@ def predict_batch(policies, states):
     return out
 
 
+def unicycle_track(vxy, theta, v):
+    """The unicycle robot's tracking law on the host (numpy float64), for a robot driven from a host-side `predict`:
+    from desired velocities vxy (..., 2) -- an ORCA / SOCIAL_FORCE ActionXY -- and the robot's heading `theta` and
+    speed `v` (the engine's r_theta and r_dv), the (..., 2) float32 unicycle actions (dv, dtheta) that the env's step
+    takes. What cn_robot_act / cn_rollout compute on the device after cn_scripted_unicycle (include/crowdnav.h):
+
+        s = |vxy|;  s == 0: dtheta = 0, target = 0
+        else: delta = remainder(atan2(vy, vx) - theta, 2 pi);  dtheta = clip(delta, -0.1, 0.1)
+              target = s * max(0, cos(delta - dtheta))         (on the heading the step will have; never backwards)
+        dv = clip(target - v, -0.1, 0.1)
+
+    The velocity is rounded to float32 first, as the device controllers round theirs. The transcendental functions
+    are the C library's (math.atan2 / remainder / cos per row), not numpy's vector variants, which may differ from
+    them in the last bit.
+    Both components lie in [-0.1, 0.1], the range the step clips a unicycle action to."""
+    vxy = np.asarray(vxy, np.float32).astype(np.float64)   # (the squares below are then exact: one rounding in s)
+    ux, uy, theta, v = np.broadcast_arrays(vxy[..., 0], vxy[..., 1], np.asarray(theta, np.float64),
+                                           np.asarray(v, np.float64))
+    out = np.empty(ux.shape + (2,), np.float64)
+    flat = out.reshape(-1, 2)
+    for k, (x, y, th, sp) in enumerate(zip(ux.ravel().tolist(), uy.ravel().tolist(), theta.ravel().tolist(),
+                                           v.ravel().tolist())):
+        s = math.sqrt(x * x + y * y)
+        turn = target = 0.0
+        if s != 0.0:
+            delta = math.remainder(math.atan2(y, x) - th, 2.0 * math.pi)
+            turn = min(max(delta, -0.1), 0.1)
+            target = s * max(0.0, math.cos(delta - turn))
+        flat[k, 0] = min(max(target - sp, -0.1), 0.1)
+        flat[k, 1] = turn
+    return out.astype(np.float32)
+
+
 class _ScriptedBase:
     """The one attribute evaluate() reads of an actor's `base` (it sizes the edge RNN state by it)."""
 
@@ -256,8 +290,10 @@ class ScriptedRobot:
 
         evaluate(ScriptedRobot(venv, 'orca'), None, venv, E, device, config, logging)
 
-    The env's config keeps robot.policy 'srnn' / 'convgru' (that selects the observation); holonomic only,
-    as the controllers return ActionXY. On an env of varying human count (config.sim.human_nums, with the opt-in
+    The env's config keeps robot.policy 'srnn' / 'convgru' (that selects the observation); holonomic, as the
+    controllers return ActionXY, or unicycle with the opt-in config.robot.scripted_unicycle, where a tracking law
+    (unicycle_track) turns the controller's velocity into the unicycle action on the device. There a rollout's noise
+    sigma is in action units: 0.1 is the whole range. On an env of varying human count (config.sim.human_nums, with the opt-in
     config.sim.human_nums_scripted) every env is driven by the controller of its own count; `base.human_num` is the
     padded (largest) one."""
 
@@ -265,15 +301,17 @@ class ScriptedRobot:
 
     @classmethod
     def check(cls, venv, name):
-        """UnsupportedConfig for an unknown controller, a unicycle config, or an env of varying human count
+        """UnsupportedConfig for an unknown controller, a unicycle config without the opt-in
+        config.robot.scripted_unicycle, or an env of varying human count
         (config.sim.human_nums) without the opt-in config.sim.human_nums_scripted (before anything touches the
         GPU)."""
         if name not in cls.NAMES:
             raise UnsupportedConfig("ScriptedRobot: %r (one of %s)" % (name, ", ".join(cls.NAMES)))
         config = venv.config
-        if config.action_space.kinematics != "holonomic":
+        if config.action_space.kinematics != "holonomic" and not getattr(config.robot, "scripted_unicycle", False):
             raise UnsupportedConfig("ScriptedRobot: action_space.kinematics=%r (the controllers return ActionXY: "
-                                    "holonomic only)" % config.action_space.kinematics)
+                                    "holonomic only, unless config.robot.scripted_unicycle puts the tracking law "
+                                    "behind them)" % config.action_space.kinematics)
         if getattr(config.sim, "human_nums", None) is not None and not getattr(config.sim, "human_nums_scripted", False):
             raise UnsupportedConfig("ScriptedRobot: an env of varying human count (config.sim.human_nums) serves the "
                                     "scripted controllers only with config.sim.human_nums_scripted")

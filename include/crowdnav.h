@@ -199,6 +199,23 @@ int cn_env_humans(const cn_engine *eng, int32_t *dst);
  * as described there; off (the default, and what an engine was before this call existed) they return
  * CN_EUNSUPPORTED for it. Host state only, no launch. CN_EINVAL: NULL or a plain engine (which they always serve). */
 int cn_mixed_scripted(cn_engine *eng, int on);
+/* Opt-in of any engine: with on != 0, cn_robot_act, cn_rollout, cn_rollout_noisy and cn_rollout_lidar serve unicycle
+ * kinematics (a plain unicycle engine; a mixed engine with a unicycle group once cn_mixed_scripted allows it at all).
+ * The controller's float32 velocity (ux, uy) -- what a holonomic engine returns -- then goes through the tracking law
+ * below, on the device in the same launch, and the calls return and step the unicycle action (dv, dtheta) that
+ * cn_step takes. With theta = r_theta, v = r_dv of the env's state, float64 without contraction:
+ *   s = norm2(ux, uy)
+ *   s == 0:  a1 = 0, target = 0
+ *   else:    delta = remainder(atan2(uy, ux) - theta, 2 pi)     (IEEE remainder: in [-pi, pi])
+ *            a1 = clip(delta, -0.1, 0.1)
+ *            target = s * max(0, cos(delta - a1))                (on the heading the step will have; never backwards)
+ *   a0 = clip(target - v, -0.1, 0.1);  action = ((float)a0, (float)a1)
+ * The limits are the step's own clip of a unicycle action, so that clip does not change a clean action.
+ * cn_rollout_noisy's sigma is in these action units here (0.1 is the whole range): the label row keeps the clean
+ * pair, `executed` and the step get the perturbed one, which the step clips.
+ * Off (the default, and what an engine was before this call existed) the four calls return CN_EUNSUPPORTED for
+ * unicycle kinematics. A holonomic engine computes the same either way. Host state only, no launch. CN_EINVAL: NULL. */
+int cn_scripted_unicycle(cn_engine *eng, int on);
 
 /* Reset all envs (fresh episodes, case_counter continues). obs out: robot_node [E][7], temporal [E][2],
  * spatial [E][N][2] float32. */
@@ -506,8 +523,10 @@ int cn_social_force_predict(void *stream, int64_t n, int M, const double *self, 
  *     unless humans.random_radii).
  * A mixed engine after cn_mixed_scripted(eng, 1): one launch per group, side by side (group 0 on `stream`, the others
  * forked from and joined to it), each with the kernel its own count selects; env r's action at row r of `actions`.
+ * A unicycle engine after cn_scripted_unicycle(eng, 1): `actions` holds the unicycle action (dv, dtheta) its tracking
+ * law derives from the controller's velocity.
  * CN_EUNSUPPORTED: a unicycle engine (the controllers return ActionXY), a mixed engine without that opt-in or with a
- * unicycle group;
+ * unicycle group (unicycle: unless cn_scripted_unicycle enabled it);
  * CN_EINVAL: an unknown policy or actions = NULL. */
 #define CN_ROBOT_ORCA 0
 #define CN_ROBOT_SOCIAL_FORCE 1
@@ -535,7 +554,10 @@ int cn_robot_act(cn_engine *eng, void *stream, int policy, float *actions);
  * where its own count allows and as launch pairs otherwise, its envs at their rows of the (T, E, ..) buffers
  * (spatial_edges padded to the largest count, the padding written as cn_step writes it); *num_launches counts the
  * launches of all groups. While a cn_profile window is open on it: launch pairs, a step at a time.
- * CN_EUNSUPPORTED: a unicycle engine, a mixed engine without the opt-in or with a unicycle group. CN_EINVAL: an
+ *   A unicycle engine after cn_scripted_unicycle(eng, 1) is served by the same rule (fused or launch pairs), its
+ * actions rows holding (dv, dtheta).
+ * CN_EUNSUPPORTED: a unicycle engine, a mixed engine without the opt-in or with a unicycle group (unicycle: unless
+ * cn_scripted_unicycle enabled it). CN_EINVAL: an
  * unknown policy, T < 0, out / actions / an
  * observation pointer NULL. All are checked before any launch (*num_launches = 0). T = 0 launches nothing. */
 typedef struct cn_rollout_out {
@@ -571,7 +593,8 @@ int cn_rollout(cn_engine *eng, void *stream, int policy, int T, const cn_rollout
  * CN_EINVAL: noise NULL, sigma < 0 or not finite, and cn_rollout's; CN_EUNSUPPORTED: cn_rollout's. All are checked
  * before any launch (*num_launches = 0). */
 typedef struct cn_rollout_noise {
-    float    sigma;     /* half-width of the uniform perturbation per action component (m/s); finite, >= 0 */
+    float    sigma;     /* half-width of the uniform perturbation per action component (m/s; on a unicycle engine in
+                           its action units, where 0.1 is the whole range); finite, >= 0 */
     uint32_t seed;
     int64_t  step0;     /* index of this call's first step in the caller's noise sequence (chunked calls continue it) */
     float   *executed;  /* [T][E][2] optional: the action the step actually took */
@@ -602,7 +625,7 @@ int cn_rollout_noisy(cn_engine *eng, void *stream, int policy, int T, const cn_r
  *     indices stay in int range. + 1 for the copy into `executed` when noise is given with sigma == 0.
  * CN_EINVAL: lidar NULL, a NULL buffer in it, cn_lidar_scan's (beams in [2, 4096], max_range in (0, 1e4] and at
  * least two 0.01 m samples), cn_rollout_noisy's for a non-NULL noise, cn_rollout's. CN_EUNSUPPORTED: cn_rollout's
- * (a unicycle engine), and any mixed engine (no LiDAR there). All are checked before any launch
+ * (a unicycle engine without cn_scripted_unicycle), and any mixed engine (no LiDAR there). All are checked before any launch
  * (*num_launches = 0). T = 0 launches nothing. */
 struct cn_rollout_lidar {   /* (no typedef: the function below has the name, as stat() and struct stat) */
     float  *obs;           /* [T][E][7 + beams]: the ConvGRU observation AFTER step t, what cn_lidar_scan writes for that state */

@@ -17,8 +17,11 @@ rows, are the same.
 human_nums[g % len] humans) and prints, after each overall row, one row per distinct count from the report's
 per-count block (evaluate.last["per_count"]).
 
+--kinematics unicycle runs it on the unicycle robot (config.robot.scripted_unicycle: the controller's velocity goes
+through the tracking law on the device, policy_factory.unicycle_track), on either loop.
+
 Usage: python tools/baseline_eval.py [--envs 100] [--test-size 500] [--humans 5 | --human-nums 5 10] [--rollout]
-           [--out FILE]
+           [--kinematics holonomic|unicycle] [--out FILE]
 """
 import argparse
 import json
@@ -45,6 +48,8 @@ def main():
     ap.add_argument("--human-nums", type=int, nargs="+", default=None,
                     help="an env of varying human count (one mixed engine); adds the per-count rows")
     ap.add_argument("--rollout", action="store_true", help="evaluate on whole rollouts (evaluate_scripted)")
+    ap.add_argument("--kinematics", default="holonomic", choices=("holonomic", "unicycle"),
+                    help="unicycle: the controllers drive the unicycle robot through the tracking law")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -62,6 +67,8 @@ def main():
                 c.sim.human_nums_scripted = True
             c.env.test_size = args.test_size
             c.robot.visible = visible
+            c.action_space.kinematics = args.kinematics
+            c.robot.scripted_unicycle = args.kinematics == "unicycle"
             E = args.envs
             envs = CrowdNavVecEnv(c, E, c.env.seed, "cuda:0", allow_early_resets=True, nenv=E, phase="test")
             t0 = time.time()
@@ -72,7 +79,7 @@ def main():
             wall = time.time() - t0
             last = evaluate.last
             nav = last["metrics"]["navigation time"]
-            rec = {"robot": name, "robot_visible": visible, "humans": args.human_nums or args.humans,
+            rec = {"robot": name, "robot_visible": visible, "kinematics": args.kinematics, "humans": args.human_nums or args.humans,
                    "episodes": args.test_size,
                    "envs": E, "path": "rollout" if args.rollout else "step",
                    "counts": {k: int(v["total"]) for k, v in last["num_events"].items()},

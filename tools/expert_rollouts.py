@@ -30,8 +30,13 @@ lidar.live, and the file also holds (cn_rollout_lidar)
 --noise-sigma S (m/s) injects noise: the steps take actions + S * uniform[-1, 1) per component (cn_rollout_noisy, seed
 --noise-seed), the labels stay clean; the chunks continue one noise sequence (step0 = steps done so far).
 
+--kinematics unicycle drives the unicycle robot (config.robot.scripted_unicycle): `actions` holds the unicycle action
+(dv, dtheta) the tracking law derives from the controller's velocity, each within [-0.1, 0.1], and --noise-sigma is
+ABSOLUTE in those action units (0.1 is the whole range); the step clips the perturbed action.
+
 Usage: python tools/expert_rollouts.py --out demos.npz [--robot orca] [--envs 256] [--steps 512] [--humans 5]
                                        [--seed 0] [--chunk-steps 128] [--noise-sigma S] [--noise-seed K] [--lidar]
+                                       [--kinematics holonomic|unicycle]
 """
 import argparse
 import os
@@ -59,15 +64,19 @@ def main():
     ap.add_argument("--humans", type=int, default=5)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--chunk-steps", type=int, default=128, help="steps per rollout call (bounds the device buffers)")
-    ap.add_argument("--noise-sigma", type=float, default=None, help="perturb the executed action (labels stay clean)")
+    ap.add_argument("--noise-sigma", type=float, default=None, help="perturb the executed action (labels stay clean); m/s, or with --kinematics unicycle absolute in "
+                         "action units, where 0.1 is the whole range")
     ap.add_argument("--noise-seed", type=int, default=0)
+    ap.add_argument("--kinematics", default="holonomic", choices=("holonomic", "unicycle"),
+                    help="unicycle: the controller drives the unicycle robot through the tracking law")
     ap.add_argument("--lidar", action="store_true", help="record the live LiDAR observation and the state rows as well")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("expert_rollouts: needs a GPU")
     c = clone_config(Config())
     c.sim.human_num = args.humans
-    c.action_space.kinematics = "holonomic"
+    c.action_space.kinematics = args.kinematics
+    c.robot.scripted_unicycle = args.kinematics == "unicycle"
     if args.lidar:
         c.robot.policy = "convgru"
         c.lidar.enable = True
@@ -104,6 +113,7 @@ def main():
         data["lidar_robot_radius"] = np.array(float(lc["robot_radius"]))
     data["pairing"] = np.array("obs[t] -> actions[t]")
     data["robot"] = np.array(args.robot)
+    data["kinematics"] = np.array(args.kinematics)
     if args.noise_sigma is not None:
         data["noise_sigma"], data["noise_seed"] = np.array(args.noise_sigma), np.array(args.noise_seed)
     np.savez_compressed(args.out, **data)

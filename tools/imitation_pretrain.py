@@ -15,11 +15,15 @@ sigma's policy (keys as the reference checkpoints'), ready for RolloutTrainer / 
 policy built for the largest count, and evaluates every row per density: at each trained count and at --unseen (7),
 on a plain test VecEnv of that count with a Policy of that size loaded from the same state_dict (as
 tools/train_varied.py does); the expert row of a density is the expert on that plain env.
+--kinematics unicycle runs all of it on the unicycle robot (config.robot.scripted_unicycle): the expert's velocity
+goes through the tracking law on the device and the labels are the unicycle actions (dv, dtheta), each within
+[-0.1, 0.1]. There the noise is given with --sigma, ABSOLUTE in those action units (0.1 is the whole range; --sigma-frac
+is not read).
 Needs a GPU.
 
 Usage: python tools/imitation_pretrain.py [--policy srnn|convgru] [--expert orca] [--updates 3000] [--envs 1024] [--steps 32] [--epochs 1]
            [--mini-batch 2] [--lr 1e-3] [--value-coef 0.5] [--sigma-frac 0 0.1 0.3] [--humans 5] [--seed 0]
-           [--human-nums 5 10 [--unseen 7]]
+           [--human-nums 5 10 [--unseen 7]] [--kinematics holonomic|unicycle [--sigma 0 0.03]]
            [--eval-envs 100] [--test-size 500] [--log-every K] [--out policy.pt] [--json FILE]
 """
 import argparse
@@ -62,6 +66,11 @@ def main():
     ap.add_argument("--lr", type=float, default=1e-3)
     ap.add_argument("--value-coef", type=float, default=0.5)
     ap.add_argument("--sigma-frac", type=float, nargs="+", default=[0.0, 0.1, 0.3])
+    ap.add_argument("--kinematics", default="holonomic", choices=("holonomic", "unicycle"),
+                    help="unicycle: clone the controller driving the unicycle robot through the tracking law")
+    ap.add_argument("--sigma", type=float, nargs="+", default=[0.0, 0.03],
+                    help="with --kinematics unicycle: the noise half-widths, absolute, in action units (0.1 is the "
+                         "whole range of an action component); replaces --sigma-frac there")
     ap.add_argument("--humans", type=int, default=5)
     ap.add_argument("--human-nums", type=int, nargs="+", default=None,
                     help="clone on an env of varying human count; every row per density")
@@ -82,7 +91,11 @@ def main():
     log.propagate = False
     c = clone_config(Config())
     c.sim.human_num = args.humans
-    c.action_space.kinematics = "holonomic"
+    c.action_space.kinematics = args.kinematics
+    uni = args.kinematics == "unicycle"
+    c.robot.scripted_unicycle = uni
+    # (sigma, the fraction it was given as or None): holonomic in fractions of v_pref, unicycle absolute
+    sigmas = [(s, None) for s in args.sigma] if uni else [(f * float(c.robot.v_pref), f) for f in args.sigma_frac]
     if args.policy == "convgru":
         c.robot.policy = "convgru"
         c.lidar.enable = True
@@ -142,6 +155,7 @@ def main():
         envs = test_envs(density_config(n))
         evaluate_scripted(args.expert, envs, EE, DEV, density_config(n), log, keep_traces=False, verbose=False)
         emit(rates({"row": "expert", "policy": args.policy, "expert": args.expert, "humans": n,
+                    "kinematics": args.kinematics,
                     "episodes": args.test_size}))
         envs.close()
     # the policy's spaces and size: the training env's (a varied env: the padded observation, the largest count)
@@ -150,11 +164,12 @@ def main():
     action_space, cpol = envs.action_space, envs.config
     envs.close()
     evaluate_policy(fresh_policy(spaces, action_space, cpol), {"row": "untrained", "policy": args.policy,
+                                                               "kinematics": args.kinematics,
                                                                "episodes": args.test_size})
-    for frac in args.sigma_frac:
+    for sigma, frac in sigmas:
         pol = fresh_policy(spaces, action_space, cpol)
         envs = CrowdNavVecEnv(ct, E, args.seed, DEV, allow_early_resets=True, nenv=E, phase="train")
-        bc = BehaviourCloning(ct, envs, pol, expert=args.expert, sigma=frac * float(c.robot.v_pref), seed=args.seed,
+        bc = BehaviourCloning(ct, envs, pol, expert=args.expert, sigma=sigma, seed=args.seed,
                               epochs=args.epochs, lr=args.lr, value_coef=args.value_coef)
         torch.cuda.synchronize()
         t0 = time.time()
@@ -164,14 +179,14 @@ def main():
             st = bc.update()
             first = first or st
             if args.log_every and (u + 1) % args.log_every == 0:
-                print("sigma_frac %g update %d nll %.4f value_loss %.4f" % (frac, u + 1, st["nll"], st["value_loss"]),
+                print("sigma %g update %d nll %.4f value_loss %.4f" % (sigma, u + 1, st["nll"], st["value_loss"]),
                       file=sys.stderr, flush=True)
             gpu_roll += st["rollout_s"]
             gpu_upd += st["update_s"]
         wall = time.time() - t0
         envs.close()
         evaluate_policy(pol, {"row": "bc", "policy": args.policy, "expert": args.expert, "sigma_frac": frac,
-                              "sigma": frac * float(c.robot.v_pref),
+                              "sigma": sigma, "kinematics": args.kinematics,
                               "updates": args.updates, "envs": E, "steps": args.steps, "epochs": args.epochs, "lr": args.lr,
                               "env_steps": bc.env_steps, "nll_first": round(first["nll"], 4), "nll_last": round(st["nll"], 4),
                               "value_loss_last": round(st["value_loss"], 4), "train_wall_s": round(wall, 2),

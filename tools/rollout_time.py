@@ -13,7 +13,11 @@ is reported (us per step) with the rounds' spread. Needs a GPU; prints one JSON 
 --noise-sigma S runs the two cn_rollout paths through cn_rollout_noisy with that sigma (0: its cn_rollout path plus the
 copy into `executed`); the Python loop stays the clean one.
 
-Usage: python tools/rollout_time.py [--envs 4096] [--steps 256] [--noise-sigma S] [--out FILE]
+--kinematics unicycle times the same paths on the unicycle robot (the engine's cn_scripted_unicycle opt-in: the
+tracking law between the controller and the step); --configs a b restricts the run to some configurations.
+
+Usage: python tools/rollout_time.py [--envs 4096] [--steps 256] [--noise-sigma S] [--kinematics holonomic|unicycle]
+           [--configs a b c d] [--out FILE]
 """
 import argparse
 import json
@@ -43,6 +47,8 @@ def main():
     ap.add_argument("--envs", type=int, default=4096)
     ap.add_argument("--steps", type=int, default=256)
     ap.add_argument("--noise-sigma", type=float, default=None)
+    ap.add_argument("--kinematics", default="holonomic", choices=("holonomic", "unicycle"))
+    ap.add_argument("--configs", nargs="+", default=["a", "b", "c", "d"], choices=("a", "b", "c", "d"))
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -52,11 +58,15 @@ def main():
     noise = None if args.noise_sigma is None else {"sigma": args.noise_sigma, "seed": 1, "step0": 0}
     kw = {} if noise is None else {"noise": noise}
     for tag, N, name in (("a", 5, "orca"), ("b", 9, "orca"), ("c", 10, "social_force"), ("d", 5, "social_force")):
+        if tag not in args.configs:
+            continue
         c = clone_config(Config())
         c.sim.human_num = N
-        c.action_space.kinematics = "holonomic"
+        c.action_space.kinematics = args.kinematics
         c.humans.policy = "orca"
         eng = CrowdNavEngine(make_cn_config(c, num_envs=E), "cuda:0")
+        if args.kinematics == "unicycle":
+            eng.scripted_unicycle(True)
         chunk = eng.seq_chunk
         eng.reset()
         eng.step(eng.robot_act(name))   # (the first step after cn_reset is a pair on every path)
@@ -81,7 +91,7 @@ def main():
         for _ in range(3):
             for k, fn in fns.items():
                 rounds[k].append(timed(fn, T))
-        rec = {"config": tag, "envs": E, "humans": N, "robot": name, "steps": T, "chunk": chunk,
+        rec = {"config": tag, "kinematics": args.kinematics, "envs": E, "humans": N, "robot": name, "steps": T, "chunk": chunk,
                "noise_sigma": args.noise_sigma,
                "unit": "us per step (HIP events)", "device": torch.cuda.get_device_name(0), "launches": launches}
         for k, v in rounds.items():
