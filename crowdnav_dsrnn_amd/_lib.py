@@ -60,6 +60,9 @@ class RolloutLidar(ctypes.Structure):
                 ("robot_radius", ctypes.c_double), ("robot_state", ctypes.c_void_p), ("human_state", ctypes.c_void_p)]
 
 
+DwaParams = abi.DwaParams   # cn_dwa_params
+
+
 class NativeLibraryMissing(RuntimeError):
     pass
 
@@ -114,6 +117,12 @@ def lib():
     if hasattr(L, "cn_scripted_unicycle") or not os.environ.get("CN_LIB_PATH"):   # (an older A/B library lacks it)
         L.cn_scripted_unicycle.argtypes = [vp, ctypes.c_int]
         L.cn_scripted_unicycle.restype = i32
+    if hasattr(L, "cn_scripted_dwa") or not os.environ.get("CN_LIB_PATH"):   # (an older A/B library lacks them)
+        L.cn_scripted_dwa.argtypes = [vp, ctypes.POINTER(DwaParams)]
+        L.cn_scripted_dwa.restype = i32
+        L.cn_dwa_predict.argtypes = [vp, i64, ctypes.c_int, vp, vp, vp, ctypes.c_double, ctypes.POINTER(DwaParams), vp,
+                                     vp, vp]
+        L.cn_dwa_predict.restype = i32
     L.cn_destroy.argtypes = [vp]
     L.cn_destroy.restype = None
     L.cn_reset.argtypes = [vp, vp, vp, vp, vp]
@@ -234,7 +243,7 @@ def check(rc):
 
 
 EXPORTED = ["cn_last_error", "cn_version", "cn_config_validate", "cn_create", "cn_create_mixed", "cn_env_humans",
-            "cn_mixed_scripted", "cn_scripted_unicycle", "cn_destroy", "cn_reset", "cn_step", "cn_step_seq",
+            "cn_mixed_scripted", "cn_scripted_unicycle", "cn_scripted_dwa", "cn_dwa_predict", "cn_destroy", "cn_reset", "cn_step", "cn_step_seq",
             "cn_state_bytes", "cn_state_layout_offsets", "cn_state_field_info", "cn_get_state", "cn_set_state",
             "cn_state_device_ptr", "cn_edge_features", "cn_profile", "cn_profile_read", "cn_gru_fwd_step", "cn_gru_fwd_step_scatter",
             "cn_gru_fwd_fused", "cn_gru_bwd_step", "cn_attn_pool_fwd", "cn_attn_pool_bwd", "cn_spatial_attn_fwd",

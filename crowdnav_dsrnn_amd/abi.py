@@ -114,6 +114,22 @@ class CnConfig(ctypes.Structure):
         return c
 
 
+ROBOT_ORCA, ROBOT_SOCIAL_FORCE, ROBOT_DWA = 0, 1, 2   # include/crowdnav.h CN_ROBOT_*
+
+
+class DwaParams(ctypes.Structure):
+    """struct cn_dwa_params (include/crowdnav.h): the dynamic-window controller's horizon and cost weights, the
+    argument of cn_dwa_predict and cn_scripted_dwa."""
+
+    _fields_ = [
+        ("horizon", ctypes.c_int32),
+        ("w_goal", ctypes.c_double),
+        ("w_clear", ctypes.c_double),
+        ("d_safe", ctypes.c_double),
+        ("w_col", ctypes.c_double),
+    ]
+
+
 # --- state blob (include/crowdnav_state.h) ---------------------------------------------------------
 CNT_ENV, CNT_HUM, CNT_PERM, CNT_MT = 0, 1, 2, 3
 _T = {0: np.float64, 1: np.float32, 2: np.int64, 3: np.int32, 4: np.uint32, 5: np.uint8}

@@ -101,6 +101,11 @@ class Config(object):
     # BehaviourCloning -- whose velocity a tracking law turns into the unicycle action (the engine's
     # cn_scripted_unicycle). Off, the default, those refuse a unicycle env with UnsupportedConfig, as before.
     robot.scripted_unicycle = False
+    # scripted_dwa (this project's opt-in as well; with action_space.kinematics = 'unicycle'): the env also serves the
+    # scripted controller 'dwa', a dynamic-window controller that plans in the unicycle's own action space
+    # (policy_factory.dwa_predict; the engine's cn_scripted_dwa). True: policy_factory.DWA_DEFAULTS; a dict: those with
+    # its overrides. None, the default: 'dwa' is refused, as before. It needs no scripted_unicycle (no tracking law).
+    robot.scripted_dwa = None
 
     noise = BaseConfig()
     noise.add_noise = False

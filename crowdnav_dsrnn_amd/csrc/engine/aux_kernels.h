@@ -1,6 +1,6 @@
 // aux_kernels.h -- the small stand-alone kernels: the debug / predictor kernels that expose the step kernel's
 // device functions on caller-given inputs (cn_disc_quad, cn_copy64, cn_orca, cn_orca_kd with RVO2's sequential
-// KdTree, cn_sf_predict), cn_robot_act's three kernels, cn_rollout_noisy's (cn_action_noise_kernel,
+// KdTree, cn_sf_predict, cn_dwa_predict), cn_robot_act's kernels (ORCA, social force, the dynamic window), cn_rollout_noisy's (cn_action_noise_kernel,
 // cn_noise_set_kernel, cn_copy32_kernel), cn_rollout_lidar's (cn_rows_set_kernel, cn_state_rows_kernel), and the
 // two stream-ordered helpers of the host API (cn_ctl_set_kernel, cn_keysnap_kernel). Part of cn_engine.hip's translation unit: included there after the device core, whose
 // geometry, ORCA and scripted-robot functions these kernels call.
@@ -397,6 +397,131 @@ __global__ void __launch_bounds__(64) cn_robot_sf_mix_kernel(cn_state_ptrs S, in
                                                              const int32_t *__restrict__ rows, int uni)
 {
     robot_sf_body<true>(S, E, N, A, B, KI, dt, actions, rows, uni);
+}
+
+// ------------------------------------------------------------------------------------------------
+// The dynamic-window controller of the unicycle robot (include/crowdnav.h, cn_dwa_predict: this project's
+// definition). One 64-lane wave per env, lane c = candidate c = 8a + b of the step's 8 x 8 action grid: every lane
+// walks its own arc over the horizon against the constant-velocity forecast of the M humans, in float64 without
+// contraction, then the wave takes the lexicographic minimum of (J, c) by a shuffle butterfly (ties: the lowest c).
+// The env, and with it every human word, is wave-uniform (the caller forms the env index through readfirstlane), so
+// the humans are read at one address per wave. A lane that reaches the goal stops walking (`go`), the others go on:
+// the loops themselves stay wave-uniform. No LDS, no atomics, no barrier: a wave past the last env returns whole.
+// Shared by cn_dwa_predict's kernel and cn_robot_act's two: one arithmetic, bit for bit.
+// ------------------------------------------------------------------------------------------------
+#define CN_DWA_WAVES 4   // envs per 256-lane workgroup
+
+__device__ __forceinline__ double dwa_grid(int k) { return ddiv(0.1 * (double)(2 * k - 7), 7.0); }
+
+// human(i, bx, by, bvx, bvy, br): belief human i of this wave's env. Returns the lane's cost J; best = the wave's choice.
+template <class Human>
+__device__ __forceinline__ double dwa_choose(Human human, int M, double px, double py, double theta, double v, double r,
+                                             double gx, double gy, double vpref, double dt, const cn_dwa_params &p,
+                                             int lane, int &best)
+{
+    const int H = p.horizon;
+    const double dv = dwa_grid(lane >> 3), dth = dwa_grid(lane & 7);
+    const double sv = v + dv;
+    const double v1 = sv < -vpref ? -vpref : (sv > vpref ? vpref : sv);
+    const double R = ddiv(v1, ddiv(dth, dt));
+    const double cx = px - R * sin(theta), cy = py + R * cos(theta);   // the arc's centre
+    double cmin = __builtin_inf(), gterm = 0.0;
+    int hit = 0;
+    bool go = true;
+    for (int k = 1; k <= H; ++k) {
+        const double phi = theta + (double)k * dth;
+        const double x = cx + R * sin(phi), y = cy - R * cos(phi);
+        const double kt = (double)k * dt;
+        double ck = __builtin_inf();
+        for (int i = 0; i < M; ++i) {
+            double bx, by, bvx, bvy, br;
+            human(i, bx, by, bvx, bvy, br);
+            const double ddx = x - (bx + kt * bvx), ddy = y - (by + kt * bvy);
+            const double c = dsqrt(ddx * ddx + ddy * ddy) - r - br;
+            ck = c < ck ? c : ck;
+        }
+        const double gdx = x - gx, gdy = y - gy;
+        const double gk = dsqrt(gdx * gdx + gdy * gdy);
+        if (go) {
+            cmin = ck < cmin ? ck : cmin;
+            if (ck < 0.0 && hit == 0) hit = H + 1 - k;
+            gterm = gk;
+            if (gk < r) { gterm = 0.0; go = false; }
+        }
+    }
+    const double short_of = p.d_safe - cmin;
+    const double J = (p.w_goal * gterm + ddiv(p.w_clear * (short_of > 0.0 ? short_of : 0.0), p.d_safe))
+                     + p.w_col * (double)hit;
+    double bj = J;
+    int bc = lane;
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const double oj = __shfl_xor(bj, m, 64);
+        const int oc = __shfl_xor(bc, m, 64);
+        if (oj < bj || (oj == bj && oc < bc)) { bj = oj; bc = oc; }
+    }
+    best = bc;
+    return J;
+}
+
+// cn_dwa_predict: the controller on caller-given arrays, env i on wave i
+__global__ void __launch_bounds__(64 * CN_DWA_WAVES) cn_dwa_predict_kernel(int64_t n, int M, const double *__restrict__ self,
+                                                                          const double *__restrict__ v,
+                                                                          const double *__restrict__ others, double dt,
+                                                                          cn_dwa_params p, float *__restrict__ actions,
+                                                                          int32_t *__restrict__ choice,
+                                                                          double *__restrict__ costs)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t i = (int64_t)blockIdx.x * CN_DWA_WAVES + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (i >= n) return;
+    const double *s = self + 9 * i;   // px, py, vx, vy, radius, gx, gy, v_pref, theta
+    const double *o = others + i * M * 5;
+    int best;
+    const double J = dwa_choose(
+        [&](int k, double &bx, double &by, double &bvx, double &bvy, double &br) {
+            bx = o[5 * k]; by = o[5 * k + 1]; bvx = o[5 * k + 2]; bvy = o[5 * k + 3]; br = o[5 * k + 4];
+        },
+        M, s[0], s[1], s[8], v[i], s[4], s[5], s[6], s[7], dt, p, lane, best);
+    if (costs) costs[64 * i + lane] = J;
+    if (lane == 0) {
+        actions[2 * i] = (float)dwa_grid(best >> 3); actions[2 * i + 1] = (float)dwa_grid(best & 7);
+        if (choice) choice[i] = best;
+    }
+}
+
+// cn_robot_act's: the controller on the engine's state, read in place (the robot's FullState with v = r_dv and the N
+// belief humans); a plain kernel and the twin of a mixed engine's group, whose action goes to row rows[e]
+template <bool MIX>
+__device__ __forceinline__ void robot_dwa_body(const cn_state_ptrs &S, int E, int N, double dt, const cn_dwa_params &p,
+                                               float *__restrict__ actions, const int32_t *__restrict__ rows)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t e = (int64_t)blockIdx.x * CN_DWA_WAVES + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (e >= E) return;
+    const int64_t h0 = e * N;
+    int best;
+    dwa_choose(
+        [&](int k, double &bx, double &by, double &bvx, double &bvy, double &br) {
+            bx = S.b_px[h0 + k]; by = S.b_py[h0 + k]; bvx = S.b_vx[h0 + k]; bvy = S.b_vy[h0 + k]; br = S.b_r[h0 + k];
+        },
+        N, S.r_px[e], S.r_py[e], S.r_theta[e], S.r_dv[e], S.r_radius[e], S.r_gx[e], S.r_gy[e], S.r_vpref[e], dt, p, lane,
+        best);
+    if (lane == 0) {
+        const int64_t o = MIX ? (int64_t)rows[e] : e;
+        actions[2 * o] = (float)dwa_grid(best >> 3); actions[2 * o + 1] = (float)dwa_grid(best & 7);
+    }
+}
+__global__ void __launch_bounds__(64 * CN_DWA_WAVES) cn_robot_dwa_kernel(cn_state_ptrs S, int E, int N, double dt,
+                                                                        cn_dwa_params p, float *__restrict__ actions)
+{
+    robot_dwa_body<false>(S, E, N, dt, p, actions, nullptr);
+}
+__global__ void __launch_bounds__(64 * CN_DWA_WAVES) cn_robot_dwa_mix_kernel(cn_state_ptrs S, int E, int N, double dt,
+                                                                            cn_dwa_params p, float *__restrict__ actions,
+                                                                            const int32_t *__restrict__ rows)
+{
+    robot_dwa_body<true>(S, E, N, dt, p, actions, rows);
 }
 
 // cn_rollout_noisy outside the fused launches: the perturbation between cn_robot_act's kernel and the step. `act` is

@@ -807,7 +807,14 @@ static int robot_act_launch(const cn_engine *g, hipStream_t st, int policy, floa
     const dim3 quads((unsigned)((g->E + 15) / 16)), lanes((unsigned)((g->E + 63) / 64));
     const float nd = (float)c.orca_neighbor_dist, th = (float)c.orca_time_horizon, ts = (float)c.time_step;
     (void)hipGetLastError();   // a stale error of an earlier call (any library) is not this launch's
-    if (policy == CN_ROBOT_SOCIAL_FORCE) {
+    if (policy == CN_ROBOT_DWA) {   // (cn_scripted_dwa let it through: a unicycle engine) a wave per env
+        const dim3 waves((unsigned)((g->E + CN_DWA_WAVES - 1) / CN_DWA_WAVES)), wg(64 * CN_DWA_WAVES);
+        if (rows)
+            hipLaunchKernelGGL(cn_robot_dwa_mix_kernel, waves, wg, 0, st, g->s, g->E, g->N, c.time_step, g->dwa_p, actions,
+                               rows);
+        else
+            hipLaunchKernelGGL(cn_robot_dwa_kernel, waves, wg, 0, st, g->s, g->E, g->N, c.time_step, g->dwa_p, actions);
+    } else if (policy == CN_ROBOT_SOCIAL_FORCE) {
         if (rows)
             hipLaunchKernelGGL(cn_robot_sf_mix_kernel, lanes, dim3(64), 0, st, g->s, g->E, g->N, c.sf_A, c.sf_B, c.sf_KI,
                                c.time_step, actions, rows, uni);
@@ -852,16 +859,45 @@ int cn_scripted_unicycle(cn_engine *g, int on)
     return CN_OK;
 }
 
+// cn_dwa_predict's and cn_scripted_dwa's rule for the parameters
+static bool dwa_params_ok(const cn_dwa_params *p)
+{
+    return p && p->horizon >= 1 && p->horizon <= 16 && isfinite(p->w_goal) && isfinite(p->w_clear) &&
+           isfinite(p->w_col) && isfinite(p->d_safe) && p->d_safe > 0;
+}
+
+// CN_ROBOT_DWA is an opt-in of the engine too: off, the id is the unknown policy it always was. The controller emits
+// the unicycle action, so only an engine whose envs are all unicycle can switch it on. A mixed engine's groups launch
+// with their own copy of the parameters.
+int cn_scripted_dwa(cn_engine *g, const cn_dwa_params *p)
+{
+    if (!g) return set_err(CN_EINVAL, "null engine");
+    if (p) {
+        if (!dwa_params_ok(p))
+            return set_err(CN_EINVAL, "cn_scripted_dwa: horizon in [1, 16], d_safe > 0 and finite weights required");
+        bool uni = g->ngroups || g->c.kinematics == CN_UNICYCLE;
+        for (int k = 0; k < g->ngroups; ++k) uni = uni && g->grp[k]->c.kinematics == CN_UNICYCLE;
+        if (!uni) return set_err(CN_EUNSUPPORTED, "cn_scripted_dwa: the controller emits (dv, dtheta): unicycle engines only");
+    }
+    for (int k = -1; k < g->ngroups; ++k) {
+        cn_engine *q = k < 0 ? g : g->grp[k];
+        q->dwa = p ? 1 : 0;
+        if (p) q->dwa_p = *p;
+    }
+    return CN_OK;
+}
+
 // A mixed engine (after cn_mixed_scripted): one controller launch per group, side by side like the groups' step
 // launches.
 int cn_robot_act(cn_engine *g, void *stream, int policy, float *actions)
 {
     if (!g) return set_err(CN_EINVAL, "null engine");
-    if ((policy != CN_ROBOT_ORCA && policy != CN_ROBOT_SOCIAL_FORCE) || !actions)
+    const bool dwa = policy == CN_ROBOT_DWA && g->dwa;   // (without cn_scripted_dwa the id is unknown, as ever)
+    if ((policy != CN_ROBOT_ORCA && policy != CN_ROBOT_SOCIAL_FORCE && !dwa) || !actions)
         return set_err(CN_EINVAL, "cn_robot_act: policy CN_ROBOT_ORCA / CN_ROBOT_SOCIAL_FORCE and actions required");
     if (g->ngroups && !g->scripted)
         return set_err(CN_EUNSUPPORTED, "cn_robot_act: not on a mixed engine (unless cn_mixed_scripted enabled it)");
-    if (!all_holonomic(g) && !g->scripted_uni)
+    if (!dwa && !all_holonomic(g) && !g->scripted_uni)
         return set_err(CN_EUNSUPPORTED, g->ngroups ? "cn_robot_act: not on a unicycle mixed engine (the controllers return ActionXY)"
                                                    : "cn_robot_act: the controllers return ActionXY (holonomic engines only)");
     const hipStream_t st = (hipStream_t)stream;
@@ -895,8 +931,9 @@ static int rollout_steps(cn_engine *g, hipStream_t st, bool fuse, int policy, in
     const RolloutRows rows = {ld ? ld->robot_state : nullptr, ld ? ld->human_state : nullptr, out->actions, (int64_t)T};
     bool rows_set = false;
     const bool every = (out->flags & CN_ROLLOUT_OBS_EVERY_STEP) != 0;
-    // the controller fits the step workgroup: social force (a lane per env) always, ORCA on its quad path
-    const bool fits = policy == CN_ROBOT_SOCIAL_FORCE || g->N + 1 <= 10;
+    // the controller fits the step workgroup: social force (a lane per env) always, ORCA on its quad path, the
+    // dynamic window (a wave per env) never
+    const bool fits = policy == CN_ROBOT_SOCIAL_FORCE || (policy == CN_ROBOT_ORCA && g->N + 1 <= 10);
     const bool fusable = fuse && fits && g->seq_chunk > 1 && !g->devseq && !g->plan.kd;
     const int64_t rollout = (int64_t)policy | ((int64_t)(out->flags & CN_ROLLOUT_OBS_EVERY_STEP) << 8);
     bool block_set = false;
@@ -979,14 +1016,15 @@ static int rollout_run(cn_engine *g, void *stream, int policy, int T, const cn_r
 {
     if (num_launches) *num_launches = 0;
     if (!g) return set_err(CN_EINVAL, "null engine");
-    if ((policy != CN_ROBOT_ORCA && policy != CN_ROBOT_SOCIAL_FORCE) || T < 0 || !out || !out->actions ||
+    const bool dwa = policy == CN_ROBOT_DWA && g->dwa;   // (without cn_scripted_dwa the id is unknown, as ever)
+    if ((policy != CN_ROBOT_ORCA && policy != CN_ROBOT_SOCIAL_FORCE && !dwa) || T < 0 || !out || !out->actions ||
         !out->robot_node || !out->temporal_edges || !out->spatial_edges)
         return set_err(CN_EINVAL, "cn_rollout: policy CN_ROBOT_ORCA / CN_ROBOT_SOCIAL_FORCE, T >= 0, out with actions "
                                   "and the observation buffers required");
     if (g->ngroups && ld) return set_err(CN_EUNSUPPORTED, "cn_rollout: not on a mixed engine");
     if (g->ngroups && !g->scripted)
         return set_err(CN_EUNSUPPORTED, "cn_rollout: not on a mixed engine (unless cn_mixed_scripted enabled it)");
-    if (!all_holonomic(g) && !g->scripted_uni)
+    if (!dwa && !all_holonomic(g) && !g->scripted_uni)
         return set_err(CN_EUNSUPPORTED, g->ngroups ? "cn_rollout: not on a unicycle mixed engine (the controllers return ActionXY)"
                                                    : "cn_rollout: the controllers return ActionXY (holonomic engines only)");
     const hipStream_t st = (hipStream_t)stream;
@@ -1145,6 +1183,21 @@ int cn_social_force_predict(void *stream, int64_t n, int M, const double *self, 
     (void)hipGetLastError();   // a stale error of an earlier call (any library) is not this launch's
     hipLaunchKernelGGL(cn_sf_predict_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, (hipStream_t)stream, n, M,
                        self, others, A, B, KI, time_step, out);
+    HIPCHK(hipGetLastError());
+    return CN_OK;
+}
+
+int cn_dwa_predict(void *stream, int64_t n, int M, const double *self, const double *v, const double *others,
+                   double time_step, const cn_dwa_params *p, float *actions, int32_t *choice, double *costs)
+{
+    if (n <= 0 || n >= (1LL << 31) || M < 0 || M > 64 || !self || !v || (M && !others) || !actions)
+        return set_err(CN_EINVAL, "cn_dwa_predict: 0 < n < 2^31, 0 <= M <= 64 and buffers required");
+    if (!dwa_params_ok(p) || !(time_step > 0) || !isfinite(time_step))
+        return set_err(CN_EINVAL, "cn_dwa_predict: horizon in [1, 16], d_safe > 0, finite weights and time_step > 0 required");
+    (void)hipGetLastError();   // a stale error of an earlier call (any library) is not this launch's
+    hipLaunchKernelGGL(cn_dwa_predict_kernel, dim3((unsigned)((n + CN_DWA_WAVES - 1) / CN_DWA_WAVES)),
+                       dim3(64 * CN_DWA_WAVES), 0, (hipStream_t)stream, n, M, self, v, others, time_step, *p, actions,
+                       choice, costs);
     HIPCHK(hipGetLastError());
     return CN_OK;
 }

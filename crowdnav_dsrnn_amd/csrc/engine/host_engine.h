@@ -62,6 +62,8 @@ struct cn_engine {
     hipEvent_t *gev;        // [ngroups + 1]: fork, then one join event per forked group
     int scripted;           // cn_mixed_scripted: cn_robot_act / cn_rollout / cn_rollout_noisy serve this mixed engine
     int scripted_uni;       // cn_scripted_unicycle: they (and cn_rollout_lidar) serve unicycle kinematics
+    int dwa;                // cn_scripted_dwa: they accept CN_ROBOT_DWA (a mixed engine: set in its groups as well)
+    cn_dwa_params dwa_p;    // ... with these parameters
 };
 
 // unit-circle table of GEOS's 64-gon point buffer (norm zones), per device; every entry point whose

@@ -54,9 +54,12 @@ class CrowdNavEngine:
     Returned tensors are the engine's own buffers (overwritten by the next call); clone to keep them.
     """
 
-    def __init__(self, cfg, device=None, _mixed=None, scripted_unicycle=False):
+    def __init__(self, cfg, device=None, _mixed=None, scripted_unicycle=False, scripted_dwa=None):
         """scripted_unicycle=True (cn_scripted_unicycle; see scripted_unicycle()): robot_act and rollout serve this
-        engine when its kinematics is unicycle. Off, the default, they refuse a unicycle engine as before."""
+        engine when its kinematics is unicycle. Off, the default, they refuse a unicycle engine as before.
+        scripted_dwa=True or a dict of parameter overrides (cn_scripted_dwa; see scripted_dwa()): robot_act and
+        rollout take the policy 'dwa' on this unicycle engine. None, the default: 'dwa' is refused as an unknown
+        policy."""
         import torch
 
         self.torch = torch
@@ -91,6 +94,8 @@ class CrowdNavEngine:
         self._h = h
         if scripted_unicycle:
             self.scripted_unicycle(True)
+        if scripted_dwa is not None and scripted_dwa is not False:
+            self.scripted_dwa(scripted_dwa)
         nb = ctypes.c_int64()
         _lib.check(L.cn_state_bytes(h, ctypes.byref(nb)))
         self.state_bytes = nb.value
@@ -114,7 +119,7 @@ class CrowdNavEngine:
         self.seq_chunk = 32   # steps per multi-step launch (the library's CN_SEQ_CHUNK; set_seq_chunk)
 
     @classmethod
-    def mixed(cls, cfgs, env_group, device=None, scripted=False, scripted_unicycle=False):
+    def mixed(cls, cfgs, env_group, device=None, scripted=False, scripted_unicycle=False, scripted_dwa=None):
         """One engine over envs of several configurations (cn_create_mixed): env r runs
         cfgs[env_group[r]] (its own human count, scenarios, radius, ...). N = the largest human count;
         spatial_edges rows past an env's own count are padding (`human_mask` False): a never-seen human
@@ -123,8 +128,10 @@ class CrowdNavEngine:
         scripted=True (cn_mixed_scripted; holonomic groups): robot_act and rollout (with noise=) serve this engine,
         every group on its own stream by the rule of a plain engine of its count. Off, the default, they refuse a
         mixed engine as before. step_seq needs no opt-in; rollout(lidar=) and graph mode are never served.
-        scripted_unicycle=True (cn_scripted_unicycle) on top of scripted=True: unicycle groups are served as well."""
-        return cls(None, device, _mixed=(list(cfgs), env_group, bool(scripted)), scripted_unicycle=scripted_unicycle)
+        scripted_unicycle=True (cn_scripted_unicycle) on top of scripted=True: unicycle groups are served as well.
+        scripted_dwa (cn_scripted_dwa) on top of scripted=True, every group unicycle: the policy 'dwa' as well."""
+        return cls(None, device, _mixed=(list(cfgs), env_group, bool(scripted)), scripted_unicycle=scripted_unicycle,
+                   scripted_dwa=scripted_dwa)
 
     def scripted_unicycle(self, on=True):
         """cn_scripted_unicycle: with on, robot_act and rollout (noise=, lidar= included) serve unicycle kinematics.
@@ -133,6 +140,45 @@ class CrowdNavEngine:
         (dv, dtheta) that step() takes, both within [-0.1, 0.1]. A rollout's noise sigma is in those action units:
         0.1 is the whole range. Off: a unicycle engine is refused as before. A holonomic engine is not affected."""
         _lib.check(_lib.lib().cn_scripted_unicycle(self._h, int(bool(on))))
+
+    def scripted_dwa(self, params=True):
+        """cn_scripted_dwa: robot_act and rollout (noise=, lidar= included) take the policy 'dwa' on this unicycle
+        engine, the dynamic-window controller of include/crowdnav.h (policy_factory.dwa_predict restates it), with
+        policy_factory.DWA_DEFAULTS (True) or those with a dict's overrides. It emits the unicycle action (dv, dtheta)
+        itself, so scripted_unicycle is not needed for it. None / False: off again -- 'dwa' is refused as an unknown
+        policy, as before. A holonomic engine refuses the opt-in."""
+        from .policy_factory import dwa_params
+
+        if params is None or params is False:
+            _lib.check(_lib.lib().cn_scripted_dwa(self._h, None))
+            return
+        p = abi.DwaParams(**dwa_params(params))
+        _lib.check(_lib.lib().cn_scripted_dwa(self._h, ctypes.byref(p)))
+
+    def dwa_predict(self, self_state, v, others, time_step, params=None, costs=True):
+        """cn_dwa_predict on device tensors: self_state (n, 9) f64 (px, py, vx, vy, radius, gx, gy, v_pref, theta),
+        v (n,) f64 (the robot's speed, r_dv), others (n, M, 5) f64; returns (actions (n, 2) f32, choice (n,) i32,
+        costs (n, 64) f64 or None). One launch on the current stream, no host sync."""
+        from .policy_factory import dwa_params
+
+        t = self.torch
+        n = int(self_state.shape[0])
+        M = int(others.shape[1]) if others is not None and others.numel() else 0
+        for name, x, want in (("self_state", self_state, n * 9), ("v", v, n), ("others", others, n * M * 5)):
+            if x is None and want == 0:
+                continue
+            if x.dtype != t.float64 or x.device != self.device or not x.is_contiguous() or x.numel() != want:
+                raise ValueError("dwa_predict: %s must be a contiguous float64 tensor of %d elements on %s"
+                                 % (name, want, self.device))
+        p = abi.DwaParams(**dwa_params(params))
+        act = t.zeros((n, 2), dtype=t.float32, device=self.device)
+        ch = t.zeros((n,), dtype=t.int32, device=self.device)
+        co = t.zeros((n, 64), dtype=t.float64, device=self.device) if costs else None
+        with t.cuda.device(self.device):
+            _lib.check(_lib.lib().cn_dwa_predict(self._stream(), n, M, self_state.data_ptr(), v.data_ptr(),
+                                                 others.data_ptr() if M else None, float(time_step), ctypes.byref(p),
+                                                 act.data_ptr(), ch.data_ptr(), co.data_ptr() if costs else None))
+        return act, ch, co
 
     # -------------------------------------------------------------------------------------------
     def _stream(self):
@@ -229,12 +275,12 @@ class CrowdNavEngine:
                                                 float(robot_radius), out.data_ptr()))
         return out
 
-    ROBOT_POLICIES = {"orca": 0, "social_force": 1}   # CN_ROBOT_ORCA / CN_ROBOT_SOCIAL_FORCE
+    ROBOT_POLICIES = {"orca": 0, "social_force": 1, "dwa": 2}   # CN_ROBOT_ORCA / CN_ROBOT_SOCIAL_FORCE / CN_ROBOT_DWA
 
     def robot_act(self, policy, out=None):
         """The scripted robot's action for the engine's current state (cn_robot_act): (E, 2) float32 on the
         device, what a fresh policy_factory['orca' | 'social_force'] object predicts from the robot's state and
-        its belief of the humans. Into `out` when given, else into a buffer the engine owns (overwritten by the
+        its belief of the humans ('dwa', after scripted_dwa: what policy_factory.dwa_predict chooses for them). Into `out` when given, else into a buffer the engine owns (overwritten by the
         next call). One launch, no host sync."""
         t = self.torch
         if policy not in self.ROBOT_POLICIES:

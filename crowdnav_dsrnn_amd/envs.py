@@ -245,15 +245,20 @@ class CrowdNavVecEnv:
             engine_device = self.device
         # robot.scripted_unicycle: the scripted controllers serve unicycle kinematics (the engine's opt-in)
         uni = bool(getattr(config.robot, "scripted_unicycle", False))
+        # robot.scripted_dwa (True, or a dict of parameter overrides): the engine's policy 'dwa', unicycle only
+        dwa = getattr(config.robot, "scripted_dwa", None) or None
+        if dwa is not None and config.action_space.kinematics != "unicycle":
+            raise UnsupportedConfig("config.robot.scripted_dwa: the dynamic-window controller emits the unicycle "
+                                    "action (action_space.kinematics=%r)" % config.action_space.kinematics)
         if mixed is not None:
             self.engine = CrowdNavEngine.mixed(mixed[0], mixed[1], engine_device,
                                                scripted=bool(getattr(config.sim, "human_nums_scripted", False)),
-                                               scripted_unicycle=uni)
+                                               scripted_unicycle=uni, scripted_dwa=dwa)
             assert self.engine.env_humans.tolist() == self.env_human_nums
             # the observation's 'detected_human_num': constant over the env's life, (E, 1) float32 on the engine's GPU
             self._detected = self.engine.env_humans.to(torch.float32).reshape(self.num_envs, 1)
         else:
-            self.engine = CrowdNavEngine(self.cn_cfg, engine_device, scripted_unicycle=uni)
+            self.engine = CrowdNavEngine(self.cn_cfg, engine_device, scripted_unicycle=uni, scripted_dwa=dwa)
         # 'convgru' observation (crowd_sim_dict.py:57-62, 96-101): robot state + the episode's LiDAR scan (or the
         # live one)
         self.obs_mode = "convgru" if getattr(config.robot, "policy", "srnn") == "convgru" else "srnn"
@@ -363,7 +368,8 @@ class CrowdNavVecEnv:
         human count (sim.human_nums) with sim.human_nums_scripted: every env by the controller of its own count;
         without that opt-in: UnsupportedConfig. A unicycle env with robot.scripted_unicycle: the unicycle action
         (dv, dtheta) the tracking law derives from the controller's velocity, what step_device takes; without that
-        opt-in the engine refuses."""
+        opt-in the engine refuses. 'dwa': a unicycle env with robot.scripted_dwa (the dynamic-window controller's own
+        unicycle action); without that opt-in the engine refuses it as an unknown policy."""
         _no_varied(self.config, "robot_act")
         return self.engine.robot_act(policy)
 
@@ -381,7 +387,7 @@ class CrowdNavVecEnv:
         (E, 1) tensor; without that opt-in: UnsupportedConfig.
         A unicycle env with robot.scripted_unicycle: 'actions' holds unicycle actions (dv, dtheta), each within
         [-0.1, 0.1], and the noise sigma is in those action units (0.1 is the whole range); without that opt-in the
-        engine refuses."""
+        engine refuses. 'dwa' (a unicycle env with robot.scripted_dwa) likewise, always as launch pairs."""
         _no_varied(self.config, "rollout")
         lidar = None
         if self.obs_mode == "convgru":

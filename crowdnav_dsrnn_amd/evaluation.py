@@ -316,14 +316,15 @@ def evaluate(actor_critic, ob_rms, eval_envs, num_processes, device, config, log
 
 def evaluate_scripted(name, eval_envs, num_processes, device, config, logging, chunk=None, keep_traces=True,
                       verbose=True, noise=None):
-    """evaluate() of the scripted robot `name` ('orca' / 'social_force') on whole rollouts: after reset(), rollouts
+    """evaluate() of the scripted robot `name` ('orca' / 'social_force' / 'dwa') on whole rollouts: after reset(), rollouts
     of `chunk` steps (default: the engine's steps per multi-step launch) through ScriptedRobot.rollout, every
     recorded row fed to the same EpisodeRecorder, the end-of-run check once per chunk, the same report. Episodes
     past test_size go to the recorder's spare slot, so the steps a chunk runs past the last counted episode do
     not change the records: they equal evaluate(ScriptedRobot(eval_envs, name), ...)'s.
     `noise` (engine.RolloutNoise or a dict with sigma / seed / step0): the controller's executed actions are perturbed
     (ScriptedRobot.rollout's noise; the chunks continue step0), i.e. the report is the noisy expert's. On a unicycle
-    env (config.robot.scripted_unicycle) sigma is in action units, where 0.1 is the whole range."""
+    env (config.robot.scripted_unicycle, or 'dwa' with config.robot.scripted_dwa) sigma is in action units, where 0.1
+    is the whole range."""
     from .engine import RolloutNoise
     from .policy_factory import ScriptedRobot
 

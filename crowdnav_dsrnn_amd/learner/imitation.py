@@ -27,7 +27,9 @@ attention of ops.spatial_attention_var).
 A unicycle env (action_space.kinematics 'unicycle' with the opt-in config.robot.scripted_unicycle): the expert's
 velocity goes through the tracking law on the device (policy_factory.unicycle_track) and the labels are the unicycle
 actions (dv, dtheta), each within [-0.1, 0.1]. `sigma` is then in those action units -- 0.1 is the whole range, so
-0.03 there is a large perturbation -- and the step clips the perturbed action.
+0.03 there is a large perturbation -- and the step clips the perturbed action. expert='dwa' (the opt-in
+config.robot.scripted_dwa) is the expert made for that robot: a dynamic-window controller whose labels are grid points
+of the unicycle action space (policy_factory.dwa_predict), with sigma in the same units.
 """
 import contextlib
 import time

@@ -18,7 +18,9 @@ KdTree neighbour order with the persisted agents_ permutation); more than 64 rai
 
 `ScriptedRobot(venv, name)` is the other direction: an actor stand-in that drives the ROBOT of a
 CrowdNavVecEnv with 'orca' / 'social_force' computed on the device from the engine's state
-(`cn_robot_act`), for baseline rows of `evaluate()` and expert rollouts without a host round trip.
+(`cn_robot_act`), for baseline rows of `evaluate()` and expert rollouts without a host round trip. For the
+unicycle robot it also takes 'dwa', this project's dynamic-window controller (`dwa_predict` restates it on the
+host; `DWA_DEFAULTS`; the device side is `cn_dwa_predict` / `cn_scripted_dwa`).
 """
 import collections
 import ctypes
@@ -275,6 +277,99 @@ def unicycle_track(vxy, theta, v):
     return out.astype(np.float32)
 
 
+# The dynamic-window controller's default parameters (cn_dwa_params): the row of the highest success rate on 500
+# validation episodes of the default unicycle config over the grids of tools/dwa_grid.py tabulated in DESIGN.md §4
+# ("A dynamic-window expert for the unicycle robot"; profiles/dwa/grid_val*.jsonl).
+DWA_DEFAULTS = {"horizon": 10, "w_goal": 1.0, "w_clear": 8.0, "d_safe": 2.0, "w_col": 100.0}
+
+
+def dwa_params(params=None):
+    """DWA_DEFAULTS with the overrides of `params` (None / True: none; a dict with some of its keys), checked by the
+    rule of include/crowdnav.h: horizon in 1..16, d_safe > 0, every weight finite."""
+    p = dict(DWA_DEFAULTS)
+    if isinstance(params, dict):
+        extra = set(params) - set(p)
+        if extra:
+            raise ValueError("dwa parameters: unknown keys %s (of %s)" % (sorted(extra), sorted(p)))
+        p.update(params)
+    elif params is not None and params is not True:
+        raise TypeError("dwa parameters: None, True or a dict, got %r" % type(params).__name__)
+    p["horizon"] = int(p["horizon"])
+    for k in ("w_goal", "w_clear", "d_safe", "w_col"):
+        p[k] = float(p[k])
+        if not math.isfinite(p[k]):
+            raise ValueError("dwa parameters: %s must be finite, got %r" % (k, p[k]))
+    if not 1 <= p["horizon"] <= 16 or not p["d_safe"] > 0:
+        raise ValueError("dwa parameters: horizon in 1..16 and d_safe > 0 required, got %r" % (p,))
+    return p
+
+
+DWA_GRID = tuple((0.1 * (2 * k - 7)) / 7 for k in range(8))   # dv of a = k, dtheta of b = k
+
+
+def dwa_predict(self_state, v, others, time_step, params=None, detail=False):
+    """The unicycle robot's dynamic-window controller on the host (Python floats: float64), the definition in
+    include/crowdnav.h restated; what cn_dwa_predict, and cn_robot_act / cn_rollout with the policy 'dwa', compute on
+    the device. self_state (n, 9) = (px, py, vx, vy, radius, gx, gy, v_pref, theta), v (n,) the robot's speed (the
+    engine's r_dv), others (n, M, 5) = (px, py, vx, vy, radius) of the humans; params: see dwa_params.
+    Returns (actions (n, 2) float32, choice (n,) int32, costs (n, 64) float64); with detail=True also a dict of
+    (n, 64) arrays 'hit', 'gterm', 'cmin' and 'sharp' (False where some c_k, or some g_k - r, of the candidate's walk
+    lies within 1e-9 of 0: a last-bit difference of the device's sin / cos could then flip a comparison).
+    math.sin / cos / sqrt per value, not numpy's vector variants, which may differ from them in the last bit."""
+    p = dwa_params(params)
+    H, wg, wc, ds, wk = p["horizon"], p["w_goal"], p["w_clear"], p["d_safe"], p["w_col"]
+    S = np.asarray(self_state, np.float64).reshape(-1, 9)
+    n = len(S)
+    V = np.asarray(v, np.float64).reshape(n)
+    O = np.asarray(others, np.float64).reshape(n, -1, 5)
+    dt = float(time_step)
+    inf = float("inf")
+    sin, cos, sqrt = math.sin, math.cos, math.sqrt
+    costs = np.empty((n, 64), np.float64)
+    hits, gterms, cmins = np.zeros((n, 64), np.int32), np.zeros((n, 64)), np.zeros((n, 64))
+    sharp = np.ones((n, 64), bool)
+    choice = np.zeros(n, np.int32)
+    for e in range(n):
+        px, py, _, _, r, gx, gy, vpref, theta = S[e].tolist()
+        hum = O[e].tolist()
+        s0, c0 = sin(theta), cos(theta)
+        best = 0
+        for c in range(64):
+            dv, dth = DWA_GRID[c >> 3], DWA_GRID[c & 7]
+            v1 = min(max(V[e].item() + dv, -vpref), vpref)
+            R = v1 / (dth / dt)
+            cx, cy = px - R * s0, py + R * c0
+            cmin, hit, gterm, ok = inf, 0, 0.0, True
+            for k in range(1, H + 1):
+                phi = theta + k * dth
+                x, y = cx + R * sin(phi), cy - R * cos(phi)
+                kt = k * dt
+                ck = inf
+                for bx, by, bvx, bvy, br in hum:
+                    dx, dy = x - (bx + kt * bvx), y - (by + kt * bvy)
+                    ck = min(ck, sqrt(dx * dx + dy * dy) - r - br)
+                cmin = min(cmin, ck)
+                if ck < 0.0 and hit == 0:
+                    hit = H + 1 - k
+                dx, dy = x - gx, y - gy
+                gk = sqrt(dx * dx + dy * dy)
+                ok = ok and abs(ck) > 1e-9 and abs(gk - r) > 1e-9
+                gterm = gk
+                if gk < r:
+                    gterm = 0.0
+                    break
+            J = (wg * gterm + (wc * max(0.0, ds - cmin)) / ds) + wk * hit
+            costs[e, c], hits[e, c], gterms[e, c], cmins[e, c], sharp[e, c] = J, hit, gterm, cmin, ok
+            if J < costs[e, best]:
+                best = c
+        choice[e] = best
+    grid = np.array(DWA_GRID, np.float64)
+    actions = np.stack([grid[choice >> 3], grid[choice & 7]], axis=1).astype(np.float32)
+    if detail:
+        return actions, choice, costs, {"hit": hits, "gterm": gterms, "cmin": cmins, "sharp": sharp}
+    return actions, choice, costs
+
+
 class _ScriptedBase:
     """The one attribute evaluate() reads of an actor's `base` (it sizes the edge RNN state by it)."""
 
@@ -285,8 +380,9 @@ class _ScriptedBase:
 class ScriptedRobot:
     """Actor stand-in that drives the robot of a CrowdNavVecEnv with a scripted controller on the device
     (cn_robot_act): the reference's "for orca and sf" robot (crowd_sim.py:1113-1114 -> robot.py:9-15), whose
-    policy predicts from the robot's own state and its belief of the humans. `name`: 'orca' or
-    'social_force'. With it evaluate() and EpisodeRecorder run a baseline unchanged:
+    policy predicts from the robot's own state and its belief of the humans. `name`: 'orca', 'social_force', or
+    'dwa' (this project's dynamic-window controller of the unicycle robot, dwa_predict: unicycle configs with the
+    opt-in config.robot.scripted_dwa; it emits the unicycle action itself, no tracking law). With it evaluate() and EpisodeRecorder run a baseline unchanged:
 
         evaluate(ScriptedRobot(venv, 'orca'), None, venv, E, device, config, logging)
 
@@ -297,18 +393,24 @@ class ScriptedRobot:
     config.sim.human_nums_scripted) every env is driven by the controller of its own count; `base.human_num` is the
     padded (largest) one."""
 
-    NAMES = ("orca", "social_force")
+    NAMES = ("orca", "social_force", "dwa")
 
     @classmethod
     def check(cls, venv, name):
         """UnsupportedConfig for an unknown controller, a unicycle config without the opt-in
-        config.robot.scripted_unicycle, or an env of varying human count
+        config.robot.scripted_unicycle ('dwa': anything but a unicycle config with the opt-in
+        config.robot.scripted_dwa), or an env of varying human count
         (config.sim.human_nums) without the opt-in config.sim.human_nums_scripted (before anything touches the
         GPU)."""
         if name not in cls.NAMES:
             raise UnsupportedConfig("ScriptedRobot: %r (one of %s)" % (name, ", ".join(cls.NAMES)))
         config = venv.config
-        if config.action_space.kinematics != "holonomic" and not getattr(config.robot, "scripted_unicycle", False):
+        if name == "dwa":
+            if config.action_space.kinematics != "unicycle" or not getattr(config.robot, "scripted_dwa", None):
+                raise UnsupportedConfig("ScriptedRobot: 'dwa' plans in the unicycle robot's action space: "
+                                        "action_space.kinematics 'unicycle' with the opt-in config.robot.scripted_dwa "
+                                        "required (kinematics=%r)" % config.action_space.kinematics)
+        elif config.action_space.kinematics != "holonomic" and not getattr(config.robot, "scripted_unicycle", False):
             raise UnsupportedConfig("ScriptedRobot: action_space.kinematics=%r (the controllers return ActionXY: "
                                     "holonomic only, unless config.robot.scripted_unicycle puts the tracking law "
                                     "behind them)" % config.action_space.kinematics)

@@ -31,6 +31,8 @@
  *   cn_gae         ⟵ RolloutStorage.compute_returns with use_gae (storage.py:132-177), one launch per rollout
  *   cn_orca_predict / cn_orca_predict_kd / cn_social_force_predict ⟵ the agent policy plugin
  *                   policy_factory[name](config).predict(JointState) (crowd_nav/policy/policy_factory.py:1-17)
+ *   cn_dwa_predict / cn_scripted_dwa ⟵ (no reference counterpart) a dynamic-window controller that plans in the
+ *                   unicycle robot's own action space; the opt-in makes it cn_robot_act's policy CN_ROBOT_DWA
  *   cn_robot_act     ⟵ Robot.act of a scripted ('orca' / 'social_force') robot on its belief
  *                   (crowd_sim/envs/utils/robot.py:9-15, crowd_sim.py:1113-1114,1185-1188), every env in one launch
  *   cn_rollout       ⟵ the closed loop `action = robot.act(ob); ob, ... = env.step(action)` of a scripted robot
@@ -500,6 +502,43 @@ int cn_orca_predict_kd(void *stream, int64_t n, int A, const float *agents, cons
 int cn_social_force_predict(void *stream, int64_t n, int M, const double *self, const double *others, double A,
                             double B, double KI, double time_step, double *out);
 
+/* The dynamic-window controller of the unicycle robot (no reference counterpart: this project's definition). It plans
+ * in the unicycle's own action space with the step's own kinematics: the 64 candidate actions of one step, each held
+ * over a horizon of H steps, against a constant-velocity forecast of the humans. Per env, float64 without contraction,
+ * every sum and product evaluated left to right as written:
+ *   robot  px, py, theta, v (the engine's r_theta and r_dv), r = radius, goal (gx, gy), vpref;  dt = time_step
+ *   humans i < M: (bx, by, bvx, bvy, br)
+ *   candidate c = 8 a + b, a, b in 0..7:  dv = (0.1 * (2 a - 7)) / 7,  dth = (0.1 * (2 b - 7)) / 7
+ *     (both inside the step's clip range [-0.1, 0.1]; |dth| >= 0.1 / 7, so no candidate falls below the step's
+ *      |dtheta| < 1e-4 rule, under which a unicycle robot does not move at all)
+ *   forecast:  v1 = clip(v + dv, -vpref, vpref),  R = v1 / (dth / dt)
+ *     for k = 1..H:  phi = theta + k * dth
+ *                    x_k = px - R * sin(theta) + R * sin(phi),  y_k = py + R * cos(theta) - R * cos(phi)
+ *     (k = 1 is the step's own arc, which is then held);  human i at step k: (bx + k * dt * bvx, by + k * dt * bvy)
+ *   walk, k upwards, from cmin = +inf, hit = 0:
+ *     c_k = min over i of sqrt(dx * dx + dy * dy) - r - br_i       (+inf when M = 0; dx, dy = robot minus human)
+ *     cmin = min(cmin, c_k);  if c_k < 0 and hit == 0: hit = H + 1 - k
+ *     g_k = sqrt(dx * dx + dy * dy) of (x_k, y_k) minus the goal;  gterm = g_k
+ *     if g_k < r: gterm = 0 and the walk stops
+ *   cost   J = w_goal * gterm + (w_clear * max(0, d_safe - cmin)) / d_safe + w_col * hit
+ *   choice the candidate of the smallest J, the lowest c among equal ones;  action = ((float)dv, (float)dth)
+ * A state or parameter set that makes a J NaN has no defined choice.
+ * cn_dwa_predict: the controller on arrays, n envs of M humans each (0 <= M <= 64, n < 2^31): self [n][9] as
+ *   cn_social_force_predict's (vx, vy are not read), v [n] = r_dv, others [n][M][5] (may be NULL when M = 0);
+ *   out actions [n][2] float32, choice [n] int32 (the chosen c; may be NULL), costs [n][64] (every candidate's J; may
+ *   be NULL). One launch, one 64-lane wavefront per env, a lane per candidate. Device pointers, stream-ordered.
+ *   CN_EINVAL: n <= 0, a NULL required buffer, M out of range, p NULL or bad: horizon outside [1, 16], d_safe <= 0 or
+ *   not finite, a weight not finite. */
+typedef struct cn_dwa_params {
+    int32_t horizon;      /* H: steps of the forecast, 1..16 */
+    double  w_goal;       /* weight of the distance to the goal where the walk ends */
+    double  w_clear;      /* weight of the clearance shortfall max(0, d_safe - cmin) / d_safe */
+    double  d_safe;       /* clearance (m) from which on a candidate pays nothing; > 0 */
+    double  w_col;        /* weight of a forecast collision, times the steps left when it happens (+ 1) */
+} cn_dwa_params;
+int cn_dwa_predict(void *stream, int64_t n, int M, const double *self, const double *v, const double *others,
+                   double time_step, const cn_dwa_params *p, float *actions, int32_t *choice, double *costs);
+
 /* Scripted robot baselines on the device (the "for orca and sf" robot the reference's env anticipates,
  * crowd_sim.py:1113-1114,1185-1188 -> robot.py:9-15, and then crashes on: those policies have no clip_action).
  * actions [E][2] float32 = for every env e, rounded to float32, what a FRESH policy object returns for the
@@ -527,10 +566,22 @@ int cn_social_force_predict(void *stream, int64_t n, int M, const double *self, 
  * law derives from the controller's velocity.
  * CN_EUNSUPPORTED: a unicycle engine (the controllers return ActionXY), a mixed engine without that opt-in or with a
  * unicycle group (unicycle: unless cn_scripted_unicycle enabled it);
- * CN_EINVAL: an unknown policy or actions = NULL. */
+ * CN_EINVAL: an unknown policy or actions = NULL.
+ * CN_ROBOT_DWA, on an engine cn_scripted_dwa enabled it for (before that the id is an unknown policy: CN_EINVAL):
+ * cn_dwa_predict's controller with that call's parameters on the robot (r_px, r_py, r_theta, r_dv, r_radius, r_gx,
+ * r_gy, r_vpref), its belief of the N humans and the config's time_step; `actions` holds the unicycle action
+ * (dv, dtheta). No tracking law is involved, so cn_scripted_unicycle is not needed; a mixed engine still needs
+ * cn_mixed_scripted. One launch (a mixed engine: one per group), as for the other two. */
 #define CN_ROBOT_ORCA 0
 #define CN_ROBOT_SOCIAL_FORCE 1
+#define CN_ROBOT_DWA 2
 int cn_robot_act(cn_engine *eng, void *stream, int policy, float *actions);
+/* Opt-in of a unicycle engine: with p != NULL, cn_robot_act, cn_rollout, cn_rollout_noisy and cn_rollout_lidar accept
+ * CN_ROBOT_DWA for it and run the controller with *p (copied); p = NULL switches it off again (the default, and what
+ * an engine was before this call existed: the id is CN_EINVAL). Policies 0 and 1 are not affected. Host state only,
+ * no launch. CN_EINVAL: eng NULL or bad parameters (cn_dwa_predict's rule); CN_EUNSUPPORTED: p != NULL on an engine
+ * with holonomic envs (the controller emits (dv, dtheta)). */
+int cn_scripted_dwa(cn_engine *eng, const cn_dwa_params *p);
 
 /* Closed-loop scripted rollout: T steps of the scripted robot driving the engine, every step recorded. For
  * t = 0..T-1 the call does cn_robot_act(eng, stream, policy, actions_t) and then cn_step(eng, stream, actions_t,
@@ -556,6 +607,9 @@ int cn_robot_act(cn_engine *eng, void *stream, int policy, float *actions);
  * launches of all groups. While a cn_profile window is open on it: launch pairs, a step at a time.
  *   A unicycle engine after cn_scripted_unicycle(eng, 1) is served by the same rule (fused or launch pairs), its
  * actions rows holding (dv, dtheta).
+ *   CN_ROBOT_DWA (after cn_scripted_dwa) always runs as launch pairs -- the controller takes a wavefront per env, which
+ * the step workgroup does not have to spare -- on a mixed engine each group on its own stream; in cn_rollout_noisy and
+ * cn_rollout_lidar likewise (their `elsewhere` rule).
  * CN_EUNSUPPORTED: a unicycle engine, a mixed engine without the opt-in or with a unicycle group (unicycle: unless
  * cn_scripted_unicycle enabled it). CN_EINVAL: an
  * unknown policy, T < 0, out / actions / an

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""The scripted-robot baseline rows: evaluate() with policy_factory.ScriptedRobot ('orca', 'social_force').
+"""The scripted-robot baseline rows: evaluate() with policy_factory.ScriptedRobot ('orca', 'social_force', 'dwa').
 
 The reference's default test configuration (crowd_nav/configs/config.py: 500 test episodes, 5 ORCA humans,
 holonomic robot, circle radius 6, the four default test scenarios -- taken round-robin by env here, where the
@@ -18,10 +18,15 @@ human_nums[g % len] humans) and prints, after each overall row, one row per dist
 per-count block (evaluate.last["per_count"]).
 
 --kinematics unicycle runs it on the unicycle robot (config.robot.scripted_unicycle: the controller's velocity goes
-through the tracking law on the device, policy_factory.unicycle_track), on either loop.
+through the tracking law on the device, policy_factory.unicycle_track), on either loop, and adds the rows of 'dwa',
+the dynamic-window controller of the unicycle robot (config.robot.scripted_dwa; policy_factory.dwa_predict).
+--robots restricts the run to some controllers; --dwa '{"horizon": 12}' overrides policy_factory.DWA_DEFAULTS;
+--phase val evaluates the validation episodes (the same count, what the defaults were selected on) instead of the test
+episodes; --visible 0 / 1 restricts the run to one visibility.
 
 Usage: python tools/baseline_eval.py [--envs 100] [--test-size 500] [--humans 5 | --human-nums 5 10] [--rollout]
-           [--kinematics holonomic|unicycle] [--out FILE]
+           [--kinematics holonomic|unicycle] [--robots orca dwa] [--dwa JSON] [--phase test|val] [--visible 0|1]
+           [--out FILE]
 """
 import argparse
 import json
@@ -37,7 +42,7 @@ import torch  # noqa: E402
 from crowdnav_dsrnn_amd.config import Config, clone_config  # noqa: E402
 from crowdnav_dsrnn_amd.envs import CrowdNavVecEnv  # noqa: E402
 from crowdnav_dsrnn_amd.evaluation import evaluate, evaluate_scripted  # noqa: E402
-from crowdnav_dsrnn_amd.policy_factory import ScriptedRobot  # noqa: E402
+from crowdnav_dsrnn_amd.policy_factory import ScriptedRobot, dwa_params  # noqa: E402
 
 
 def main():
@@ -50,27 +55,36 @@ def main():
     ap.add_argument("--rollout", action="store_true", help="evaluate on whole rollouts (evaluate_scripted)")
     ap.add_argument("--kinematics", default="holonomic", choices=("holonomic", "unicycle"),
                     help="unicycle: the controllers drive the unicycle robot through the tracking law")
+    ap.add_argument("--robots", nargs="+", default=None, choices=ScriptedRobot.NAMES,
+                    help="the controllers to run (default: all the kinematics serves)")
+    ap.add_argument("--dwa", default=None, help="JSON dict of overrides of policy_factory.DWA_DEFAULTS")
+    ap.add_argument("--phase", default="test", choices=("test", "val"))
+    ap.add_argument("--visible", type=int, default=None, choices=(0, 1))
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    uni = args.kinematics == "unicycle"
+    names = args.robots or [n for n in ScriptedRobot.NAMES if uni or n != "dwa"]
+    dwa = json.loads(args.dwa) if args.dwa else True
     if not torch.cuda.is_available():
         raise SystemExit("baseline_eval: needs a GPU")
     log = logging.getLogger("baseline_eval")
     log.addHandler(logging.NullHandler())
     log.propagate = False
     lines = []
-    for visible in (False, True):
-        for name in ScriptedRobot.NAMES:
+    for visible in ((False, True) if args.visible is None else (bool(args.visible),)):
+        for name in names:
             c = clone_config(Config())
             c.sim.human_num = args.humans
             if args.human_nums:
                 c.sim.human_nums = list(args.human_nums)
                 c.sim.human_nums_scripted = True
-            c.env.test_size = args.test_size
+            c.env.test_size = c.env.val_size = args.test_size
             c.robot.visible = visible
             c.action_space.kinematics = args.kinematics
-            c.robot.scripted_unicycle = args.kinematics == "unicycle"
+            c.robot.scripted_unicycle = uni
+            c.robot.scripted_dwa = dwa if uni and name == "dwa" else None
             E = args.envs
-            envs = CrowdNavVecEnv(c, E, c.env.seed, "cuda:0", allow_early_resets=True, nenv=E, phase="test")
+            envs = CrowdNavVecEnv(c, E, c.env.seed, "cuda:0", allow_early_resets=True, nenv=E, phase=args.phase)
             t0 = time.time()
             if args.rollout:
                 evaluate_scripted(name, envs, E, "cuda:0", c, log, keep_traces=False, verbose=False)
@@ -79,6 +93,7 @@ def main():
             wall = time.time() - t0
             last = evaluate.last
             nav = last["metrics"]["navigation time"]
+            envs.close()
             rec = {"robot": name, "robot_visible": visible, "kinematics": args.kinematics, "humans": args.human_nums or args.humans,
                    "episodes": args.test_size,
                    "envs": E, "path": "rollout" if args.rollout else "step",
@@ -87,6 +102,10 @@ def main():
                    "collision_rate": round(last["collision_rate"], 3), "timeout_rate": round(last["timeout_rate"], 3),
                    "nav_time_mean_s": round(float(nav[0]), 2), "nav_time_std_s": round(float(nav[1]), 2),
                    "wall_s": round(wall, 2)}
+            if name == "dwa":
+                rec["dwa"] = dwa_params(dwa)
+            if args.phase != "test":
+                rec["phase"] = args.phase
             lines.append(json.dumps(rec))
             print(lines[-1], flush=True)
             for n, v in (last.get("per_count") or {}).items():

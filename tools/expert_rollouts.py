@@ -32,7 +32,8 @@ lidar.live, and the file also holds (cn_rollout_lidar)
 
 --kinematics unicycle drives the unicycle robot (config.robot.scripted_unicycle): `actions` holds the unicycle action
 (dv, dtheta) the tracking law derives from the controller's velocity, each within [-0.1, 0.1], and --noise-sigma is
-ABSOLUTE in those action units (0.1 is the whole range); the step clips the perturbed action.
+ABSOLUTE in those action units (0.1 is the whole range); the step clips the perturbed action. --robot dwa (unicycle
+only) records the dynamic-window controller (config.robot.scripted_dwa), whose actions are grid points of that range.
 
 Usage: python tools/expert_rollouts.py --out demos.npz [--robot orca] [--envs 256] [--steps 512] [--humans 5]
                                        [--seed 0] [--chunk-steps 128] [--noise-sigma S] [--noise-seed K] [--lidar]
@@ -77,6 +78,10 @@ def main():
     c.sim.human_num = args.humans
     c.action_space.kinematics = args.kinematics
     c.robot.scripted_unicycle = args.kinematics == "unicycle"
+    if args.robot == "dwa":
+        if args.kinematics != "unicycle":
+            raise SystemExit("expert_rollouts: --robot dwa needs --kinematics unicycle")
+        c.robot.scripted_dwa = True   # (policy_factory.DWA_DEFAULTS)
     if args.lidar:
         c.robot.policy = "convgru"
         c.lidar.enable = True

@@ -18,7 +18,8 @@ tools/train_varied.py does); the expert row of a density is the expert on that p
 --kinematics unicycle runs all of it on the unicycle robot (config.robot.scripted_unicycle): the expert's velocity
 goes through the tracking law on the device and the labels are the unicycle actions (dv, dtheta), each within
 [-0.1, 0.1]. There the noise is given with --sigma, ABSOLUTE in those action units (0.1 is the whole range; --sigma-frac
-is not read).
+is not read). --expert dwa (unicycle only) clones the dynamic-window controller made for that robot
+(config.robot.scripted_dwa at policy_factory.DWA_DEFAULTS) instead of ORCA or the social force behind the tracking law.
 Needs a GPU.
 
 Usage: python tools/imitation_pretrain.py [--policy srnn|convgru] [--expert orca] [--updates 3000] [--envs 1024] [--steps 32] [--epochs 1]
@@ -94,6 +95,10 @@ def main():
     c.action_space.kinematics = args.kinematics
     uni = args.kinematics == "unicycle"
     c.robot.scripted_unicycle = uni
+    if args.expert == "dwa":
+        if not uni:
+            raise SystemExit("imitation_pretrain: --expert dwa needs --kinematics unicycle")
+        c.robot.scripted_dwa = True   # (policy_factory.DWA_DEFAULTS)
     # (sigma, the fraction it was given as or None): holonomic in fractions of v_pref, unicycle absolute
     sigmas = [(s, None) for s in args.sigma] if uni else [(f * float(c.robot.v_pref), f) for f in args.sigma_frac]
     if args.policy == "convgru":

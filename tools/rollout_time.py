@@ -15,9 +15,12 @@ copy into `executed`); the Python loop stays the clean one.
 
 --kinematics unicycle times the same paths on the unicycle robot (the engine's cn_scripted_unicycle opt-in: the
 tracking law between the controller and the step); --configs a b restricts the run to some configurations.
+Two more configurations exist there and run only when named: (e) 5 humans and (f) 9 humans with the dynamic-window
+controller 'dwa' (cn_scripted_dwa at policy_factory.DWA_DEFAULTS). It always runs as launch pairs, so `fused` equals
+`native_pairs` for it; its rows gain `robot_act_only`, T controller launches alone, for the controller's share.
 
 Usage: python tools/rollout_time.py [--envs 4096] [--steps 256] [--noise-sigma S] [--kinematics holonomic|unicycle]
-           [--configs a b c d] [--out FILE]
+           [--configs a b c d e f] [--out FILE]
 """
 import argparse
 import json
@@ -48,7 +51,7 @@ def main():
     ap.add_argument("--steps", type=int, default=256)
     ap.add_argument("--noise-sigma", type=float, default=None)
     ap.add_argument("--kinematics", default="holonomic", choices=("holonomic", "unicycle"))
-    ap.add_argument("--configs", nargs="+", default=["a", "b", "c", "d"], choices=("a", "b", "c", "d"))
+    ap.add_argument("--configs", nargs="+", default=["a", "b", "c", "d"], choices=("a", "b", "c", "d", "e", "f"))
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -57,9 +60,12 @@ def main():
     lines = []
     noise = None if args.noise_sigma is None else {"sigma": args.noise_sigma, "seed": 1, "step0": 0}
     kw = {} if noise is None else {"noise": noise}
-    for tag, N, name in (("a", 5, "orca"), ("b", 9, "orca"), ("c", 10, "social_force"), ("d", 5, "social_force")):
+    for tag, N, name in (("a", 5, "orca"), ("b", 9, "orca"), ("c", 10, "social_force"), ("d", 5, "social_force"),
+                         ("e", 5, "dwa"), ("f", 9, "dwa")):
         if tag not in args.configs:
             continue
+        if name == "dwa" and args.kinematics != "unicycle":
+            raise SystemExit("rollout_time: configurations e and f (dwa) need --kinematics unicycle")
         c = clone_config(Config())
         c.sim.human_num = N
         c.action_space.kinematics = args.kinematics
@@ -67,6 +73,8 @@ def main():
         eng = CrowdNavEngine(make_cn_config(c, num_envs=E), "cuda:0")
         if args.kinematics == "unicycle":
             eng.scripted_unicycle(True)
+        if name == "dwa":
+            eng.scripted_dwa(True)
         chunk = eng.seq_chunk
         eng.reset()
         eng.step(eng.robot_act(name))   # (the first step after cn_reset is a pair on every path)
@@ -86,7 +94,14 @@ def main():
                 eng.step(eng.robot_act(name))
             launches["python_pairs"] = 2 * T
 
+        def robot_act_only():
+            for _ in range(T):
+                eng.robot_act(name)
+            launches["robot_act_only"] = T
+
         fns = {"fused": fused, "native_pairs": native_pairs, "python_pairs": python_pairs}
+        if name == "dwa":
+            fns["robot_act_only"] = robot_act_only
         rounds = {k: [] for k in fns}
         for _ in range(3):
             for k, fn in fns.items():
