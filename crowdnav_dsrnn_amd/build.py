@@ -25,7 +25,7 @@ PKG = os.path.basename(HERE)
 
 
 def sources(root=REPO):
-    return [os.path.join(root, PKG, "csrc", "cn_engine.hip"), os.path.join(root, PKG, "csrc", "cn_gru.hip")]
+    return [os.path.join(root, PKG, "csrc", n) for n in ("cn_engine.hip", "cn_gru.hip", "cn_attn_mask.hip")]
 
 
 def deps(root=REPO):

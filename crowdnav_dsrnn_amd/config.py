@@ -38,6 +38,11 @@ class Config(object):
     # rollout, ScriptedRobot, evaluate_scripted, BehaviourCloning (the mixed engine's cn_mixed_scripted opt-in).
     # Off, the default, those refuse an env of varying human count with UnsupportedConfig, as before.
     sim.human_nums_scripted = False
+    # visible_masks (this project's opt-in, not a reference option; the key CrowdNav++ uses): the observation also
+    # carries 'visible_masks' (N,), 1.0 for the humans the robot currently sees (the engine's cn_visible_mask: the
+    # step's own FOV decisions), and the DSRNN's spatial attention runs over those slots only. Off, the default,
+    # the observation and the policy are what they were. Not with robot.policy 'convgru' (no human slots there).
+    sim.visible_masks = False
 
     env = BaseConfig()
     env.env_name = "CrowdSimDict-v0"
@@ -327,6 +332,24 @@ def make_mixed_cn_configs(scenario_configs, scenarios, num_envs, env_offset=0, n
                            scenarios=list(scenarios), scenario_mode=abi.SCMODE_ROUND_ROBIN, rng=rng)
             for g, c in enumerate(groups)]
     return cfgs, env_group
+
+
+def visible_masks_on(config):
+    """config.sim.visible_masks as a bool (absent: False). UnsupportedConfig with robot.policy 'convgru', whose
+    observation has no human slots to mask (read from the config alone)."""
+    on = bool(getattr(config.sim, "visible_masks", False))
+    if on and getattr(config.robot, "policy", "srnn") == "convgru":
+        raise UnsupportedConfig("sim.visible_masks with robot.policy='convgru' (the LiDAR observation has no human "
+                                "slots to mask)")
+    return on
+
+
+def no_visible_masks(config, what):
+    """UnsupportedConfig for what an env with config.sim.visible_masks does not serve: the scripted rollouts, whose
+    rows recorded inside multi-step launches carry no mask (read from the config alone)."""
+    if getattr(config.sim, "visible_masks", False):
+        raise UnsupportedConfig("%s: not served on an env with config.sim.visible_masks (the rows a scripted "
+                                "rollout records carry no mask)" % what)
 
 
 MAX_VARIED_HUMANS = 31   # the engine's largest human count per env

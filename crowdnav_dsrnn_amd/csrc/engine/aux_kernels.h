@@ -596,3 +596,48 @@ __global__ void cn_keysnap_kernel(const int32_t *__restrict__ reset_count, const
     const uint4 v = make_uint4((uint32_t)e, (uint32_t)reset_count[e], (uint32_t)cc, (uint32_t)(cc >> 32));
     *(uint4 *)q = v;
 }
+
+// ------------------------------------------------------------------------------------------------
+// cn_visible_mask: which humans the robot sees in the state the engine now holds, one lane per (env, slot of the
+// padded stride NS). It is the decision the step made when it wrote that state's belief -- human_post's in phase 4 of
+// cn_step_kernel once the robot carries its float32 state (CN_FLAG_ROBOT_F32: heading atan2f of the float32 velocity
+// for a holonomic robot, the float32 r_theta for a unicycle), write_reset's float64 path before that -- recomputed
+// from the blob's r_px, r_py, r_vx, r_vy, r_theta, flags, h_px, h_py with the same device functions on the same
+// words, so the booleans are the step's by construction. The belief itself does not determine it: an invisible human
+// that keeps its velocity is extrapolated exactly. A group of a mixed engine (MIX) writes its envs' rows rows[e] of the
+// caller's [E][NS] buffer, the padded slots k >= N as 0. No LDS, no cross-lane reads, no barrier.
+// ------------------------------------------------------------------------------------------------
+template <bool MIX>
+__global__ void __launch_bounds__(64) cn_visible_mask_kernel(cn_state_ptrs S, int E, int N, int NS, int holo, double fov,
+                                                             double cth, float *__restrict__ mask,
+                                                             const int32_t *__restrict__ rows)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t e = i / NS;
+    if (e >= E) return;
+    const int k = (int)(i - e * NS);
+    const int64_t o = MIX ? (int64_t)rows[e] : e;
+    int rv = 0;
+    if (k < N) {
+        const int64_t h = e * N + k;
+        const double rpx = S.r_px[e], rpy = S.r_py[e], px = S.h_px[h], py = S.h_py[h];
+        const bool full = fov >= 2.0 * CN_PI;
+        if (S.flags[e] & CN_FLAG_ROBOT_F32) {
+            const float rvx = (float)S.r_vx[e], rvy = (float)S.r_vy[e];
+            const float rth = holo ? 0.0f : (float)S.r_theta[e];
+            const bool rfin = holo ? (rvx == rvx && rvy == rvy) : isfinite(rth);
+            rv = full ? vis360(rfin, rpx, rpy, px, py) : -1;
+            if (rv < 0) {
+                double fx, fy;
+                if (holo) fov_dir32(atan2f(rvy, rvx), fx, fy);
+                else fov_dir32(rth, fx, fy);
+                rv = in_fov_fast(fx, fy, rpx, rpy, px, py, fov, cth) ? 1 : 0;
+            }
+        } else {
+            const double th0 = holo ? 0.0 : S.r_theta[e];
+            rv = full ? vis360(isfinite(th0), rpx, rpy, px, py) : -1;
+            if (rv < 0) rv = reset_fov_test(th0, rpx, rpy, px, py, fov);
+        }
+    }
+    mask[o * NS + k] = rv ? 1.0f : 0.0f;
+}

@@ -909,6 +909,37 @@ int cn_robot_act(cn_engine *g, void *stream, int policy, float *actions)
     return rc ? rc : rj;
 }
 
+// cn_visible_mask's launch for a plain engine or a group of a mixed engine (its envs' rows of the [E][NS] buffer)
+static int visible_mask_launch(const cn_engine *g, hipStream_t st, float *mask)
+{
+    const cn_config &c = g->c;
+    const int64_t n = (int64_t)g->E * g->NS;
+    (void)hipGetLastError();   // a stale error of an earlier call (any library) is not this launch's
+    const dim3 grid((unsigned)((n + 63) / 64));
+    const int holo = c.kinematics == CN_HOLONOMIC ? 1 : 0;
+    if (g->rows)
+        hipLaunchKernelGGL(cn_visible_mask_kernel<true>, grid, dim3(64), 0, st, g->s, g->E, g->N, g->NS, holo, c.robot_fov,
+                           cos(c.robot_fov / 2), mask, g->rows);
+    else
+        hipLaunchKernelGGL(cn_visible_mask_kernel<false>, grid, dim3(64), 0, st, g->s, g->E, g->N, g->NS, holo,
+                           c.robot_fov, cos(c.robot_fov / 2), mask, (const int32_t *)nullptr);
+    HIPCHK(hipGetLastError());
+    return CN_OK;
+}
+
+// One launch (a mixed engine: one per group, side by side like the groups' step launches); no engine state changes.
+int cn_visible_mask(cn_engine *g, void *stream, float *mask)
+{
+    if (!g || !mask) return set_err(CN_EINVAL, "cn_visible_mask: engine and mask required");
+    const hipStream_t st = (hipStream_t)stream;
+    if (!g->ngroups) return visible_mask_launch(g, st, mask);
+    int rc = mix_fork(g, st);
+    if (rc) return rc;
+    for (int k = 0; k < g->ngroups && !rc; ++k) rc = visible_mask_launch(g->grp[k], mix_stream(g, k, st), mask);
+    const int rj = mix_join(g, st);
+    return rc ? rc : rj;
+}
+
 // Steps [t0, t1) of a rollout call of T steps for g, a plain engine or a group of a mixed engine on its own stream:
 // cn_robot_act + cn_step with every step recorded at row t of the caller's (T, ER, ..) buffers (ER = NS-strided rows
 // of the whole engine; the group's envs at their own rows). Fused (the ROBOT kernels: up to seq_chunk steps per

@@ -116,6 +116,7 @@ class CrowdNavEngine:
         self.robot_actions = torch.zeros((E, 2), dtype=torch.float32, device=dev)   # robot_act()'s own output
         self._step_args = None   # cached output pointers of step() (the buffers above are never reallocated)
         self._seq_fn = None
+        self._visible = None     # visible_mask()'s own output, allocated at its first call
         self.seq_chunk = 32   # steps per multi-step launch (the library's CN_SEQ_CHUNK; set_seq_chunk)
 
     @classmethod
@@ -273,6 +274,23 @@ class CrowdNavEngine:
         with t.cuda.device(self.device):
             _lib.check(_lib.lib().cn_lidar_scan(self._h, self._stream(), int(beams), float(max_range),
                                                 float(robot_radius), out.data_ptr()))
+        return out
+
+    def visible_mask(self, out=None):
+        """Which humans the robot sees in the engine's current state (cn_visible_mask): (E, N) float32 on the device,
+        1.0 where the step (or the reset) that wrote the state found human i of env e visible, 0.0 otherwise and in
+        the padded slots of a mixed engine. Into `out` when given, else into a buffer the engine owns (overwritten by
+        the next call). One launch (a mixed engine: one per group), no host sync."""
+        t = self.torch
+        if out is None:
+            if self._visible is None:
+                self._visible = t.zeros((self.E, self.N), dtype=t.float32, device=self.device)
+            out = self._visible
+        elif (out.dtype != t.float32 or out.device != self.device or not out.is_contiguous()
+                or out.numel() != self.E * self.N):
+            raise ValueError("visible_mask: out must be a contiguous float32 (E, N) tensor on %s" % self.device)
+        with t.cuda.device(self.device):
+            _lib.check(_lib.lib().cn_visible_mask(self._h, self._stream(), out.data_ptr()))
         return out
 
     ROBOT_POLICIES = {"orca": 0, "social_force": 1, "dwa": 2}   # CN_ROBOT_ORCA / CN_ROBOT_SOCIAL_FORCE / CN_ROBOT_DWA

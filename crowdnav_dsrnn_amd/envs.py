@@ -16,6 +16,8 @@ VecPyTorch's return types:
 With config.sim.human_nums (a list of human counts; this project's opt-in) the envs differ in crowd size inside one
 mixed engine: spatial_edges is padded to the largest count and the dict gains 'detected_human_num' (E,1), each env's
 own count; `venv.config` is then a clone of the caller's config whose sim.human_num is that largest count.
+With config.sim.visible_masks (this project's opt-in as well) the dict gains 'visible_masks' (E,N) float32: 1.0 for the
+humans the robot sees in the state the observation describes (the step's own FOV decisions, one cn_visible_mask launch).
 All env work runs on the GPU in one cn_step launch pair; there is no per-env Python and no CPU fallback.
 `step_device(actions)` is the zero-copy variant for on-device rollouts (no host sync).
 
@@ -29,7 +31,8 @@ import time
 import numpy as np
 
 from . import abi, info as info_mod, spaces
-from .config import UnsupportedConfig, clone_config, make_cn_config, make_varied_cn_configs, varied_human_nums
+from .config import (UnsupportedConfig, clone_config, make_cn_config, make_varied_cn_configs, no_visible_masks,
+                     varied_human_nums, visible_masks_on)
 
 _REGISTRY = {}
 
@@ -227,6 +230,8 @@ class CrowdNavVecEnv:
         # before anything touches the GPU); self.config is then a clone whose sim.human_num is the largest count
         # (what a Policy over this env's padded observation is built with), the caller's config stays as it is
         self.human_nums = varied_human_nums(config)
+        # sim.visible_masks: the observation also carries 'visible_masks' (UnsupportedConfig with 'convgru')
+        self.visible_masks = visible_masks_on(config)
         mixed = None
         if self.human_nums is not None:
             mixed = make_varied_cn_configs(config, self.human_nums, self.num_envs, env_offset=env_offset, nenv=nenv,
@@ -275,7 +280,8 @@ class CrowdNavVecEnv:
             self._lidar_obs = torch.zeros((self.num_envs, 1, 7 + B), dtype=torch.float32, device=self.engine.device)
         else:
             self.observation_space = spaces.observation_space(int(self.config.sim.human_num),
-                                                              detected_human_num=mixed is not None)
+                                                              detected_human_num=mixed is not None,
+                                                              visible_masks=self.visible_masks)
         self.action_space = spaces.action_space()
         self.scenario_names = list(abi.SCENARIOS)
         self.side_preference = bool(config.test.side_preference)
@@ -300,6 +306,16 @@ class CrowdNavVecEnv:
             return {k: v.to(self.device, copy=True) for k, v in o.items()}
         return o.to(self.device, copy=True)
 
+    def _srnn_extras(self, o):
+        """The 'srnn' observation with this env's opt-in keys: 'detected_human_num' (sim.human_nums) and
+        'visible_masks' (sim.visible_masks: one cn_visible_mask launch on the state the observation describes, (E, N)
+        float32 in a buffer the engine owns). Without either the dict is returned as it is."""
+        if self.human_nums is not None:
+            o = dict(o, detected_human_num=self._detected)
+        if self.visible_masks:
+            o = dict(o, visible_masks=self.engine.visible_mask())
+        return o
+
     def _convgru_obs(self, reset_mask):
         if self._lidar_live:
             c = self._lidar_cfg
@@ -317,8 +333,8 @@ class CrowdNavVecEnv:
         o = self.engine.reset()
         if self.obs_mode == "convgru":
             o = self._convgru_obs(None)
-        elif self.human_nums is not None:
-            o = dict(o, detected_human_num=self._detected)
+        else:
+            o = self._srnn_extras(o)
         return self._obs_out(o)
 
     def step_async(self, actions):
@@ -358,8 +374,8 @@ class CrowdNavVecEnv:
         out = self.engine.step(actions.reshape(self.num_envs, 2))
         if self.obs_mode == "convgru":
             out = (self._convgru_obs(out[2]),) + tuple(out[1:])
-        elif self.human_nums is not None:
-            out = (dict(out[0], detected_human_num=self._detected),) + tuple(out[1:])
+        elif self.human_nums is not None or self.visible_masks:
+            out = (self._srnn_extras(out[0]),) + tuple(out[1:])
         return out
 
     def robot_act(self, policy):
@@ -387,8 +403,10 @@ class CrowdNavVecEnv:
         (E, 1) tensor; without that opt-in: UnsupportedConfig.
         A unicycle env with robot.scripted_unicycle: 'actions' holds unicycle actions (dv, dtheta), each within
         [-0.1, 0.1], and the noise sigma is in those action units (0.1 is the whole range); without that opt-in the
-        engine refuses. 'dwa' (a unicycle env with robot.scripted_dwa) likewise, always as launch pairs."""
+        engine refuses. 'dwa' (a unicycle env with robot.scripted_dwa) likewise, always as launch pairs.
+        An env with sim.visible_masks: UnsupportedConfig (the recorded rows carry no mask)."""
         _no_varied(self.config, "rollout")
+        no_visible_masks(self.config, "rollout")
         lidar = None
         if self.obs_mode == "convgru":
             if not self._lidar_live:

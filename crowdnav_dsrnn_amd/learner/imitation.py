@@ -47,10 +47,11 @@ EVENT_COLLISION, EVENT_SUCCESS, EVENT_TIMEOUT = 2, 3, 4   # cn_step's event code
 class BehaviourCloning:
     def __init__(self, config, envs, actor_critic, expert="orca", sigma=0.0, seed=0, num_steps=None,
                  num_mini_batch=None, epochs=1, lr=None, value_coef=0.5):
-        from ..config import UnsupportedConfig
+        from ..config import UnsupportedConfig, no_visible_masks
         from ..policy_factory import ScriptedRobot
 
         ScriptedRobot.check(envs, expert)   # unknown controller / unicycle without its opt-in: before anything touches the GPU
+        no_visible_masks(envs.config, "BehaviourCloning")   # (the rollout's rows carry no 'visible_masks')
         mode = getattr(envs, "obs_mode", "srnn")
         self.convgru = mode == "convgru"
         if self.convgru:

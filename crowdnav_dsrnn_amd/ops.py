@@ -8,6 +8,7 @@ linear(...)         — nn.Linear with a split-K weight gradient (library GEMMs;
 attention_pool(...) — EdgeAttention's weighted sum of the spatial edge states (cn_attn_pool_*).
 spatial_attention(...) / spatial_attention_var(...) — EdgeAttention's whole spatial branch in one pass
                       (cn_spatial_attn_*); _var: rows padded to N slots, each with its own human count.
+spatial_attention_mask(...) — the same over the slots a per-slot mask marks visible (cn_spatial_attn_mask_*).
 masked_gru(...)     — the mask-segmented GRU of the three DSRNN RNNs over a (T, B) sequence
                       (cn_gru_fwd_fused: recurrent GEMM on the f32 matrix cores + gates in one launch per
                       step; cn_gru_bwd_step + library GEMMs backward), with its own backward.
@@ -693,3 +694,104 @@ def spatial_attention_var(hs, te, ws, bs, count, attention_size):
     count = count.reshape(R).contiguous()
     row_scale = row_scale_table(N, attention_size, hs.device).index_select(0, count.long())
     return _SpatialAttnVar.apply(hs, te, ws, bs, count, row_scale)
+
+
+_ROW_SCALE_FULL = {}
+
+
+def row_scale_full(R, N, attention_size, device):
+    """(R,) float32, every entry row_scale_table's N / sqrt(attention_size): the temperature vector of a batch whose
+    rows all hold N humans. Kept per (R, N, attention_size, device), so a call costs no kernel (a captured rollout
+    replays none for it)."""
+    key = (int(R), int(N), attention_size, str(device))
+    if key not in _ROW_SCALE_FULL:
+        _ROW_SCALE_FULL[key] = row_scale_table(N, attention_size, device)[int(N)].expand(int(R)).contiguous()
+    return _ROW_SCALE_FULL[key]
+
+
+class _SpatialAttnMask(torch.autograd.Function):
+    """_SpatialAttnVar with a per-slot mask in place of the count (cn_spatial_attn_mask_fwd / _bwd): row r attends
+    to the slots whose mask is set, in slot order, with row_scale[r]; attn and d hs of the masked slots are exact
+    zeros and their hs / d attn are never read; a row without a visible slot gives zeros. The host GEMMs (u, c,
+    d te, dWs, dbs) are _SpatialAttn's."""
+
+    @staticmethod
+    def forward(ctx, hs, te, ws, bs, mask, row_scale):
+        R, N, H = hs.shape
+        hs, te = _c(hs), _c(te)
+        u = torch.mm(te, ws)                 # (R, H)
+        c = torch.mv(te, bs)                 # (R,)
+        out = torch.empty((R, H), dtype=torch.float32, device=hs.device)
+        attn = torch.empty((R, N), dtype=torch.float32, device=hs.device)
+        with torch.cuda.device(hs.device):
+            _lib.check(_lib.lib().cn_spatial_attn_mask_fwd(_stream(hs.device), R, N, H, mask.data_ptr(),
+                                                           row_scale.data_ptr(), hs.data_ptr(), u.data_ptr(),
+                                                           c.data_ptr(), out.data_ptr(), attn.data_ptr()))
+        ctx.save_for_backward(hs, te, ws, bs, u, attn, mask, row_scale)
+        return out, attn.reshape(R, N, 1)
+
+    @staticmethod
+    def backward(ctx, dout, dattn):
+        hs, te, ws, bs, u, attn, mask, row_scale = ctx.saved_tensors
+        R, N, H = hs.shape
+        dev = hs.device
+        dout = _c(dout) if dout is not None else torch.zeros((R, H), dtype=torch.float32, device=dev)
+        da = _c(dattn).reshape(R, N) if dattn is not None else None
+        dhs = torch.empty_like(hs)
+        ld = H + 4                           # [du | dc | pad] rows: dWs and dbs from one split-K GEMM
+        due = torch.empty((R, ld), dtype=torch.float32, device=dev)
+        du, dc = due[:, :H], due[:, H]
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().cn_spatial_attn_mask_bwd(_stream(dev), R, N, H, mask.data_ptr(),
+                                                           row_scale.data_ptr(), hs.data_ptr(), u.data_ptr(),
+                                                           attn.data_ptr(), dout.data_ptr(),
+                                                           da.data_ptr() if da is not None else None, dhs.data_ptr(),
+                                                           due.data_ptr(), ld, due.data_ptr() + 4 * H, ld))
+        dte = torch.addmm(torch.outer(dc, bs), du, ws.t()) if ctx.needs_input_grad[1] else None
+        dws = dbs = None
+        if ctx.needs_input_grad[2] or ctx.needs_input_grad[3]:
+            g = wgrad(te, due)               # (A, H + 4) = te^T [du | dc | pad]; the pad columns are dropped
+            dws, dbs = g[:, :H].contiguous(), g[:, H].contiguous()
+        return dhs, dte, dws, dbs, None, None
+
+
+def spatial_attention_mask_torch(hs, te, ws, bs, visible, row_scale):
+    """The torch composition of spatial_attention_mask, for CPU tensors and the sizes the kernels do not serve:
+    visible (R, N) bool, row_scale (R,). The masked slots leave the softmax through -inf and their states are zeroed
+    (nothing they hold reaches the pooling); a row without a visible slot gives zeros, not NaN."""
+    R, N, H = hs.shape
+    hs = torch.where(visible.unsqueeze(-1), hs, torch.zeros_like(hs))
+    score = (torch.nn.functional.linear(hs, ws, bs) * te.reshape(R, 1, -1)).sum(-1) * row_scale.reshape(R, 1)
+    some = visible.any(-1, keepdim=True)
+    score = score.masked_fill(~visible, float("-inf")).masked_fill(~some, 0.0)   # (an empty row: no NaN softmax)
+    attn = torch.softmax(score, dim=-1)
+    attn = torch.where(visible, attn, torch.zeros_like(attn)).reshape(R, N, 1)
+    weighted = attention_pool(hs, attn) if hs.is_cuda else (hs * attn).sum(1)
+    return weighted, attn
+
+
+def spatial_attention_mask(hs, te, ws, bs, mask, attention_size, count=None):
+    """spatial_attention over the slots the robot sees: hs (R, N, H), mask (R, N) float32 (nonzero and not NaN =
+    visible: the observation's 'visible_masks'). Row r attends to its visible slots only; attn (R, N, 1) is exactly 0
+    in the others, whose hs is never read (cn_spatial_attn_mask_*). The temperature does not depend on visibility --
+    N / sqrt(attention_size), or count[r] / sqrt(attention_size) with count (R,) int32 (rows of varying human count:
+    the mask is then ANDed with slot < count[r]) -- the mask changes which slots compete, not how sharply. CUDA
+    tensors with H in {64, 128, 256} and N <= 64 run the HIP kernels; CPU tensors and other sizes the torch
+    composition (spatial_attention_mask_torch)."""
+    R, N, H = hs.shape
+    if mask.device != hs.device or mask.numel() != R * N:
+        raise ValueError("spatial_attention_mask: mask must be an (R, N) tensor on %s" % hs.device)
+    mask = mask.reshape(R, N).to(torch.float32)
+    if count is not None:
+        if count.dtype != torch.int32 or count.device != hs.device or count.numel() != R:
+            raise ValueError("spatial_attention_mask: count must be an int32 (R,) tensor on %s" % hs.device)
+        count = count.reshape(R)
+        row_scale = row_scale_table(N, attention_size, hs.device).index_select(0, count.long())
+        real = torch.arange(N, device=hs.device, dtype=torch.int32)[None, :] < count[:, None]
+        mask = torch.where(real, mask, torch.zeros_like(mask))
+    else:
+        row_scale = row_scale_full(R, N, attention_size, hs.device)
+    if hs.is_cuda and H in (64, 128, 256) and N <= 64:
+        return _SpatialAttnMask.apply(hs, te, ws, bs, mask.contiguous(), row_scale)
+    visible = (mask != 0) & ~torch.isnan(mask)
+    return spatial_attention_mask_torch(hs, te, ws, bs, visible, row_scale)

@@ -113,13 +113,22 @@ class EdgeAttention(nn.Module):
         self.agent_num = 1
         self.num_attention_head = 1
 
-    def forward(self, h_temporal, h_spatials, count=None):
+    def forward(self, h_temporal, h_spatials, count=None, mask=None):
         """h_temporal (T,B,256), h_spatials (T,B,N,256) -> weighted (T,B,256), attn (T*B,N,1).
         count (T*B,) int32 (optional): the humans of each row, its other slots being padding -- the row attends
         to its first count slots at the temperature count / sqrt(d) (attn 0 elsewhere), as a policy built at
-        that human_num does."""
+        that human_num does.
+        mask (T*B,N) float32 (optional; the observation's 'visible_masks'): the row attends only to the slots the
+        robot sees (attn exactly 0 elsewhere, whatever those slots hold; a row that sees nobody pools zeros). The
+        temperature stays N / sqrt(d) (count / sqrt(d) with count, whose padding is masked as well)."""
         T, B, N, H = h_spatials.shape
         temporal_embed = self.temporal_edge_layer[0](h_temporal)          # (T,B,64)
+        if mask is not None:
+            sl = self.spatial_edge_layer[0]
+            weighted, attn = ops.spatial_attention_mask(h_spatials.reshape(T * B, N, H),
+                                                        temporal_embed.reshape(T * B, -1), sl.weight, sl.bias,
+                                                        mask.reshape(T * B, N), self.attention_size, count)
+            return weighted.reshape(T, B, H), attn
         if count is not None:
             return self._forward_var(temporal_embed, h_spatials, count)
         scale = N / np.sqrt(self.attention_size)                          # temperature = num_edges / sqrt(d)
@@ -161,6 +170,13 @@ class EdgeAttention(nn.Module):
         CrowdNav++ uses) as the attention's (rows,) int32; None without the key."""
         n = inputs.get("detected_human_num") if isinstance(inputs, dict) else None
         return None if n is None else n.reshape(rows).to(torch.int32)
+
+    @staticmethod
+    def masks(inputs, rows):
+        """The per-slot visibility of an observation dict ('visible_masks', (..., N) float32: the key CrowdNav++
+        uses) as the attention's (rows, N) mask; None without the key."""
+        v = inputs.get("visible_masks") if isinstance(inputs, dict) else None
+        return None if v is None else v.reshape(rows, -1)
 
 
 class SRNN(nn.Module):
@@ -234,7 +250,7 @@ class SRNN(nn.Module):
             out_t, h_t = self.humanhumanEdgeRNN_temporal(x_t, h0_t, m)
             out_s, h_s = self.humanhumanEdgeRNN_spatial(x_s, h0_s, m_s)
         out_s = out_s.reshape(T, B, N, H)
-        weighted, _ = self.attn(out_t, out_s, EdgeAttention.counts(inputs, T * B))
+        weighted, _ = self.attn(out_t, out_s, EdgeAttention.counts(inputs, T * B), EdgeAttention.masks(inputs, T * B))
         outputs, h_n = self.humanNodeRNN(ne.reshape(T, B, 64), out_t, weighted, h_node, m)
 
         rnn_hxs["human_node_rnn"] = h_n.reshape(B, 1, -1)
@@ -281,7 +297,8 @@ class SRNN(nn.Module):
                                                                d_edge[:, 0:1, :])
             out_s = self.humanhumanEdgeRNN_spatial.infer_step(se.reshape(B * N, 64), h_edge[:, 1:, :], m,
                                                               d_edge[:, 1:, :])
-        weighted, _ = self.attn(out_t.view(1, B, H), out_s.view(1, B, N, H), EdgeAttention.counts(inputs, B))
+        weighted, _ = self.attn(out_t.view(1, B, H), out_s.view(1, B, N, H), EdgeAttention.counts(inputs, B),
+                                EdgeAttention.masks(inputs, B))
         outputs, _ = self.humanNodeRNN(ne.reshape(1, B, 64), out_t.view(1, B, H), weighted, h_node, m, dest=d_node)
         rnn_hxs["human_node_rnn"] = d_node
         rnn_hxs["human_human_edge_rnn"] = d_edge

@@ -29,7 +29,7 @@ import math
 import numpy as np
 
 from . import _lib
-from .config import UnsupportedConfig
+from .config import UnsupportedConfig, no_visible_masks
 
 ActionXY = collections.namedtuple("ActionXY", ["vx", "vy"])      # crowd_sim/envs/utils/action.py:3
 ActionRot = collections.namedtuple("ActionRot", ["v", "r"])      # crowd_sim/envs/utils/action.py:4
@@ -421,8 +421,10 @@ class ScriptedRobot:
     @classmethod
     def check_rollout(cls, venv, name):
         """check(), and UnsupportedConfig for an env whose observation a rollout cannot record: 'convgru' without
-        lidar.live (before anything touches the GPU)."""
+        lidar.live, or an env with config.sim.visible_masks, whose mask the recorded rows do not carry (before anything
+        touches the GPU)."""
         cls.check(venv, name)
+        no_visible_masks(venv.config, "ScriptedRobot.rollout")
         mode = getattr(venv, "obs_mode", "srnn")
         if mode == "convgru":
             lc = venv.config.lidar

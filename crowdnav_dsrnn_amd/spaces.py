@@ -49,14 +49,18 @@ def _box(shape):
     return Box(-np.inf, np.inf, shape, np.float32)
 
 
-def observation_space(human_num, detected_human_num=False):
+def observation_space(human_num, detected_human_num=False, visible_masks=False):
     """robot_node (1,7), temporal_edges (1,2), spatial_edges (N,2), float32, unbounded (crowd_sim_dict.py:31-56).
     detected_human_num: also 'detected_human_num' (1,), the env's own human count when spatial_edges is padded
-    to N (envs of varying crowd size, config.sim.human_nums; the key CrowdNav++ uses)."""
+    to N (envs of varying crowd size, config.sim.human_nums; the key CrowdNav++ uses).
+    visible_masks: also 'visible_masks' (N,), 1.0 for the humans the robot currently sees (config.sim.visible_masks;
+    CrowdNav++'s key as well)."""
     d = OrderedDict([("robot_node", _box((1, 7))), ("temporal_edges", _box((1, 2))),
                      ("spatial_edges", _box((human_num, 2)))])
     if detected_human_num:
         d["detected_human_num"] = _box((1,))
+    if visible_masks:
+        d["visible_masks"] = _box((human_num,))
     return _GymDict(d) if _GymDict is not None else Dict(d)
 
 

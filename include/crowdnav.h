@@ -55,6 +55,10 @@
  *   cn_spatial_attn_var_fwd / cn_spatial_attn_var_bwd ⟵ (no reference counterpart) the same with a per-row
  *                   human count and temperature: the rows of envs with different crowd sizes, padded to the
  *                   largest, in one launch (observation key 'detected_human_num')
+ *   cn_visible_mask ⟵ (no reference counterpart; CrowdNav++'s 'visible_masks') which humans the robot sees in the
+ *                   current state: the step's own detect_visible decisions (crowd_sim.py:820-847), one launch
+ *   cn_spatial_attn_mask_fwd / cn_spatial_attn_mask_bwd ⟵ (no reference counterpart) the spatial attention over the
+ *                   visible slots of each row only (observation key 'visible_masks')
  *
  * Conventions
  *   - All array arguments are DEVICE pointers (torch tensors' data_ptr()), row-major, caller-owned.
@@ -583,6 +587,19 @@ int cn_robot_act(cn_engine *eng, void *stream, int policy, float *actions);
  * with holonomic envs (the controller emits (dv, dtheta)). */
 int cn_scripted_dwa(cn_engine *eng, const cn_dwa_params *p);
 
+/* Which humans the robot sees in the state the engine now holds (after cn_reset / cn_step / cn_step_seq /
+ * cn_set_state): mask [E][NS] float32, NS = the padded human stride of the observation (N; a mixed engine: its
+ * largest count), 1.0 where the robot sees human i of env e, 0.0 otherwise and in the padded slots. It is
+ * detect_visible(robot, human, robot1=True) (crowd_sim.py:820-847) as the step itself evaluated it when it wrote
+ * that state's belief (b_*): recomputed from r_px, r_py, r_vx, r_vy, r_theta, flags, h_px, h_py and robot_fov with
+ * the step's own device functions -- the float32 heading once the robot carries its float32 state, the float64 reset
+ * path before. mask == 1 implies b_* == the human's true state bit for bit; the converse does not hold (an invisible
+ * human that keeps its velocity is extrapolated exactly), which is why the mask is not derivable from the
+ * observation. Reads the state only. One launch (a mixed engine: one per group, group 0 on `stream`, the others
+ * forked from and joined to it, no opt-in needed). Stream-ordered; no allocation, no synchronisation, no memset;
+ * capturable (graph mode: one more kernel node). CN_EINVAL: eng or mask NULL (before any launch). */
+int cn_visible_mask(cn_engine *eng, void *stream, float *mask);
+
 /* Closed-loop scripted rollout: T steps of the scripted robot driving the engine, every step recorded. For
  * t = 0..T-1 the call does cn_robot_act(eng, stream, policy, actions_t) and then cn_step(eng, stream, actions_t,
  * ...row t of every output...); every recorded row and the state blob afterwards equal that pair sequence bit for
@@ -750,6 +767,20 @@ int cn_spatial_attn_var_fwd(void *stream, int64_t R, int N, int H, const int32_t
 int cn_spatial_attn_var_bwd(void *stream, int64_t R, int N, int H, const int32_t *count, const float *row_scale,
                             const float *hs, const float *u, const float *attn, const float *dout, const float *dattn,
                             float *dhs, float *du, int64_t ldu, float *dc, int64_t ldc);
+
+/* cn_spatial_attn_var_fwd / _bwd with a per-slot mask in place of the count (attention over the humans the robot
+ * sees: cn_visible_mask's rows): mask [R][N] float32, nonzero and not NaN = visible. Row r attends to its visible
+ * slots only, visited in ascending slot order, with the temperature row_scale[r], and is computed as the _var pair
+ * computes a row that holds those slots compacted to the front (same operations, same order: a full mask is
+ * cn_spatial_attn_fwd's row, a prefix mask the _var row of that count, bit for bit). attn[r][n] and dhs[r][n][:] of
+ * masked slots are written as exact zeros; hs[r][n] and dattn[r][n] are never read there. A row without a visible
+ * slot gives out = 0, attn = 0, du = 0, dc = 0, dhs = 0. Shapes, alignment and strides as above; mask and row_scale
+ * non-null. No allocation, sync or memset. */
+int cn_spatial_attn_mask_fwd(void *stream, int64_t R, int N, int H, const float *mask, const float *row_scale,
+                             const float *hs, const float *u, const float *c, float *out, float *attn);
+int cn_spatial_attn_mask_bwd(void *stream, int64_t R, int N, int H, const float *mask, const float *row_scale,
+                             const float *hs, const float *u, const float *attn, const float *dout, const float *dattn,
+                             float *dhs, float *du, int64_t ldu, float *dc, int64_t ldc);
 
 /* Weight gradient of a Linear layer over K rows with a tiny side (ops.linear / the fused input layers'
  * backward, replacing torch's dy^T x in the reference's autograd of srnn_model.py:160-161,210-211,466 and

@@ -1,0 +1,186 @@
+"""config.sim.visible_masks, the parts that need no GPU: the opt-in is off by default and leaves the observation space
+as it was, what such an env refuses is refused before anything touches the GPU, the mask cases of the kernel tests
+cover the kernels' paths, and the torch branch of ops.spatial_attention_mask (CPU tensors, sizes the kernels do not
+serve) against the float64 composition."""
+import types
+
+import numpy as np
+import pytest
+import torch
+
+from crowdnav_dsrnn_amd import spaces
+from crowdnav_dsrnn_amd.config import Config, UnsupportedConfig, clone_config, visible_masks_on
+
+A = 64
+SHAPES = [(1, 1, 256), (37, 10, 256), (300, 25, 128), (5, 3, 64), (9, 64, 64), (4099, 20, 256)]   # test_varied_humans'
+PINNED = ("full", "first", "last", "empty", "prefix10", "prefix11", "prefix16", "prefix17", "alternate")
+
+
+def _cfg(**sim):
+    c = clone_config(Config())
+    for k, v in sim.items():
+        setattr(c.sim, k, v)
+    return c
+
+
+def masks_for(R, N):
+    """(R, N) bool: seeded Bernoulli(0.5); the first rows are pinned to all ones, only slot 0, only slot N - 1, empty,
+    the prefixes of 10 / 11 / 16 / 17 slots (both sides of the register-held NR = 10 and 16) and every other slot
+    (the k-th visible slot is slot 2k: visible index and slot differ), as far as R and N allow."""
+    m = torch.rand(R, N, generator=torch.Generator().manual_seed(R * 13 + N)) < 0.5
+    n = torch.arange(N)
+    rows = {"full": n >= 0, "first": n == 0, "last": n == N - 1, "empty": n < 0, "prefix10": n < 10, "prefix11": n < 11,
+            "prefix16": n < 16, "prefix17": n < 17, "alternate": n % 2 == 0}
+    for k, name in enumerate(PINNED):
+        if k < R:
+            m[k] = rows[name]
+    return m
+
+
+def test_masks_cover_the_kernel_paths():
+    """Over SHAPES the masks hold a full row, single slots at both ends, an empty row, prefixes on both sides of
+    NR = 10 and of 16 in the N > 10 kernels, rows whose k-th visible slot is not slot k with fewer and with more
+    visible slots than the NR = 16 registers hold, random rows with more than NR visible slots, and a ragged last
+    workgroup."""
+    seen = set()
+    for R, N, Hh in SHAPES:
+        m = masks_for(R, N)
+        cnt = m.sum(1)
+        prefix = (m == (torch.arange(N)[None, :] < cnt[:, None])).all(1)
+        seen |= {("full", bool((cnt == N).any())), ("empty", bool((cnt == 0).any())),
+                 ("first", bool(((cnt == 1) & m[:, 0]).any())), ("last", bool(((cnt == 1) & m[:, N - 1]).any()))}
+        if N > 10:
+            for v in (10, 11, 16, 17):
+                seen.add(("prefix%d" % v, bool((prefix & (cnt == min(v, N))).any())))
+            seen |= {("scattered_le16", bool((~prefix & (cnt <= 16) & (cnt > 0)).any())),
+                     ("scattered_gt16", bool((~prefix & (cnt > 16)).any()))}
+        else:
+            seen.add(("scattered_nr10", bool((~prefix & (cnt > 1)).any())))
+        seen.add(("ragged", R % (256 // (Hh // 4)) != 0))
+    assert {k for k, v in seen if v} == {"full", "empty", "first", "last", "prefix10", "prefix11", "prefix16",
+                                         "prefix17", "scattered_le16", "scattered_gt16", "scattered_nr10", "ragged"}
+
+
+def attn_inputs(R, N, Hh):
+    g = torch.Generator().manual_seed(R * 11 + N)
+    hs = torch.randn(R, N, Hh, generator=g)
+    te = torch.relu(torch.randn(R, A, generator=g)) * 0.3
+    ws = torch.randn(A, Hh, generator=g) / 16
+    bs = torch.randn(A, generator=g) * 0.1
+    dout = torch.randn(R, Hh, generator=g)
+    datt = torch.randn(R, N, 1, generator=g)
+    return hs, te, ws, bs, dout, datt
+
+
+def spatial_attention_mask_ref(hs, te, ws, bs, vis, scale):
+    """The reference composition (spatial_embed, product, sum, temperature, -inf-masked softmax, pooling) in the
+    operands' dtype; a row without a visible slot gives zeros. scale: (R,) or a number."""
+    R, N, _ = hs.shape
+    se = hs @ ws.t() + bs
+    score = (se * te.unsqueeze(1)).sum(-1) * torch.as_tensor(scale, dtype=hs.dtype).reshape(-1, 1)
+    some = vis.any(1, keepdim=True)
+    attn = torch.softmax(score.masked_fill(~vis, float("-inf")).masked_fill(~some, 0.0), -1)
+    attn = (attn * vis.to(hs.dtype)).unsqueeze(-1)
+    return torch.bmm(hs.transpose(1, 2), attn).squeeze(-1), attn
+
+
+def check_vs_ref(got, want, R, label=""):
+    """tests/test_varied_humans.py::_check_vs_ref: the project's pinned bound for the attention kernels."""
+    for n, a, b in zip(("out", "attn", "d_hs", "d_te", "d_ws", "d_bs"), got, want):
+        ref = want[4] if n == "d_bs" else b
+        tol = 2e-5 * max(1.0, float(ref.abs().max())) * (max(1.0, R / 256) if n in ("d_ws", "d_bs") else 1.0)
+        print("%s%s max|err| %.3e tol %.3e" % (label, n, float((a - b).abs().max()), tol))
+        assert torch.isfinite(a).all(), n
+        np.testing.assert_allclose(a.numpy(), b.numpy(), atol=tol, rtol=0, err_msg=n)
+
+
+def run_fp64(hs, te, ws, bs, dout, datt, vis, scale):
+    """out, attn and the gradients of hs, te, ws, bs of the float64 composition, with d attn arriving too (masked
+    slots of hs and d attn taken as 0)."""
+    ys = [t.double().requires_grad_(True) for t in (hs.masked_fill(~vis.unsqueeze(-1), 0.0), te, ws, bs)]
+    o64, a64 = spatial_attention_mask_ref(*ys, vis, scale)
+    torch.autograd.backward([o64, a64], [dout.double(), datt.double().masked_fill(~vis.unsqueeze(-1), 0.0)])
+    return [x.detach() for x in [o64, a64] + [t.grad for t in ys]]
+
+
+def test_opt_in_is_off_by_default_and_space_is_unchanged_without_it():
+    c = _cfg()
+    assert c.sim.visible_masks is False and visible_masks_on(c) is False
+    del c.sim.visible_masks                                   # a config written before the option existed
+    assert visible_masks_on(c) is False
+    plain = spaces.observation_space(5).spaces
+    assert list(plain) == ["robot_node", "temporal_edges", "spatial_edges"]
+    assert list(spaces.observation_space(12, detected_human_num=True).spaces) == [
+        "robot_node", "temporal_edges", "spatial_edges", "detected_human_num"]
+    sp = spaces.observation_space(12, detected_human_num=True, visible_masks=True).spaces
+    assert list(sp) == ["robot_node", "temporal_edges", "spatial_edges", "detected_human_num", "visible_masks"]
+    assert tuple(sp["visible_masks"].shape) == (12,) and sp["visible_masks"].dtype == np.float32
+    sp = spaces.observation_space(5, visible_masks=True).spaces
+    assert list(sp) == ["robot_node", "temporal_edges", "spatial_edges", "visible_masks"]
+
+
+def test_convgru_with_visible_masks_is_unsupported_before_the_gpu():
+    from crowdnav_dsrnn_amd.envs import CrowdNavVecEnv, make_vec_envs
+
+    c = _cfg(visible_masks=True)
+    c.robot.policy = "convgru"
+    c.lidar.enable = True
+    with pytest.raises(UnsupportedConfig, match="visible_masks"):
+        visible_masks_on(c)
+    with pytest.raises(UnsupportedConfig, match="visible_masks"):
+        CrowdNavVecEnv(c, 4, 0, "cpu")
+    with pytest.raises(UnsupportedConfig, match="visible_masks"):
+        make_vec_envs("CrowdSimDict-v0", 0, 4, 0.99, None, "cpu", False, config=c)
+
+
+def test_scripted_rollouts_and_behaviour_cloning_are_unsupported_before_the_gpu():
+    from crowdnav_dsrnn_amd.envs import CrowdNavVecEnv
+    from crowdnav_dsrnn_amd.evaluation import evaluate_scripted
+    from crowdnav_dsrnn_amd.learner.imitation import BehaviourCloning
+    from crowdnav_dsrnn_amd.policy_factory import ScriptedRobot
+
+    c = _cfg(visible_masks=True)
+    venv = types.SimpleNamespace(config=c, obs_mode="srnn")   # (no engine: the checks read the config alone)
+    with pytest.raises(UnsupportedConfig, match="visible_masks"):
+        ScriptedRobot.check_rollout(venv, "orca")
+    robot = ScriptedRobot(venv, "social_force")               # (act() on the current state needs no recorded row)
+    with pytest.raises(UnsupportedConfig, match="visible_masks"):
+        robot.rollout(4)
+    with pytest.raises(UnsupportedConfig, match="visible_masks"):
+        BehaviourCloning(c, venv, types.SimpleNamespace(srnn=True), expert="orca")
+    with pytest.raises(UnsupportedConfig, match="visible_masks"):
+        evaluate_scripted("orca", venv, 4, "cpu", c, None)
+    bare = CrowdNavVecEnv.__new__(CrowdNavVecEnv)             # the env's own rollout: same answer
+    bare.config = c
+    with pytest.raises(UnsupportedConfig, match="visible_masks"):
+        bare.rollout("orca", 4)
+    ScriptedRobot.check_rollout(types.SimpleNamespace(config=_cfg(), obs_mode="srnn"), "orca")   # off: as ever
+
+
+@pytest.mark.parametrize("R,N,Hh,with_count", [(37, 10, 256, False), (9, 64, 64, True), (12, 7, 96, False),
+                                               (6, 70, 32, True)])
+def test_torch_branch_matches_fp64_composition(R, N, Hh, with_count):
+    """ops.spatial_attention_mask on CPU tensors (sizes the kernels serve and sizes they do not): out, attn and the
+    four gradients against the float64 composition at the attention kernels' bound, NaN in the masked slots of hs
+    and of the incoming d attn, attn and d hs exactly 0 there and in the empty rows."""
+    from crowdnav_dsrnn_amd import ops
+
+    hs, te, ws, bs, dout, datt = attn_inputs(R, N, Hh)
+    vis = masks_for(R, N)
+    count = None
+    scale = N / np.sqrt(A)
+    if with_count:
+        count = torch.randint(1, N + 1, (R,), generator=torch.Generator().manual_seed(R)).to(torch.int32)
+        scale = count.double() / np.sqrt(A)
+    eff = vis & (torch.arange(N)[None, :] < count[:, None]) if with_count else vis
+    assert bool((eff.sum(1) == 0).any()) and bool((~eff).any())
+    nan = ~eff.unsqueeze(-1)
+    xs = [t.requires_grad_(True) for t in (hs.masked_fill(nan, float("nan")), te.clone(), ws.clone(), bs.clone())]
+    out, att = ops.spatial_attention_mask(*xs, vis.float(), A, count)
+    torch.autograd.backward([out, att], [dout, datt.masked_fill(nan, float("nan"))])
+    got = [x.detach().double() for x in [out, att] + [t.grad for t in xs]]
+    want = run_fp64(hs, te, ws, bs, dout, datt, eff, scale)
+    check_vs_ref(got, want, R)
+    assert (got[1].squeeze(-1)[~eff] == 0.0).all() and (got[2][~eff] == 0.0).all()
+    empty = eff.sum(1) == 0
+    assert (got[0][empty] == 0.0).all() and (got[3][empty] == 0.0).all()
