@@ -43,6 +43,10 @@ class Config(object):
     # step's own FOV decisions), and the DSRNN's spatial attention runs over those slots only. Off, the default,
     # the observation and the policy are what they were. Not with robot.policy 'convgru' (no human slots there).
     sim.visible_masks = False
+    # visible_masks_scripted (with visible_masks): the env also serves the scripted rollouts -- CrowdNavVecEnv.rollout,
+    # ScriptedRobot.rollout, evaluate_scripted, BehaviourCloning -- whose rows then carry 'visible_masks' too (the
+    # engine's cn_rollout_masked). Off, the default, those refuse a visible_masks env with UnsupportedConfig, as before.
+    sim.visible_masks_scripted = False
 
     env = BaseConfig()
     env.env_name = "CrowdSimDict-v0"
@@ -344,12 +348,26 @@ def visible_masks_on(config):
     return on
 
 
+def visible_masks_scripted(config):
+    """config.sim.visible_masks_scripted as a bool (absent: False): the scripted rollouts serve the visible_masks env
+    and record the mask. UnsupportedConfig when it is set without sim.visible_masks (read from the config alone)."""
+    on = bool(getattr(config.sim, "visible_masks_scripted", False))
+    if on and not getattr(config.sim, "visible_masks", False):
+        raise UnsupportedConfig("sim.visible_masks_scripted without sim.visible_masks (the opt-in lets the scripted "
+                                "rollouts record the mask of a visible_masks env)")
+    return on
+
+
 def no_visible_masks(config, what):
-    """UnsupportedConfig for what an env with config.sim.visible_masks does not serve: the scripted rollouts, whose
-    rows recorded inside multi-step launches carry no mask (read from the config alone)."""
+    """UnsupportedConfig for what an env with config.sim.visible_masks does not serve without the
+    sim.visible_masks_scripted opt-in: the scripted rollouts, whose rows then carry no mask (read from the config
+    alone). Returns whether the rollout has to record the mask (both keys set)."""
+    if visible_masks_scripted(config):
+        return visible_masks_on(config)
     if getattr(config.sim, "visible_masks", False):
         raise UnsupportedConfig("%s: not served on an env with config.sim.visible_masks (the rows a scripted "
-                                "rollout records carry no mask)" % what)
+                                "rollout records carry no mask) unless config.sim.visible_masks_scripted is set" % what)
+    return False
 
 
 MAX_VARIED_HUMANS = 31   # the engine's largest human count per env

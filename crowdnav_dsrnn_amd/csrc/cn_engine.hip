@@ -2685,6 +2685,52 @@ __device__ __forceinline__ void state_rows_copy(const cn_state_ptrs &S, const Ro
     }
 }
 
+// cn_visible_mask's decision for slot k of env e (k >= N: a padded slot, 0): the step's own FOV test on the blob's
+// r_px, r_py, r_vx, r_vy, r_theta, flags, h_px, h_py (aux_kernels.h: cn_visible_mask_kernel). Shared by that kernel
+// and cn_step_kernel's mask-recording rollout variant: one arithmetic, so the rows are the same by construction.
+// Reads no other lane.
+__device__ __forceinline__ float visible_mask_slot(const cn_state_ptrs &S, int64_t e, int k, int N, int holo, double fov,
+                                                   double cth)
+{
+    int rv = 0;
+    if (k < N) {
+        const int64_t h = e * N + k;
+        const double rpx = S.r_px[e], rpy = S.r_py[e], px = S.h_px[h], py = S.h_py[h];
+        const bool full = fov >= 2.0 * CN_PI;
+        if (S.flags[e] & CN_FLAG_ROBOT_F32) {
+            const float rvx = (float)S.r_vx[e], rvy = (float)S.r_vy[e];
+            const float rth = holo ? 0.0f : (float)S.r_theta[e];
+            const bool rfin = holo ? (rvx == rvx && rvy == rvy) : isfinite(rth);
+            rv = full ? vis360(rfin, rpx, rpy, px, py) : -1;
+            if (rv < 0) {
+                double fx, fy;
+                if (holo) fov_dir32(atan2f(rvy, rvx), fx, fy);
+                else fov_dir32(rth, fx, fy);
+                rv = in_fov_fast(fx, fy, rpx, rpy, px, py, fov, cth) ? 1 : 0;
+            }
+        } else {
+            const double th0 = holo ? 0.0 : S.r_theta[e];
+            rv = full ? vis360(isfinite(th0), rpx, rpy, px, py) : -1;
+            if (rv < 0) rv = reset_fov_test(th0, rpx, rpy, px, py, fov);
+        }
+    }
+    return rv ? 1.0f : 0.0f;
+}
+
+// The mask rows of envs [e0, e0 + ne) of a step workgroup into `row` (one step's [ER][NS] rows of the caller's
+// buffer; the envs at orow(ov, e)), one (env, slot) per pass of thread k of nthr.
+__device__ __forceinline__ void visible_mask_rows(const cn_state_ptrs &S, const OutView &ov, int e0, int ne, int N,
+                                                  int holo, double fov, double cth, float *__restrict__ row, int k,
+                                                  int nthr)
+{
+    const int NS = ov.NS, n = ne * NS;
+    for (int q = k; q < n; q += nthr) {
+        const int el = q / NS, s = q - el * NS;
+        const int64_t e = e0 + el;
+        row[orow(ov, e) * NS + s] = visible_mask_slot(S, e, s, N, holo, fov, cth);
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // kernel A
 // ------------------------------------------------------------------------------------------------
@@ -2714,8 +2760,14 @@ struct StepArgs {
         int64_t rollout;
     };
     uint32_t *plist_base;  // [3][E + 64][4] spawn lists: {env, reset_count, case_counter lo, hi} after the reset
-    uint32_t *rlist_base;   // [3][2E + 64][4] parked-spawn lists
-    uint32_t *plist_w;      // envs reset by this launch (their next spawn is drawn by the next launch); a multi-step
+    union {
+        uint32_t *rlist_base;   // [3][2E + 64][4] parked-spawn lists (read by the DEVSEQ kernels only)
+        // MASK (cn_rollout_masked's launches, never graph mode's): row 0 of the launch in the caller's mask buffer,
+        // [nsteps][ER][NS] with CN_ROLLOUT_OBS_EVERY_STEP, one row [ER][NS] otherwise. In the kernarg segment and
+        // not in a device block as RolloutRows is: the call then issues exactly cn_rollout's launches.
+        float *mask;
+    };
+    uint32_t *plist_w;     // envs reset by this launch (their next spawn is drawn by the next launch); a multi-step
                             // launch keeps one entry per env and slot parity, the first E of them
     uint32_t *pcount_w;
     uint32_t *pcount_zero;  // the counter the NEXT launch appends to (triple-buffered), zeroed here
@@ -2790,7 +2842,14 @@ __device__ inline float bbox_dist(float x, float y, float mnx, float mxx, float 
 // step s - 1 left in global memory to its row; the launch's last step copies its own after its closing barrier.
 // (The state before a launch's step 0 is the previous launch's last row.) A flag of its own, so that cn_rollout's
 // kernels stay what they were.
-template <bool KD, bool PHX, bool MIX, bool DEVSEQ = false, bool SEQ = false, bool ROBOT = false, bool REC = false>
+// MASK (ROBOT only, never with REC): a launch of cn_rollout_masked, which also records which humans the robot sees in
+// the state every step leaves (cn_visible_mask's row, visible_mask_slot) at row `step` of g.mask, in REC's places:
+// waves 1-3 write row s - 1 while wave 0 runs the controller of step s >= 1, one lane per (env of the workgroup,
+// slot), and the launch's last step writes its own after its closing barrier. Without CN_ROLLOUT_OBS_EVERY_STEP only
+// that last row is written, to the single row. The mask lanes read no other lane and sit behind launch-uniform
+// conditions. A flag of its own again, so that cn_rollout's kernels stay what they were.
+template <bool KD, bool PHX, bool MIX, bool DEVSEQ = false, bool SEQ = false, bool ROBOT = false, bool REC = false,
+          bool MASK = false>
 __global__ void __launch_bounds__(CN_BLK, 3) cn_step_kernel(StepArgs g, cn_config c)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -3024,6 +3083,10 @@ __global__ void __launch_bounds__(CN_BLK, 3) cn_step_kernel(StepArgs g, cn_confi
                 const RolloutRows rr = *(const RolloutRows *)(g.pend.stats + (CN_ROWS_W - 8));
                 state_rows_copy(S, rr, g.E, N, (actions - rr.actions) / 2 - g.E, e0, nenv_here, tid - 64, CN_BLK - 64);
             }
+        } else if constexpr (MASK) {
+            if (step > 0 && obs_rows)   // the mask of the state step - 1 left, into its row
+                visible_mask_rows(S, ov, e0, nenv_here, N, holo ? 1 : 0, c.robot_fov, g.cth_r,
+                                  g.mask + (orw_e - erow) * ov.NS, tid - 64, CN_BLK - 64);
         }
         __syncthreads();
     }
@@ -3992,6 +4055,11 @@ __global__ void __launch_bounds__(CN_BLK, 3) cn_step_kernel(StepArgs g, cn_confi
             const RolloutRows rr = *(const RolloutRows *)(g.pend.stats + (CN_ROWS_W - 8));
             state_rows_copy(S, rr, g.E, N, (actions - rr.actions) / 2, e0, nenv_here, tid, CN_BLK);
         }
+    }
+    if constexpr (MASK) {
+        if (step == g.nsteps - 1)
+            visible_mask_rows(S, ov, e0, nenv_here, N, holo ? 1 : 0, c.robot_fov, g.cth_r, g.mask + orw_o * ov.NS, tid,
+                              CN_BLK);
     }
     } while (SEQ && ++step < g.nsteps);
 #ifdef CN_STAMPS

@@ -617,27 +617,5 @@ __global__ void __launch_bounds__(64) cn_visible_mask_kernel(cn_state_ptrs S, in
     if (e >= E) return;
     const int k = (int)(i - e * NS);
     const int64_t o = MIX ? (int64_t)rows[e] : e;
-    int rv = 0;
-    if (k < N) {
-        const int64_t h = e * N + k;
-        const double rpx = S.r_px[e], rpy = S.r_py[e], px = S.h_px[h], py = S.h_py[h];
-        const bool full = fov >= 2.0 * CN_PI;
-        if (S.flags[e] & CN_FLAG_ROBOT_F32) {
-            const float rvx = (float)S.r_vx[e], rvy = (float)S.r_vy[e];
-            const float rth = holo ? 0.0f : (float)S.r_theta[e];
-            const bool rfin = holo ? (rvx == rvx && rvy == rvy) : isfinite(rth);
-            rv = full ? vis360(rfin, rpx, rpy, px, py) : -1;
-            if (rv < 0) {
-                double fx, fy;
-                if (holo) fov_dir32(atan2f(rvy, rvx), fx, fy);
-                else fov_dir32(rth, fx, fy);
-                rv = in_fov_fast(fx, fy, rpx, rpy, px, py, fov, cth) ? 1 : 0;
-            }
-        } else {
-            const double th0 = holo ? 0.0 : S.r_theta[e];
-            rv = full ? vis360(isfinite(th0), rpx, rpy, px, py) : -1;
-            if (rv < 0) rv = reset_fov_test(th0, rpx, rpy, px, py, fov);
-        }
-    }
-    mask[o * NS + k] = rv ? 1.0f : 0.0f;
+    mask[o * NS + k] = visible_mask_slot(S, e, k, N, holo, fov, cth);   // (cn_engine.hip: the rollout kernels' too)
 }

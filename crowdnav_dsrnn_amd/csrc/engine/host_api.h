@@ -445,9 +445,12 @@ int cn_reset(cn_engine *g, void *stream, float *robot_node, float *temporal, flo
 // rollout >= 0 (cn_rollout's fused launches, nsteps >= 1, same engines): StepArgs::rollout of the ROBOT kernels,
 // which compute the actions themselves and record every step at row t of the outputs (`actions` is written).
 // rec (cn_rollout_lidar's fused launches): the ROBOT kernels that record the state rows as well (RolloutRows block).
+// mask (cn_rollout_masked's fused launches, never with rec): the ROBOT kernels that record the visible_masks rows as
+// well, from the launch's row 0 (StepArgs::mask).
 static int step_launch(cn_engine *g, void *stream, const float *actions, int nsteps, int64_t action_stride,
                        float *robot_node, float *temporal, float *spatial, float *reward, uint8_t *done, int8_t *event,
-                       float *info, double *ep_return, int32_t *ep_len, int64_t rollout = -1, bool rec = false)
+                       float *info, double *ep_return, int32_t *ep_len, int64_t rollout = -1, bool rec = false,
+                       float *mask = nullptr)
 {
     if (!g || !actions || !robot_node || !temporal || !spatial) return set_err(CN_EINVAL, "null argument");
     hipStream_t st = (hipStream_t)stream;
@@ -505,9 +508,10 @@ static int step_launch(cn_engine *g, void *stream, const float *actions, int nst
     const bool phx = g->c.rng_mode == CN_RNG_PHILOX;
     (void)hipGetLastError();   // a stale error of an earlier call (any library) is not this launch's
     const bool multi = nsteps > 1 || rollout >= 0;
-    if (multi && (g->devseq || g->plan.kd || a.pend.all || (rec && g->rows)))
+    if (multi && (g->devseq || g->plan.kd || a.pend.all || (rec && (g->rows || mask))))
         return set_err(CN_EINVAL, "multi-step launch: quad-path engine outside graph mode required");
-    const StepMode mode = rollout >= 0 ? (rec ? STEP_ROBOT_REC : STEP_ROBOT)
+    if (mask && rollout >= 0) a.mask = mask;   // (shares rlist_base's slot: the ROBOT kernels are never graph mode's)
+    const StepMode mode = rollout >= 0 ? (rec ? STEP_ROBOT_REC : mask ? STEP_ROBOT_MASK : STEP_ROBOT)
                           : nsteps > 1 ? STEP_SEQ : g->devseq ? STEP_DEVSEQ : STEP_SINGLE;
     const StepKernelFn kern = step_kernel_for(g->plan.kd, phx, g->rows != nullptr, mode);
     // (a guard only: the check above and cn_set_graph_mode's refusal of mixed engines exclude every combination
@@ -952,10 +956,14 @@ int cn_visible_mask(cn_engine *g, void *stream, float *mask)
 // the pair's two launches and the step reads the engine's scratch. Both key the noise by the global env index.
 // ld (cn_rollout_lidar, plain engines; null: none): the state every step leaves goes to row t of ld's state rows -- the
 // fused launches are the recording ROBOT kernels, told where through the engine's RolloutRows block (one small launch
-// per call before the first of them); elsewhere cn_state_rows_kernel follows the step. *nl counts the launches.
+// per call before the first of them); elsewhere cn_state_rows_kernel follows the step.
+// mask (cn_rollout_masked; null: none; never with ld): the call's row 0 of the (T, ER, NS) visible_masks buffer (one
+// row (ER, NS) without CN_ROLLOUT_OBS_EVERY_STEP). The fused launches are the mask-recording ROBOT kernels, handed
+// their own row 0 in the kernel arguments (no launch added); elsewhere cn_visible_mask's launch follows the step, into
+// the observation's row. *nl counts the launches.
 static int rollout_steps(cn_engine *g, hipStream_t st, bool fuse, int policy, int t0, int t1, int T,
                          const cn_rollout_out *out, const cn_rollout_noise *nz, const struct cn_rollout_lidar *ld,
-                         int *nl)
+                         float *mask, int *nl)
 {
     void *const stream = (void *)st;
     const int64_t E = g->ER, N = g->NS;
@@ -973,6 +981,7 @@ static int rollout_steps(cn_engine *g, hipStream_t st, bool fuse, int policy, in
         float *const act = out->actions + t * E * 2;
         float *const rn = out->robot_node + ro * E * 7, *const te = out->temporal_edges + ro * E * 2;
         float *const se = out->spatial_edges + ro * E * N * 2;
+        float *const mk = mask ? mask + ro * E * N : nullptr;
         float *const rw = out->reward ? out->reward + t * E : nullptr;
         uint8_t *const dn = out->done ? out->done + t * E : nullptr;
         int8_t *const ev = out->event ? out->event + t * E : nullptr;
@@ -1006,7 +1015,7 @@ static int rollout_steps(cn_engine *g, hipStream_t st, bool fuse, int policy, in
                 rows_set = true;
                 *nl += 1;
             }
-            rc = step_launch(g, stream, act, n, 2 * E, rn, te, se, rw, dn, ev, inf, epr, epl, word, ld != nullptr);
+            rc = step_launch(g, stream, act, n, 2 * E, rn, te, se, rw, dn, ev, inf, epr, epl, word, ld != nullptr, mk);
             *nl += 1;
         } else {
             rc = robot_act_launch(g, st, policy, act);
@@ -1030,6 +1039,10 @@ static int rollout_steps(cn_engine *g, hipStream_t st, bool fuse, int policy, in
                 HIPCHK(hipGetLastError());
                 *nl += 1;
             }
+            if (mk && !rc) {
+                rc = visible_mask_launch(g, st, mk);
+                *nl += 1;
+            }
         }
         if (rc) return rc;
         t += n;
@@ -1043,7 +1056,8 @@ static int rollout_steps(cn_engine *g, hipStream_t st, bool fuse, int policy, in
 // time instead (every group's launch pair or triple between a fork and a join per step), so the window counts steps.
 // ld: one scan over the T * E state rows follows the last step.
 static int rollout_run(cn_engine *g, void *stream, int policy, int T, const cn_rollout_out *out,
-                       const cn_rollout_noise *nz, int32_t *num_launches, const struct cn_rollout_lidar *ld = nullptr)
+                       const cn_rollout_noise *nz, int32_t *num_launches, const struct cn_rollout_lidar *ld = nullptr,
+                       float *mask = nullptr)
 {
     if (num_launches) *num_launches = 0;
     if (!g) return set_err(CN_EINVAL, "null engine");
@@ -1068,7 +1082,7 @@ static int rollout_run(cn_engine *g, void *stream, int policy, int T, const cn_r
     }
     int nl = 0, rc = CN_OK;
     if (!g->ngroups) {
-        rc = rollout_steps(g, st, true, policy, 0, T, T, out, nz, ld, &nl);
+        rc = rollout_steps(g, st, true, policy, 0, T, T, out, nz, ld, mask, &nl);
     } else if (g->prof_on && g->prof_n < g->prof_cap) {
         for (int t = 0; t < T && !rc; ++t) {
             const bool prof = g->prof_on && g->prof_n < g->prof_cap;
@@ -1076,7 +1090,8 @@ static int rollout_run(cn_engine *g, void *stream, int policy, int T, const cn_r
             rc = mix_fork(g, st);
             if (rc) break;
             for (int k = 0; k < g->ngroups && !rc; ++k)
-                rc = rollout_steps(g->grp[k], mix_stream(g, k, st), false, policy, t, t + 1, T, out, nz, nullptr, &nl);
+                rc = rollout_steps(g->grp[k], mix_stream(g, k, st), false, policy, t, t + 1, T, out, nz, nullptr, mask,
+                                   &nl);
             const int rj = mix_join(g, st);
             if (!rc) rc = rj;
             if (!rc && prof && ++g->prof_n == g->prof_cap) HIPCHK(hipEventRecord(g->ev[1], st));
@@ -1085,7 +1100,7 @@ static int rollout_run(cn_engine *g, void *stream, int policy, int T, const cn_r
         rc = mix_fork(g, st);
         if (rc) return rc;
         for (int k = 0; k < g->ngroups && !rc; ++k)
-            rc = rollout_steps(g->grp[k], mix_stream(g, k, st), true, policy, 0, T, T, out, nz, nullptr, &nl);
+            rc = rollout_steps(g->grp[k], mix_stream(g, k, st), true, policy, 0, T, T, out, nz, nullptr, mask, &nl);
         const int rj = mix_join(g, st);
         if (!rc) rc = rj;
     }
@@ -1106,6 +1121,19 @@ static int rollout_run(cn_engine *g, void *stream, int policy, int T, const cn_r
     return CN_OK;
 }
 
+// sigma == 0: `executed` is a copy of the actions the rollout recorded (one launch)
+static int executed_copy(const cn_engine *g, void *stream, int T, const cn_rollout_out *out,
+                         const cn_rollout_noise *noise, int32_t *num_launches)
+{
+    const int64_t n = (int64_t)T * g->E * 2;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(cn_copy32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n,
+                       (const uint32_t *)out->actions, (uint32_t *)noise->executed);
+    HIPCHK(hipGetLastError());
+    if (num_launches) *num_launches += 1;
+    return CN_OK;
+}
+
 int cn_rollout(cn_engine *g, void *stream, int policy, int T, const cn_rollout_out *out, int32_t *num_launches)
 {
     return rollout_run(g, stream, policy, T, out, nullptr, num_launches);
@@ -1122,13 +1150,7 @@ int cn_rollout_noisy(cn_engine *g, void *stream, int policy, int T, const cn_rol
     // sigma == 0: cn_rollout itself; `executed` is a copy of the actions it recorded
     const int rc = rollout_run(g, stream, policy, T, out, nullptr, num_launches);
     if (rc || !noise->executed || T == 0) return rc;
-    const int64_t n = (int64_t)T * g->E * 2;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(cn_copy32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n,
-                       (const uint32_t *)out->actions, (uint32_t *)noise->executed);
-    HIPCHK(hipGetLastError());
-    if (num_launches) *num_launches += 1;
-    return CN_OK;
+    return executed_copy(g, stream, T, out, noise, num_launches);
 }
 
 int cn_rollout_lidar(cn_engine *g, void *stream, int policy, int T, const cn_rollout_out *out,
@@ -1143,13 +1165,21 @@ int cn_rollout_lidar(cn_engine *g, void *stream, int policy, int T, const cn_rol
     const int rc = rollout_run(g, stream, policy, T, out, noisy ? noise : nullptr, num_launches, lidar);
     if (rc || noisy || !noise || !noise->executed || T == 0) return rc;
     // sigma == 0: cn_rollout_noisy's copy of the actions into `executed`
-    const int64_t n = (int64_t)T * g->E * 2;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(cn_copy32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n,
-                       (const uint32_t *)out->actions, (uint32_t *)noise->executed);
-    HIPCHK(hipGetLastError());
-    if (num_launches) *num_launches += 1;
-    return CN_OK;
+    return executed_copy(g, stream, T, out, noise, num_launches);
+}
+
+int cn_rollout_masked(cn_engine *g, void *stream, int policy, int T, const cn_rollout_out *out,
+                      const cn_rollout_noise *noise, float *mask, int32_t *num_launches)
+{
+    if (num_launches) *num_launches = 0;
+    if (!g) return set_err(CN_EINVAL, "null engine");
+    if (!mask) return set_err(CN_EINVAL, "cn_rollout_masked: mask required");
+    if (noise && !(noise->sigma >= 0.0f && noise->sigma <= 3.402823466e38f))   // (NaN fails both comparisons)
+        return set_err(CN_EINVAL, "cn_rollout_masked: noise with a finite sigma >= 0 required");
+    const bool noisy = noise && noise->sigma > 0.0f;
+    const int rc = rollout_run(g, stream, policy, T, out, noisy ? noise : nullptr, num_launches, nullptr, mask);
+    if (rc || noisy || !noise || !noise->executed || T == 0) return rc;
+    return executed_copy(g, stream, T, out, noise, num_launches);   // sigma == 0: cn_rollout_noisy's copy
 }
 
 int cn_debug_disc_quad(void *stream, int64_t n, int mode, const double *px, const double *py, const double *r,

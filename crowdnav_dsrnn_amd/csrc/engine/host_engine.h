@@ -119,11 +119,13 @@ static int keysnap(const cn_engine *g, hipStream_t st)
 // Launch modes: a single step with host-passed arguments; graph mode (DEVSEQ, plain engines); a multi-step launch
 // (SEQ, quad-path engines and quad-path groups of a mixed engine); a cn_rollout launch (SEQ + ROBOT, the same
 // engines and groups) and a cn_rollout_lidar launch (SEQ + ROBOT + REC, plain engines: it records the state rows
-// as well). A combination that is not listed does not exist: the kd-tree path (kd) has no SEQ / ROBOT kernel,
-// mixed-engine groups (mix) none for graph mode or the recording rollout (no LiDAR on a mixed engine).
+// as well); a cn_rollout_masked launch (SEQ + ROBOT + MASK, the engines and groups of cn_rollout: it records the
+// visible_masks rows as well). A combination that is not listed does not exist: the kd-tree path (kd) has no SEQ /
+// ROBOT kernel, mixed-engine groups (mix) none for graph mode or the recording rollout (no LiDAR on a mixed engine).
 // (The entries' order is the order in which the compiler emits the kernels into the code object: the groups'
-// multi-step kernels are appended at the end, so the earlier ones are emitted as before.)
-enum StepMode { STEP_SINGLE, STEP_DEVSEQ, STEP_SEQ, STEP_ROBOT, STEP_ROBOT_REC };
+// multi-step kernels and then the mask-recording kernels are appended at the end, so the earlier ones are emitted as
+// before.)
+enum StepMode { STEP_SINGLE, STEP_DEVSEQ, STEP_SEQ, STEP_ROBOT, STEP_ROBOT_REC, STEP_ROBOT_MASK };
 typedef void (*StepKernelFn)(StepArgs, cn_config);
 struct StepKernelEntry {
     bool kd, phx, mix;
@@ -132,8 +134,9 @@ struct StepKernelEntry {
 };
 #define STEP_KERNEL(KD, PHX, MIX, MODE) \
     {KD, PHX, MIX, MODE,                                                                                             \
-     cn_step_kernel<KD, PHX, MIX, MODE == STEP_DEVSEQ, MODE == STEP_SEQ || MODE == STEP_ROBOT || MODE == STEP_ROBOT_REC, \
-                    MODE == STEP_ROBOT || MODE == STEP_ROBOT_REC, MODE == STEP_ROBOT_REC>}
+     cn_step_kernel<KD, PHX, MIX, MODE == STEP_DEVSEQ, MODE != STEP_SINGLE && MODE != STEP_DEVSEQ,                   \
+                    MODE == STEP_ROBOT || MODE == STEP_ROBOT_REC || MODE == STEP_ROBOT_MASK, MODE == STEP_ROBOT_REC,  \
+                    MODE == STEP_ROBOT_MASK>}
 static const StepKernelEntry step_kernels[] = {
     STEP_KERNEL(false, false, false, STEP_SEQ),    STEP_KERNEL(false, true, false, STEP_SEQ),
     STEP_KERNEL(true, false, false, STEP_SINGLE),  STEP_KERNEL(false, false, false, STEP_SINGLE),
@@ -145,7 +148,9 @@ static const StepKernelEntry step_kernels[] = {
     STEP_KERNEL(false, false, false, STEP_ROBOT),  STEP_KERNEL(false, true, false, STEP_ROBOT),
     STEP_KERNEL(false, false, false, STEP_ROBOT_REC), STEP_KERNEL(false, true, false, STEP_ROBOT_REC),
     STEP_KERNEL(false, false, true, STEP_SEQ),     STEP_KERNEL(false, true, true, STEP_SEQ),
-    STEP_KERNEL(false, false, true, STEP_ROBOT),   STEP_KERNEL(false, true, true, STEP_ROBOT)};
+    STEP_KERNEL(false, false, true, STEP_ROBOT),   STEP_KERNEL(false, true, true, STEP_ROBOT),
+    STEP_KERNEL(false, false, false, STEP_ROBOT_MASK), STEP_KERNEL(false, true, false, STEP_ROBOT_MASK),
+    STEP_KERNEL(false, false, true, STEP_ROBOT_MASK),  STEP_KERNEL(false, true, true, STEP_ROBOT_MASK)};
 #undef STEP_KERNEL
 
 // the kernel of a launch, or null where the combination does not exist

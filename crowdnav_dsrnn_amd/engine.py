@@ -126,7 +126,7 @@ class CrowdNavEngine:
         spatial_edges rows past an env's own count are padding (`human_mask` False): a never-seen human
         at the reference's unseen-belief position (15, 15). Build the configs with
         config.make_mixed_cn_configs.
-        scripted=True (cn_mixed_scripted; holonomic groups): robot_act and rollout (with noise=) serve this engine,
+        scripted=True (cn_mixed_scripted; holonomic groups): robot_act and rollout (with noise=, mask=) serve this engine,
         every group on its own stream by the rule of a plain engine of its count. Off, the default, they refuse a
         mixed engine as before. step_seq needs no opt-in; rollout(lidar=) and graph mode are never served.
         scripted_unicycle=True (cn_scripted_unicycle) on top of scripted=True: unicycle groups are served as well.
@@ -320,10 +320,10 @@ class CrowdNavEngine:
         except (KeyError, TypeError):
             raise ValueError("rollout: lidar must be a dict with beams, max_range and robot_radius")
 
-    def rollout_buffers(self, T, obs_every_step=True, executed=False, lidar=None):
+    def rollout_buffers(self, T, obs_every_step=True, executed=False, lidar=None, mask=False):
         """Fresh device tensors for rollout(T): the `out` dict without 'num_launches' (executed=True: with the
         'executed' rows of a rollout with noise; lidar=dict(beams=, ..): with the 'lidar' rows and the state rows
-        of a rollout with lidar)."""
+        of a rollout with lidar; mask=True: with the 'visible_masks' rows of a rollout with mask)."""
         t, E, N, dev = self.torch, self.E, self.N, self.device
         out = {"actions": t.zeros((T, E, 2), dtype=t.float32, device=dev)}
         if executed:
@@ -333,6 +333,8 @@ class CrowdNavEngine:
             out["lidar"] = t.zeros((T, E, 1, 7 + beams), dtype=t.float32, device=dev)
             out["robot_state"] = t.zeros((9, T, E), dtype=t.float64, device=dev)
             out["human_state"] = t.zeros((3, T, E, N), dtype=t.float64, device=dev)
+        if mask:
+            out["visible_masks"] = t.zeros((T, E, N) if obs_every_step else (E, N), dtype=t.float32, device=dev)
         if obs_every_step:
             out["robot_node"] = t.zeros((T, E, 1, 7), dtype=t.float32, device=dev)
             out["temporal_edges"] = t.zeros((T, E, 1, 2), dtype=t.float32, device=dev)
@@ -349,7 +351,7 @@ class CrowdNavEngine:
 
     _ROLLOUT_OPTIONAL = ("reward", "done", "event", "info", "ep_return", "ep_len")
 
-    def rollout(self, policy, T, obs_every_step=True, out=None, noise=None, lidar=None):
+    def rollout(self, policy, T, obs_every_step=True, out=None, noise=None, lidar=None, mask=False):
         """T closed-loop steps of the scripted robot (cn_rollout): robot_act(policy) -> step, every step recorded,
         with the rows of that eager loop bit for bit. Returns a dict of device tensors: actions (T, E, 2);
         robot_node / temporal_edges / spatial_edges (T, E, ...) = the observation AFTER step t (with
@@ -366,7 +368,12 @@ class CrowdNavEngine:
         'lidar' (T, E, 1, 7 + beams) f32, the live ConvGRU observation AFTER step t (what lidar_scan writes right
         after that step), and the state it was scanned from, 'robot_state' (9, T, E) and 'human_state' (3, T, E, N)
         f64 (r_px, r_py, r_vx, r_vy, r_radius, r_gx, r_gy, r_vpref, r_theta; h_px, h_py, h_r). Each is taken from
-        `out` when given (a trainer aims 'lidar' at its storage) and allocated otherwise."""
+        `out` when given (a trainer aims 'lidar' at its storage) and allocated otherwise.
+        mask (True, or `out` holding 'visible_masks'; not with lidar) -> cn_rollout_masked: the dict gains
+        'visible_masks' (T, E, N) f32, what visible_mask() returns right after step t ((E, N) with
+        obs_every_step=False: the last step's), written by the rollout launches themselves where the steps are fused
+        and by one visible_mask launch per step elsewhere. Taken from `out` when given (a trainer aims it at its
+        storage) and allocated otherwise."""
         t = self.torch
         if policy not in self.ROBOT_POLICIES:
             raise ValueError("rollout: policy %r (one of %s)" % (policy, sorted(self.ROBOT_POLICIES)))
@@ -376,9 +383,10 @@ class CrowdNavEngine:
         noise = RolloutNoise.of(noise)
         E, N = self.E, self.N
         if out is None:
-            out = self.rollout_buffers(T, obs_every_step, executed=noise is not None)
+            out = self.rollout_buffers(T, obs_every_step, executed=noise is not None, mask=bool(mask))
         else:
             out = dict(out)
+            mask = bool(mask) or out.get("visible_masks") is not None
             if noise is not None and out.get("executed") is None:
                 out["executed"] = t.zeros((T, E, 2), dtype=t.float32, device=self.device)
         rl = None
@@ -399,6 +407,17 @@ class CrowdNavEngine:
             rl = _lib.RolloutLidar(out["lidar"].data_ptr(), beams, max_range, robot_radius,
                                    out["robot_state"].data_ptr(), out["human_state"].data_ptr())
         R = 1 if not obs_every_step else T
+        if mask:
+            if lidar is not None:
+                raise ValueError("rollout: mask and lidar exclude each other (no visible_masks with the LiDAR "
+                                 "observation)")
+            v = out.get("visible_masks")
+            if v is None:
+                v = out["visible_masks"] = t.zeros((T, E, N) if obs_every_step else (E, N), dtype=t.float32,
+                                                   device=self.device)
+            if v.dtype != t.float32 or v.device != self.device or not v.is_contiguous() or v.numel() != R * E * N:
+                raise ValueError("rollout: out['visible_masks'] must be a contiguous %s tensor of %d elements on %s"
+                                 % (t.float32, R * E * N, self.device))
         want = {"actions": (T * E * 2, t.float32), "robot_node": (R * E * 7, t.float32),
                 "temporal_edges": (R * E * 2, t.float32), "spatial_edges": (R * E * N * 2, t.float32),
                 "reward": (T * E, t.float32), "done": (T * E, t.uint8), "event": (T * E, t.int8),
@@ -432,6 +451,10 @@ class CrowdNavEngine:
                 _lib.check(_lib.lib().cn_rollout_lidar(self._h, self._stream(), self.ROBOT_POLICIES[policy], T,
                                                        ctypes.byref(ro), None if nz is None else ctypes.byref(nz),
                                                        ctypes.byref(rl), ctypes.byref(nl)))
+            elif mask:
+                _lib.check(_lib.lib().cn_rollout_masked(self._h, self._stream(), self.ROBOT_POLICIES[policy], T,
+                                                        ctypes.byref(ro), None if nz is None else ctypes.byref(nz),
+                                                        out["visible_masks"].data_ptr(), ctypes.byref(nl)))
             elif noise is None:
                 _lib.check(_lib.lib().cn_rollout(self._h, self._stream(), self.ROBOT_POLICIES[policy], T,
                                                  ctypes.byref(ro), ctypes.byref(nl)))

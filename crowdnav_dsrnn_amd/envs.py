@@ -32,7 +32,7 @@ import numpy as np
 
 from . import abi, info as info_mod, spaces
 from .config import (UnsupportedConfig, clone_config, make_cn_config, make_varied_cn_configs, no_visible_masks,
-                     varied_human_nums, visible_masks_on)
+                     varied_human_nums, visible_masks_on, visible_masks_scripted)
 
 _REGISTRY = {}
 
@@ -232,6 +232,7 @@ class CrowdNavVecEnv:
         self.human_nums = varied_human_nums(config)
         # sim.visible_masks: the observation also carries 'visible_masks' (UnsupportedConfig with 'convgru')
         self.visible_masks = visible_masks_on(config)
+        visible_masks_scripted(config)   # (UnsupportedConfig when set without sim.visible_masks)
         mixed = None
         if self.human_nums is not None:
             mixed = make_varied_cn_configs(config, self.human_nums, self.num_envs, env_offset=env_offset, nenv=nenv,
@@ -404,9 +405,12 @@ class CrowdNavVecEnv:
         A unicycle env with robot.scripted_unicycle: 'actions' holds unicycle actions (dv, dtheta), each within
         [-0.1, 0.1], and the noise sigma is in those action units (0.1 is the whole range); without that opt-in the
         engine refuses. 'dwa' (a unicycle env with robot.scripted_dwa) likewise, always as launch pairs.
-        An env with sim.visible_masks: UnsupportedConfig (the recorded rows carry no mask)."""
+        An env with sim.visible_masks and sim.visible_masks_scripted: the dict gains 'visible_masks' (T, E, N), the
+        mask step_device would have returned after every step ((E, N) without obs_every_step: the last step's),
+        recorded by the rollout's own launches (the engine's rollout with mask=True; `out` may bring the tensor);
+        without that opt-in: UnsupportedConfig (the recorded rows would carry no mask)."""
         _no_varied(self.config, "rollout")
-        no_visible_masks(self.config, "rollout")
+        mask = no_visible_masks(self.config, "rollout")
         lidar = None
         if self.obs_mode == "convgru":
             if not self._lidar_live:
@@ -418,7 +422,7 @@ class CrowdNavVecEnv:
             raise UnsupportedConfig("rollout: obs_mode=%r" % self.obs_mode)
         self._state_cache = None
         if lidar is None:
-            ro = self.engine.rollout(policy, T, obs_every_step=obs_every_step, out=out, noise=noise)
+            ro = self.engine.rollout(policy, T, obs_every_step=obs_every_step, out=out, noise=noise, mask=mask)
             if self.human_nums is not None:
                 d = self._detected
                 ro["detected_human_num"] = d.unsqueeze(0).expand(int(T), -1, -1) if obs_every_step else d

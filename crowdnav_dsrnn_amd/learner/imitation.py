@@ -24,6 +24,10 @@ on the mixed engine and records the padded observation into the same storage ten
 'detected_human_num' rows, constant over the env's life, are filled once, and the policy reads them as under PPO (the
 attention of ops.spatial_attention_var).
 
+An env with config.sim.visible_masks and sim.visible_masks_scripted: the rollout records 'visible_masks' into the
+storage as well (cn_rollout_masked, row 0 from reset()), and the DSRNN policy attends to the visible humans only, as
+under PPO (ops.spatial_attention_mask). Without the second opt-in: UnsupportedConfig.
+
 A unicycle env (action_space.kinematics 'unicycle' with the opt-in config.robot.scripted_unicycle): the expert's
 velocity goes through the tracking law on the device (policy_factory.unicycle_track) and the labels are the unicycle
 actions (dv, dtheta), each within [-0.1, 0.1]. `sigma` is then in those action units -- 0.1 is the whole range, so
@@ -51,7 +55,8 @@ class BehaviourCloning:
         from ..policy_factory import ScriptedRobot
 
         ScriptedRobot.check(envs, expert)   # unknown controller / unicycle without its opt-in: before anything touches the GPU
-        no_visible_masks(envs.config, "BehaviourCloning")   # (the rollout's rows carry no 'visible_masks')
+        # sim.visible_masks: only with sim.visible_masks_scripted, where the rollout records 'visible_masks' as well
+        masked = no_visible_masks(envs.config, "BehaviourCloning")
         mode = getattr(envs, "obs_mode", "srnn")
         self.convgru = mode == "convgru"
         if self.convgru:
@@ -102,6 +107,8 @@ class BehaviourCloning:
             self._buf["human_state"] = torch.zeros((3, T, E, N), dtype=torch.float64, device=dev)
         else:
             self._buf = {k: r.obs[k][1:] for k in ("robot_node", "temporal_edges", "spatial_edges")}
+            if masked:   # (cn_rollout_masked writes the rows; SRNN.forward reads the key as under PPO)
+                self._buf["visible_masks"] = r.obs["visible_masks"][1:]
         self._buf["actions"] = r.actions
         self._buf["reward"] = r.rewards.view(T, E)
         self._buf["done"] = torch.zeros((T, E), dtype=torch.uint8, device=dev)

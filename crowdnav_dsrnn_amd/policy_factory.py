@@ -421,8 +421,8 @@ class ScriptedRobot:
     @classmethod
     def check_rollout(cls, venv, name):
         """check(), and UnsupportedConfig for an env whose observation a rollout cannot record: 'convgru' without
-        lidar.live, or an env with config.sim.visible_masks, whose mask the recorded rows do not carry (before anything
-        touches the GPU)."""
+        lidar.live, or an env with config.sim.visible_masks without the opt-in config.sim.visible_masks_scripted, whose
+        mask the recorded rows would not carry (before anything touches the GPU)."""
         cls.check(venv, name)
         no_visible_masks(venv.config, "ScriptedRobot.rollout")
         mode = getattr(venv, "obs_mode", "srnn")
@@ -456,7 +456,9 @@ class ScriptedRobot:
         On a 'convgru' env with lidar.live the dict also holds 'lidar' (T, E, 1, 7 + beams), the LiDAR observation
         after each step, with the state rows it was scanned from (cn_rollout_lidar); without lidar.live the
         observation carries the scan held since the episode's reset, which no recorded row determines:
-        UnsupportedConfig."""
+        UnsupportedConfig.
+        On an env with sim.visible_masks and sim.visible_masks_scripted the dict also holds 'visible_masks' (T, E, N),
+        the mask after each step (cn_rollout_masked); without that opt-in: UnsupportedConfig."""
         self.check_rollout(self.venv, self.name)
         return self.venv.rollout(self.name, T, obs_every_step=obs_every_step, out=out, noise=noise)
 

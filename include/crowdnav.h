@@ -42,6 +42,8 @@
  *                   noise, the label staying clean: noise-injected expert demonstrations for behaviour cloning
  *   cn_rollout_lidar ⟵ (no reference counterpart) either of the two, recording the state every step leaves and,
  *                   from it, the live ConvGRU observation (cn_lidar_scan's) of every step in one scan launch
+ *   cn_rollout_masked ⟵ (no reference counterpart) either of the two, recording cn_visible_mask's row of every step
+ *                   inside the rollout launches: expert demonstrations for the masked spatial attention
  *   cn_lidar_obs     ⟵ CrowdSimDict.generate_ob's 'convgru' observation (crowd_sim_dict.py:96-101) with
  *                   LidarSensor.sensor_spin (crowd_sim/envs/utils/lidarv2.py:398-427) evaluated at reset
  *   cn_lidar_scan    ⟵ the scan CrowdSimDict.step() takes every step and discards (crowd_sim_dict.py:224-251):
@@ -707,6 +709,34 @@ struct cn_rollout_lidar {   /* (no typedef: the function below has the name, as 
 int cn_rollout_lidar(cn_engine *eng, void *stream, int policy, int T, const cn_rollout_out *out,
                      const cn_rollout_noise *noise /* NULL: no noise */, const struct cn_rollout_lidar *lidar,
                      int32_t *num_launches);
+
+/* cn_rollout / cn_rollout_noisy that also record which humans the robot sees after every step, so that a policy with
+ * the masked spatial attention (the observation key 'visible_masks') can be trained from the scripted expert.
+ * mask is [T][E][NS] float32, NS = cn_visible_mask's padded stride: row t of env e is bit for bit what
+ * cn_visible_mask(eng, stream, ..) writes for env e when called right after step t (one device function serves
+ * both). An env that ended and auto-reset inside step t therefore carries its new episode's mask (the reset path:
+ * flags == 0 and the float64 test). Without CN_ROLLOUT_OBS_EVERY_STEP mask is one row [E][NS] holding the last
+ * step's, as the observation buffers do. `out` is cn_rollout's; noise = NULL is cn_rollout, otherwise
+ * cn_rollout_noisy (sigma == 0 included). Every row those record and the state blob afterwards are theirs bit for
+ * bit; a call of T steps equals calls of T1 and T - T1 steps. It is a new function and needs no opt-in of its own.
+ * Stream-ordered; no allocation, no synchronisation, no memset. *num_launches counts every kernel launch:
+ *   Fused path (cn_rollout's conditions), T' = T minus a first step after cn_reset / cn_set_state:
+ *       [1 if sigma > 0: the noise block] + ceil(T' / C)                               (T' > 0)
+ *     i.e. cn_rollout's / cn_rollout_noisy's own count: the rollout launches record the mask themselves (their row 0
+ *     travels in the kernel arguments). While the controller of step s >= 1 runs on one wave, the other waves of the
+ *     workgroup evaluate the mask of the state step s - 1 left, one lane per (env, slot); the launch's last step
+ *     writes its own row.
+ *   Elsewhere (chunk 1, graph mode, that first step, ORCA at N + 1 > 10, the kd-tree step path, CN_ROBOT_DWA), per
+ *     step: cn_robot_act, [the perturbation if sigma > 0], cn_step, cn_visible_mask's launch into row t: 3 or 4
+ *     launches (graph mode: one more kernel node per step).
+ *   A mixed engine after cn_mixed_scripted(eng, 1): every group on its own stream by the same rule, its envs at their
+ *     rows of the buffer, the padded slots written as 0.0f in every row; *num_launches counts all groups.
+ *   A unicycle engine after cn_scripted_unicycle / cn_scripted_dwa: the same rule, as in cn_rollout.
+ *   + 1 for the copy into `executed` when noise is given with sigma == 0.
+ * CN_EINVAL: mask NULL, cn_rollout_noisy's for a non-NULL noise, cn_rollout's. CN_EUNSUPPORTED: cn_rollout's. All are
+ * checked before any launch (*num_launches = 0). T = 0 launches nothing. */
+int cn_rollout_masked(cn_engine *eng, void *stream, int policy, int T, const cn_rollout_out *out,
+                      const cn_rollout_noise *noise /* NULL: no noise */, float *mask, int32_t *num_launches);
 
 /* Test hooks of the kd-tree path's resumable spawns (the spawn waves that draw upcoming episodes park a
  * crowded spawn between two humans once a wave has worked `cycles` clock cycles in a launch, and a later

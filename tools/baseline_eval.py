@@ -24,9 +24,13 @@ the dynamic-window controller of the unicycle robot (config.robot.scripted_dwa; 
 --phase val evaluates the validation episodes (the same count, what the defaults were selected on) instead of the test
 episodes; --visible 0 / 1 restricts the run to one visibility.
 
+--fov F sets robot.FOV (in units of pi; default 2.0, the full circle). --visible-masks runs on an env with
+sim.visible_masks and sim.visible_masks_scripted (the rollouts then record the mask as well, cn_rollout_masked); a
+scripted robot does not read the mask, so the rows are those of the same env without it.
+
 Usage: python tools/baseline_eval.py [--envs 100] [--test-size 500] [--humans 5 | --human-nums 5 10] [--rollout]
            [--kinematics holonomic|unicycle] [--robots orca dwa] [--dwa JSON] [--phase test|val] [--visible 0|1]
-           [--out FILE]
+           [--fov F] [--visible-masks] [--out FILE]
 """
 import argparse
 import json
@@ -60,6 +64,9 @@ def main():
     ap.add_argument("--dwa", default=None, help="JSON dict of overrides of policy_factory.DWA_DEFAULTS")
     ap.add_argument("--phase", default="test", choices=("test", "val"))
     ap.add_argument("--visible", type=int, default=None, choices=(0, 1))
+    ap.add_argument("--fov", type=float, default=None, help="robot.FOV in units of pi (default: the config's 2.0)")
+    ap.add_argument("--visible-masks", action="store_true",
+                    help="an env with sim.visible_masks + sim.visible_masks_scripted")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     uni = args.kinematics == "unicycle"
@@ -80,6 +87,10 @@ def main():
                 c.sim.human_nums_scripted = True
             c.env.test_size = c.env.val_size = args.test_size
             c.robot.visible = visible
+            if args.fov is not None:
+                c.robot.FOV = args.fov
+            if args.visible_masks:
+                c.sim.visible_masks = c.sim.visible_masks_scripted = True
             c.action_space.kinematics = args.kinematics
             c.robot.scripted_unicycle = uni
             c.robot.scripted_dwa = dwa if uni and name == "dwa" else None
@@ -102,6 +113,8 @@ def main():
                    "collision_rate": round(last["collision_rate"], 3), "timeout_rate": round(last["timeout_rate"], 3),
                    "nav_time_mean_s": round(float(nav[0]), 2), "nav_time_std_s": round(float(nav[1]), 2),
                    "wall_s": round(wall, 2)}
+            if args.fov is not None or args.visible_masks:
+                rec["fov"], rec["visible_masks"] = float(c.robot.FOV), bool(args.visible_masks)
             if name == "dwa":
                 rec["dwa"] = dwa_params(dwa)
             if args.phase != "test":

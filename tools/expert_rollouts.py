@@ -35,9 +35,14 @@ lidar.live, and the file also holds (cn_rollout_lidar)
 ABSOLUTE in those action units (0.1 is the whole range); the step clips the perturbed action. --robot dwa (unicycle
 only) records the dynamic-window controller (config.robot.scripted_dwa), whose actions are grid points of that range.
 
+--visible-masks (with --fov F, robot.FOV in units of pi) records on an env with sim.visible_masks and
+sim.visible_masks_scripted: the file also holds (cn_rollout_masked)
+
+  visible_masks   (T + 1, E, N)      1.0 for the humans the robot sees in the state of that observation row
+
 Usage: python tools/expert_rollouts.py --out demos.npz [--robot orca] [--envs 256] [--steps 512] [--humans 5]
                                        [--seed 0] [--chunk-steps 128] [--noise-sigma S] [--noise-seed K] [--lidar]
-                                       [--kinematics holonomic|unicycle]
+                                       [--kinematics holonomic|unicycle] [--fov F] [--visible-masks]
 """
 import argparse
 import os
@@ -71,6 +76,8 @@ def main():
     ap.add_argument("--kinematics", default="holonomic", choices=("holonomic", "unicycle"),
                     help="unicycle: the controller drives the unicycle robot through the tracking law")
     ap.add_argument("--lidar", action="store_true", help="record the live LiDAR observation and the state rows as well")
+    ap.add_argument("--fov", type=float, default=None, help="robot.FOV in units of pi (default: the config's 2.0)")
+    ap.add_argument("--visible-masks", action="store_true", help="record the 'visible_masks' rows as well")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("expert_rollouts: needs a GPU")
@@ -82,6 +89,12 @@ def main():
         if args.kinematics != "unicycle":
             raise SystemExit("expert_rollouts: --robot dwa needs --kinematics unicycle")
         c.robot.scripted_dwa = True   # (policy_factory.DWA_DEFAULTS)
+    if args.fov is not None:
+        c.robot.FOV = args.fov
+    if args.visible_masks:
+        if args.lidar:
+            raise SystemExit("expert_rollouts: --visible-masks is not for --lidar (no human slots to mask)")
+        c.sim.visible_masks = c.sim.visible_masks_scripted = True
     if args.lidar:
         c.robot.policy = "convgru"
         c.lidar.enable = True
@@ -95,7 +108,8 @@ def main():
         obs0 = envs.engine.obs()
     else:
         rows = {}
-    rows.update({k: [obs0[k].reshape((1,) + tuple(obs0[k].shape)).cpu().numpy()] for k in OBS})
+    obs_keys = OBS + (("visible_masks",) if args.visible_masks else ())
+    rows.update({k: [obs0[k].reshape((1,) + tuple(obs0[k].shape)).cpu().numpy()] for k in obs_keys})
     step_keys = STEP + (("executed",) if args.noise_sigma is not None else ())
     state_keys = ("robot_state", "human_state") if args.lidar else ()
     rows.update({k: [] for k in step_keys + state_keys})
@@ -108,7 +122,7 @@ def main():
             out = robot.rollout(n, noise={"sigma": args.noise_sigma, "seed": args.noise_seed, "step0": t})
         launches += out["num_launches"]
         torch.cuda.synchronize()
-        for k in OBS + step_keys + state_keys + (("lidar",) if args.lidar else ()):
+        for k in obs_keys + step_keys + state_keys + (("lidar",) if args.lidar else ()):
             rows[k].append(out[k].cpu().numpy())
         t += n
     data = {k: np.concatenate(v, axis=1 if k in state_keys else 0) for k, v in rows.items()}

@@ -20,12 +20,16 @@ goes through the tracking law on the device and the labels are the unicycle acti
 [-0.1, 0.1]. There the noise is given with --sigma, ABSOLUTE in those action units (0.1 is the whole range; --sigma-frac
 is not read). --expert dwa (unicycle only) clones the dynamic-window controller made for that robot
 (config.robot.scripted_dwa at policy_factory.DWA_DEFAULTS) instead of ORCA or the social force behind the tracking law.
+--fov F sets robot.FOV (in units of pi; the default config's is 2.0, the full circle) for training and evaluation
+alike; --visible-masks (DSRNN only) also runs all of it on envs with sim.visible_masks and sim.visible_masks_scripted:
+the rollouts record the 'visible_masks' rows (cn_rollout_masked) and the policy attends to the visible humans only.
 Needs a GPU.
 
 Usage: python tools/imitation_pretrain.py [--policy srnn|convgru] [--expert orca] [--updates 3000] [--envs 1024] [--steps 32] [--epochs 1]
            [--mini-batch 2] [--lr 1e-3] [--value-coef 0.5] [--sigma-frac 0 0.1 0.3] [--humans 5] [--seed 0]
            [--human-nums 5 10 [--unseen 7]] [--kinematics holonomic|unicycle [--sigma 0 0.03]]
-           [--eval-envs 100] [--test-size 500] [--log-every K] [--out policy.pt] [--json FILE]
+           [--fov F] [--visible-masks] [--eval-envs 100] [--test-size 500] [--log-every K] [--out policy.pt]
+           [--json FILE]
 """
 import argparse
 import json
@@ -76,6 +80,9 @@ def main():
     ap.add_argument("--human-nums", type=int, nargs="+", default=None,
                     help="clone on an env of varying human count; every row per density")
     ap.add_argument("--unseen", type=int, default=7, help="with --human-nums: a density the cloning never saw")
+    ap.add_argument("--fov", type=float, default=None, help="robot.FOV in units of pi (default: the config's 2.0)")
+    ap.add_argument("--visible-masks", action="store_true",
+                    help="envs with sim.visible_masks + sim.visible_masks_scripted: the masked spatial attention")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--eval-envs", type=int, default=100)
     ap.add_argument("--test-size", type=int, default=500)
@@ -87,6 +94,8 @@ def main():
         raise SystemExit("imitation_pretrain: needs a GPU")
     if args.human_nums and args.policy != "srnn":
         raise SystemExit("imitation_pretrain: --human-nums is the DSRNN policy's (no LiDAR on a mixed engine)")
+    if args.visible_masks and args.policy != "srnn":
+        raise SystemExit("imitation_pretrain: --visible-masks is the DSRNN policy's (no human slots in the LiDAR row)")
     log = logging.getLogger("imitation_pretrain")
     log.addHandler(logging.NullHandler())
     log.propagate = False
@@ -95,6 +104,10 @@ def main():
     c.action_space.kinematics = args.kinematics
     uni = args.kinematics == "unicycle"
     c.robot.scripted_unicycle = uni
+    if args.fov is not None:
+        c.robot.FOV = args.fov
+    if args.visible_masks:
+        c.sim.visible_masks = c.sim.visible_masks_scripted = True
     if args.expert == "dwa":
         if not uni:
             raise SystemExit("imitation_pretrain: --expert dwa needs --kinematics unicycle")
@@ -119,6 +132,7 @@ def main():
         ct.sim.human_nums_scripted = True
 
     def emit(row):
+        row = dict(row, fov=float(c.robot.FOV), visible_masks=bool(args.visible_masks))
         lines.append(json.dumps(row))
         print(lines[-1], flush=True)
 

@@ -19,8 +19,13 @@ Two more configurations exist there and run only when named: (e) 5 humans and (f
 controller 'dwa' (cn_scripted_dwa at policy_factory.DWA_DEFAULTS). It always runs as launch pairs, so `fused` equals
 `native_pairs` for it; its rows gain `robot_act_only`, T controller launches alone, for the controller's share.
 
+--mask (with --fov F, robot.FOV in units of pi, default 0.5 then) times the masked rollout (cn_rollout_masked: the
+'visible_masks' rows recorded by the rollout launches themselves) on both cn_rollout paths and adds two rows per
+configuration: `fused_unmasked`, the same engine's cn_rollout without the mask, and `python_triple`, the Python loop
+robot_act() + step() + visible_mask().
+
 Usage: python tools/rollout_time.py [--envs 4096] [--steps 256] [--noise-sigma S] [--kinematics holonomic|unicycle]
-           [--configs a b c d e f] [--out FILE]
+           [--configs a b c d e f] [--fov F] [--mask] [--out FILE]
 """
 import argparse
 import json
@@ -52,6 +57,8 @@ def main():
     ap.add_argument("--noise-sigma", type=float, default=None)
     ap.add_argument("--kinematics", default="holonomic", choices=("holonomic", "unicycle"))
     ap.add_argument("--configs", nargs="+", default=["a", "b", "c", "d"], choices=("a", "b", "c", "d", "e", "f"))
+    ap.add_argument("--fov", type=float, default=None, help="robot.FOV in units of pi (default: the config's 2.0)")
+    ap.add_argument("--mask", action="store_true", help="time the masked rollout (cn_rollout_masked)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -60,6 +67,7 @@ def main():
     lines = []
     noise = None if args.noise_sigma is None else {"sigma": args.noise_sigma, "seed": 1, "step0": 0}
     kw = {} if noise is None else {"noise": noise}
+    fov = args.fov if args.fov is not None else (0.5 if args.mask else None)
     for tag, N, name in (("a", 5, "orca"), ("b", 9, "orca"), ("c", 10, "social_force"), ("d", 5, "social_force"),
                          ("e", 5, "dwa"), ("f", 9, "dwa")):
         if tag not in args.configs:
@@ -70,6 +78,8 @@ def main():
         c.sim.human_num = N
         c.action_space.kinematics = args.kinematics
         c.humans.policy = "orca"
+        if fov is not None:
+            c.robot.FOV = fov
         eng = CrowdNavEngine(make_cn_config(c, num_envs=E), "cuda:0")
         if args.kinematics == "unicycle":
             eng.scripted_unicycle(True)
@@ -79,15 +89,26 @@ def main():
         eng.reset()
         eng.step(eng.robot_act(name))   # (the first step after cn_reset is a pair on every path)
         buf = eng.rollout_buffers(T, **({} if noise is None else {"executed": True}))
+        mbuf = eng.rollout_buffers(T, mask=True, **({} if noise is None else {"executed": True})) if args.mask else buf
         launches = {}
 
         def fused():
             eng.set_seq_chunk(chunk)
-            launches["fused"] = eng.rollout(name, T, out=buf, **kw)["num_launches"]
+            launches["fused"] = eng.rollout(name, T, out=mbuf, **kw)["num_launches"]
 
         def native_pairs():
             eng.set_seq_chunk(1)
-            launches["native_pairs"] = eng.rollout(name, T, out=buf, **kw)["num_launches"]
+            launches["native_pairs"] = eng.rollout(name, T, out=mbuf, **kw)["num_launches"]
+
+        def fused_unmasked():
+            eng.set_seq_chunk(chunk)
+            launches["fused_unmasked"] = eng.rollout(name, T, out=buf, **kw)["num_launches"]
+
+        def python_triple():
+            for _ in range(T):
+                eng.step(eng.robot_act(name))
+                eng.visible_mask()
+            launches["python_triple"] = 3 * T
 
         def python_pairs():
             for _ in range(T):
@@ -102,12 +123,14 @@ def main():
         fns = {"fused": fused, "native_pairs": native_pairs, "python_pairs": python_pairs}
         if name == "dwa":
             fns["robot_act_only"] = robot_act_only
+        if args.mask:
+            fns["fused_unmasked"], fns["python_triple"] = fused_unmasked, python_triple
         rounds = {k: [] for k in fns}
         for _ in range(3):
             for k, fn in fns.items():
                 rounds[k].append(timed(fn, T))
         rec = {"config": tag, "kinematics": args.kinematics, "envs": E, "humans": N, "robot": name, "steps": T, "chunk": chunk,
-               "noise_sigma": args.noise_sigma,
+               "noise_sigma": args.noise_sigma, "fov": fov, "mask": bool(args.mask),
                "unit": "us per step (HIP events)", "device": torch.cuda.get_device_name(0), "launches": launches}
         for k, v in rounds.items():
             v = sorted(v)
