@@ -25,7 +25,7 @@ PKG = os.path.basename(HERE)
 
 
 def sources(root=REPO):
-    return [os.path.join(root, PKG, "csrc", n) for n in ("cn_engine.hip", "cn_gru.hip", "cn_attn_mask.hip")]
+    return [os.path.join(root, PKG, "csrc", n) for n in ("cn_engine.hip", "cn_gru.hip", "cn_attn_mask.hip", "cn_lattice.hip")]
 
 
 def deps(root=REPO):

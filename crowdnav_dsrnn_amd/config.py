@@ -115,6 +115,11 @@ class Config(object):
     # (policy_factory.dwa_predict; the engine's cn_scripted_dwa). True: policy_factory.DWA_DEFAULTS; a dict: those with
     # its overrides. None, the default: 'dwa' is refused, as before. It needs no scripted_unicycle (no tracking law).
     robot.scripted_dwa = None
+    # action_head (this project's opt-in; read by policy.Policy alone, the engine never sees it): 'gaussian', the
+    # default, is the reference's DiagGaussian; 'lattice' (with action_space.kinematics = 'unicycle') a 64-way
+    # categorical over the grid of unicycle actions the 'dwa' controller chooses from (policy.LatticeCategorical,
+    # state_dict keys dist.fc_logits.*). Policy(..., head=...) overrides it.
+    robot.action_head = "gaussian"
 
     noise = BaseConfig()
     noise.add_noise = False

@@ -34,6 +34,12 @@ actions (dv, dtheta), each within [-0.1, 0.1]. `sigma` is then in those action u
 0.03 there is a large perturbation -- and the step clips the perturbed action. expert='dwa' (the opt-in
 config.robot.scripted_dwa) is the expert made for that robot: a dynamic-window controller whose labels are grid points
 of the unicycle action space (policy_factory.dwa_predict), with sigma in the same units.
+
+The action head: the loss goes through evaluate_actions, so "the policy's Gaussian" above is whatever head the policy
+has. With the lattice head (config.robot.action_head = 'lattice', unicycle envs) the NLL is the cross-entropy of a
+64-way classification: a 'dwa' label is one of the head's candidates and is scored at its own index, exactly; a
+continuous label (ORCA or the social force through the tracking law) is scored at its nearest lattice point. Nothing
+else in this trainer depends on the head.
 """
 import contextlib
 import time

@@ -7,6 +7,11 @@ infos of every env at every step).
 
 `envs` is a crowdnav_dsrnn_amd.envs.CrowdNavVecEnv (step_device path); episode returns are read from the
 engine's Monitor counters where `done`.
+
+The trainer talks to the action head through `act` and `evaluate_actions` alone, so a policy with the lattice head
+(config.robot.action_head = 'lattice', unicycle envs) runs unchanged: the stored actions are lattice points, which
+PPO's evaluate_actions maps back to their index exactly, and the captured rollout holds one cn_lattice_act node where
+the Gaussian head has cn_gaussian_act.
 """
 import time
 

@@ -12,6 +12,9 @@ spatial_attention_mask(...) — the same over the slots a per-slot mask marks vi
 masked_gru(...)     — the mask-segmented GRU of the three DSRNN RNNs over a (T, B) sequence
                       (cn_gru_fwd_fused: recurrent GEMM on the f32 matrix cores + gates in one launch per
                       step; cn_gru_bwd_step + library GEMMs backward), with its own backward.
+lattice_act(...) / lattice_evaluate(...) — the lattice action head of the unicycle robot: sample or mode with its
+                      log-probability (cn_lattice_act), log-probability and entropy of given actions with their
+                      gradient (cn_lattice_eval_fwd / _bwd); CPU tensors run the torch restatements (*_torch).
 gru_infer_step(...) — one no-autograd step of the same GRU for act(): reads the state through strided views
                       and writes the new state straight into the (B, N + 1, H) layout (cn_gru_fwd_fused).
 """
@@ -527,6 +530,118 @@ def gaussian_act(mean, logstd, deterministic=False):
                                               eps.data_ptr() if eps is not None else None, action.data_ptr(),
                                               logp.data_ptr()))
     return action, logp
+
+
+LATTICE = 64   # candidates of the lattice action head: cn_dwa_predict's 8 x 8 grid, c = 8 a + b
+
+
+def lattice_actions(device=None):
+    """(64, 2) float32: the action of every candidate c = 8 a + b, ((float)((0.1 (2a - 7)) / 7), the same of b):
+    cn_dwa_predict's values, computed in float64 and rounded once."""
+    k = (0.1 * (2.0 * np.arange(8, dtype=np.float64) - 7.0)) / 7.0
+    t = np.stack([np.repeat(k, 8), np.tile(k, 8)], 1).astype(np.float32)
+    return torch.from_numpy(t).to(device) if device is not None else torch.from_numpy(t)
+
+
+def lattice_index(actions):
+    """(..., 2) actions -> (...) int64 index of the nearest lattice point: per component
+    clamp(rint((x * 70 + 7) * 0.5), 0, 7) in float32 (include/crowdnav.h); exact for every lattice point."""
+    k = torch.clamp(torch.round((actions.float() * 70.0 + 7.0) * 0.5), 0.0, 7.0).long()
+    return k[..., 0] * 8 + k[..., 1]
+
+
+def lattice_act_torch(logits, u=None):
+    """The torch restatement of cn_lattice_act: logits (E, 64), u (E,) in [0, 1) or None (the mode) ->
+    (action (E, 2), logp (E, 1), choice (E,) int64). Sampling: the smallest c with p_c > 0 whose inclusive prefix sum
+    exceeds u * S_63, else the highest c with p_c > 0, found by masked index minima / maxima (no data-dependent
+    shapes, no host read)."""
+    logits = logits.float()
+    lane = torch.arange(LATTICE, device=logits.device)
+    m = logits.max(-1, keepdim=True).values
+    if u is None:
+        c = torch.where(logits == m, lane, LATTICE).amin(-1).clamp(max=LATTICE - 1)
+    else:
+        p = torch.exp(logits - m)
+        S = torch.cumsum(p, -1)
+        thr = u.reshape(-1, 1).float() * S[:, -1:]
+        live = p > 0
+        first = torch.where((S > thr) & live, lane, LATTICE).amin(-1)
+        last = torch.where(live, lane, 0).amax(-1)
+        c = torch.where(first < LATTICE, first, last)
+    logp = torch.log_softmax(logits, -1).gather(1, c.unsqueeze(1))
+    return lattice_actions(logits.device)[c], logp, c
+
+
+def lattice_evaluate_torch(logits, actions):
+    """The torch restatement of cn_lattice_eval_fwd (autograd supplies cn_lattice_eval_bwd): logits (B, 64), actions
+    (B, 2) -> (logp (B, 1) of the nearest lattice point, entropy (B,)); candidates of zero probability add nothing to
+    the entropy (no 0 * -inf)."""
+    lsm = torch.log_softmax(logits.float(), -1)
+    q = lsm.exp()
+    ent = -torch.where(q > 0, q * lsm, torch.zeros_like(q)).sum(-1)
+    return lsm.gather(1, lattice_index(actions).unsqueeze(1)), ent
+
+
+def lattice_act(logits, deterministic=False):
+    """The no-grad act() tail of the lattice head in one launch (cn_lattice_act): logits (E, 64) -> (action (E, 2),
+    the lattice point; log_prob (E, 1)); sampled with u = torch.rand((E,)), as gaussian_act draws its eps, or the mode.
+    CPU tensors: lattice_act_torch on the same draw."""
+    logits = _c(logits)
+    E = logits.shape[0]
+    if logits.dim() != 2 or logits.shape[1] != LATTICE:
+        raise ValueError("lattice_act: logits must be (E, %d)" % LATTICE)
+    u = None if deterministic else torch.rand((E,), dtype=torch.float32, device=logits.device)
+    if not logits.is_cuda:
+        action, logp, _ = lattice_act_torch(logits, u)
+        return action, logp
+    action = torch.empty((E, 2), dtype=torch.float32, device=logits.device)
+    logp = torch.empty((E, 1), dtype=torch.float32, device=logits.device)
+    with torch.cuda.device(logits.device):
+        _lib.check(_lib.lib().cn_lattice_act(_stream(logits.device), E, logits.data_ptr(),
+                                             u.data_ptr() if u is not None else None, action.data_ptr(),
+                                             logp.data_ptr(), None))
+    return action, logp
+
+
+class _LatticeEvaluate(torch.autograd.Function):
+    """cn_lattice_eval_fwd / cn_lattice_eval_bwd: only the logits and the action's index are kept for the backward,
+    which recomputes the row's softmax."""
+
+    @staticmethod
+    def forward(ctx, logits, actions):
+        logits, actions = _c(logits), _c(actions)
+        B, dev = logits.shape[0], logits.device
+        logp = torch.empty((B, 1), dtype=torch.float32, device=dev)
+        ent = torch.empty((B,), dtype=torch.float32, device=dev)
+        choice = torch.empty((B,), dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().cn_lattice_eval_fwd(_stream(dev), B, logits.data_ptr(), actions.data_ptr(),
+                                                      logp.data_ptr(), ent.data_ptr(), choice.data_ptr()))
+        ctx.save_for_backward(logits, choice)
+        ctx.mark_non_differentiable(choice)
+        return logp, ent, choice
+
+    @staticmethod
+    def backward(ctx, g_logp, g_ent, _g_choice):
+        logits, choice = ctx.saved_tensors
+        B, dev = logits.shape[0], logits.device
+        g_logp, g_ent = _c(g_logp).reshape(B), _c(g_ent).reshape(B)   # (an unused output arrives as zeros)
+        dlogits = torch.empty_like(logits)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().cn_lattice_eval_bwd(_stream(dev), B, logits.data_ptr(), choice.data_ptr(),
+                                                      g_logp.data_ptr(), g_ent.data_ptr(), dlogits.data_ptr()))
+        return dlogits, None
+
+
+def lattice_evaluate(logits, actions):
+    """logits (B, 64), actions (B, 2) -> (log_prob (B, 1) of each action's nearest lattice point, entropy (B,)), with
+    the gradient to the logits (cn_lattice_eval_fwd / _bwd). CPU tensors: lattice_evaluate_torch."""
+    if logits.dim() != 2 or logits.shape[1] != LATTICE or actions.shape != (logits.shape[0], 2):
+        raise ValueError("lattice_evaluate: logits (B, %d) and actions (B, 2) required" % LATTICE)
+    if not logits.is_cuda:
+        return lattice_evaluate_torch(logits, actions)
+    logp, ent, _ = _LatticeEvaluate.apply(logits, actions)
+    return logp, ent
 
 
 class _AttnPool(torch.autograd.Function):

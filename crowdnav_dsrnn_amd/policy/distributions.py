@@ -1,7 +1,9 @@
-"""Action distribution of the Box action space (pytorchBaselines/a2c_ppo_acktr/distributions.py:36-94)."""
+"""Action distribution of the Box action space (pytorchBaselines/a2c_ppo_acktr/distributions.py:36-94), and this
+project's opt-in lattice head for the unicycle robot (LatticeCategorical: no reference counterpart)."""
 import torch
 import torch.nn as nn
 
+from .. import ops
 from .utils import AddBias, Linear, init
 
 
@@ -45,3 +47,43 @@ class DiagGaussian(nn.Module):
         action_mean = self.fc_mean(x)
         action_logstd = self.logstd(torch.zeros_like(action_mean))
         return FixedNormal(action_mean, action_logstd.exp())
+
+
+class FixedLattice:
+    """The lattice head's distribution over cn_dwa_predict's 64 unicycle actions for a batch of logits (B, 64)
+    (include/crowdnav.h, cn_lattice_*): actions are lattice points (B, 2); log_probs scores an action at its nearest
+    lattice point, so a continuous label (ORCA or the social force through the tracking law) is scored there too."""
+
+    def __init__(self, logits):
+        self.logits = logits
+
+    def mode(self):
+        with torch.no_grad():
+            return ops.lattice_act(self.logits, True)[0]
+
+    def sample(self):
+        with torch.no_grad():
+            return ops.lattice_act(self.logits, False)[0]
+
+    def evaluate(self, actions):
+        """(log_probs (B, 1), entropy (B,)) from one pass over the logits."""
+        return ops.lattice_evaluate(self.logits, actions)
+
+    def log_probs(self, actions):
+        return self.evaluate(actions)[0]
+
+    def entropy(self):
+        return ops.lattice_evaluate(self.logits, self.logits.new_zeros((self.logits.shape[0], 2)))[1]
+
+
+class LatticeCategorical(nn.Module):
+    """The opt-in action head of the unicycle robot (robot.action_head = 'lattice'): 64 logits from a linear layer
+    (orthogonal, gain 0.01, zero bias: a near-uniform policy at the start), one per candidate of the 8 x 8 lattice."""
+
+    def __init__(self, num_inputs):
+        super().__init__()
+        self.fc_logits = init(Linear(num_inputs, ops.LATTICE), nn.init.orthogonal_,
+                              lambda x: nn.init.constant_(x, 0), gain=0.01)
+
+    def forward(self, x):
+        return FixedLattice(self.fc_logits(x))

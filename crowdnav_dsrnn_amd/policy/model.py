@@ -5,18 +5,27 @@ API and return values as in the reference:
   get_value(inputs, rnn_hxs, masks) -> value (E,1)
   evaluate_actions(inputs, rnn_hxs, masks, action) -> value, log_prob, entropy, rnn_hxs
 `base.nenv` is writable (test.py:199) and `base.human_num` readable (evaluation.py:34).
+
+head (this project's opt-in; None reads base_kwargs.robot.action_head, default 'gaussian'): 'lattice' replaces the
+Gaussian by a 64-way categorical over the unicycle actions cn_dwa_predict chooses from (LatticeCategorical; state_dict
+keys dist.fc_logits.{weight,bias}). act() still returns a float32 (E, 2) action -- the lattice point -- so envs,
+storages, evaluate() and the captured rollout are the Gaussian head's; evaluate_actions scores an action at its nearest
+lattice point. Unicycle action spaces only (UnsupportedConfig otherwise).
 """
 import torch
 import torch.nn as nn
 
 from .. import ops
 from .convgru_model import ConvGRU
-from .distributions import DiagGaussian
+from ..config import UnsupportedConfig
+from .distributions import DiagGaussian, LatticeCategorical
 from .srnn_model import SRNN
 
 
 class Policy(nn.Module):
-    def __init__(self, obs_shape, action_space, base=None, base_kwargs=None):
+    HEADS = ("gaussian", "lattice")
+
+    def __init__(self, obs_shape, action_space, base=None, base_kwargs=None, head=None):
         super().__init__()
         if base == "srnn":
             self.base = SRNN(obs_shape, base_kwargs)
@@ -30,7 +39,19 @@ class Policy(nn.Module):
             raise NotImplementedError("base must be 'srnn' or 'convgru'")
         if action_space.__class__.__name__ != "Box":
             raise NotImplementedError("CrowdSimDict drives a Box(2,) action space")
-        self.dist = DiagGaussian(dist_in, action_space.shape[0])
+        if head is None:
+            head = getattr(getattr(base_kwargs, "robot", None), "action_head", "gaussian")
+        if head not in self.HEADS:
+            raise UnsupportedConfig("Policy: action head %r (one of %s)" % (head, ", ".join(self.HEADS)))
+        if head == "lattice":
+            kin = getattr(getattr(base_kwargs, "action_space", None), "kinematics", None)
+            if kin != "unicycle":
+                raise UnsupportedConfig("Policy: the 'lattice' action head is the unicycle robot's (its candidates are "
+                                        "(dv, dtheta) pairs); config.action_space.kinematics is %r" % (kin,))
+            self.dist = LatticeCategorical(dist_in)
+        else:
+            self.dist = DiagGaussian(dist_in, action_space.shape[0])
+        self.head = head
 
     @property
     def is_recurrent(self):
@@ -53,6 +74,11 @@ class Policy(nn.Module):
             action, action_log_probs = ops.gaussian_act(d.fc_mean(actor_features), d.logstd._bias.view(-1),
                                                         deterministic)
             return value, action, action_log_probs, rnn_hxs
+        if self.head == "lattice" and not torch.is_grad_enabled():
+            # sample / mode and its log-probability from one pass over the logits (ops.lattice_act: on CUDA one
+            # cn_lattice_act launch after fc_logits)
+            action, action_log_probs = ops.lattice_act(self.dist.fc_logits(actor_features), deterministic)
+            return value, action, action_log_probs, rnn_hxs
         dist = self.dist(actor_features)
         action = dist.mode() if deterministic else dist.sample()
         action_log_probs = dist.log_probs(action)
@@ -65,6 +91,9 @@ class Policy(nn.Module):
     def evaluate_actions(self, inputs, rnn_hxs, masks, action):
         value, actor_features, rnn_hxs = self.base(inputs, rnn_hxs, masks)
         dist = self.dist(actor_features)
+        if self.head == "lattice":   # both from one pass (ops.lattice_evaluate)
+            action_log_probs, entropy = dist.evaluate(action)
+            return value, action_log_probs, entropy.mean(), rnn_hxs
         action_log_probs = dist.log_probs(action)
         dist_entropy = dist.entropy().mean()
         return value, action_log_probs, dist_entropy, rnn_hxs

@@ -28,6 +28,8 @@
  *                   library GEMMs
  *   cn_gaussian_act ⟵ the act() tail of DiagGaussian / FixedNormal (distributions.py:36-94): sample or
  *                   mode and the summed log-probability
+ *   cn_lattice_act / cn_lattice_eval_fwd / cn_lattice_eval_bwd ⟵ (no reference counterpart) the opt-in lattice action
+ *                   head of the unicycle robot: a categorical policy over cn_dwa_predict's 64 candidate actions
  *   cn_gae         ⟵ RolloutStorage.compute_returns with use_gae (storage.py:132-177), one launch per rollout
  *   cn_orca_predict / cn_orca_predict_kd / cn_social_force_predict ⟵ the agent policy plugin
  *                   policy_factory[name](config).predict(JointState) (crowd_nav/policy/policy_factory.py:1-17)
@@ -361,6 +363,38 @@ int cn_gru_bias_reduce(void *stream, int64_t rows, int H, const float *part, flo
  * mean, eps, action: [E][A]; A <= 64. */
 int cn_gaussian_act(void *stream, int64_t E, int A, const float *mean, const float *logstd, const float *eps,
                     float *action, float *logp);
+
+/* The lattice action head of the unicycle robot (no reference counterpart: this project's definition; the policy's
+ * opt-in robot.action_head = 'lattice'): a categorical distribution over the 64 actions cn_dwa_predict chooses from.
+ * Candidate c = 8 a + b, a, b in 0..7, is the action ((float)((0.1 * (2 a - 7)) / 7), (float)((0.1 * (2 b - 7)) / 7)):
+ * cn_dwa_predict's numbering and values, bit for bit. For one row l of 64 float32 logits, in float32:
+ *   m = max l,  p_j = expf(l_j - m),  Z = sum p_j,  logp_j = (l_j - m) - logf(Z)
+ *   mode     the c of the largest logit, the lowest c among equal ones
+ *   sample   with u in [0, 1) from the caller and S_c the inclusive prefix sums of p: the smallest c with
+ *            S_c > u * S_63; if rounding leaves none, the highest c with p_c > 0. A candidate with p_c == 0 is never
+ *            chosen
+ *   index of an action (x, y): a = clamp(rintf((x * 70 + 7) * 0.5), 0, 7) and b from y the same way: the nearest
+ *            lattice point, exact for every lattice point (cn_dwa_predict's labels among them)
+ *   entropy  H = -sum over p_j > 0 of (p_j / Z) * logp_j
+ *   backward with upstream g_lp, g_H and q = p / Z:  dl_j = g_lp * (delta_jc - q_j) - g_H * q_j * (logp_j + H), the
+ *            terms with q_j == 0 being 0
+ * The order of the 64-term sums is the kernels' own (xor butterflies for Z and H, a shuffle scan for S), so a result
+ * agrees with another evaluation of the definition to float32 rounding of such a sum, not bit for bit.
+ * cn_lattice_act: the act() tail for E rows in one launch: logits [E][64], u [E] or NULL (NULL: the mode);
+ *   out action [E][2] (the lattice point of c), logp [E] (logp_c), choice [E] int32 (c; may be NULL).
+ * cn_lattice_eval_fwd: evaluate_actions for B rows: actions [B][2] -> logp [B] of the action's index, entropy [B],
+ *   choice [B] (that index, for the backward).
+ * cn_lattice_eval_bwd: dlogits [B][64] from the same logits, the forward's choice, g_logp [B] and g_entropy [B]
+ *   (nothing but the logits is kept between the two: the softmax is recomputed).
+ * One 64-lane wavefront per row, a lane per candidate, 4 rows per workgroup; no LDS, scratch, atomics or memset.
+ * Device pointers, stream-ordered. CN_EINVAL, before any launch: a row count <= 0 or above 4 * (2^31 - 1), or a NULL
+ * pointer other than u / cn_lattice_act's choice. */
+int cn_lattice_act(void *stream, int64_t E, const float *logits, const float *u, float *action, float *logp,
+                   int32_t *choice);
+int cn_lattice_eval_fwd(void *stream, int64_t B, const float *logits, const float *actions, float *logp,
+                        float *entropy, int32_t *choice);
+int cn_lattice_eval_bwd(void *stream, int64_t B, const float *logits, const int32_t *choice, const float *g_logp,
+                        const float *g_entropy, float *dlogits);
 
 /* One step of up to two GRUs of the same H in one launch (the act() path's temporal and spatial edge RNNs,
  * srnn_model.py:455-460 at T = 1): cn_gru_fwd_fused per GRU, with the input projection in the kernel when

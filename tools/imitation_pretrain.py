@@ -20,6 +20,9 @@ goes through the tracking law on the device and the labels are the unicycle acti
 [-0.1, 0.1]. There the noise is given with --sigma, ABSOLUTE in those action units (0.1 is the whole range; --sigma-frac
 is not read). --expert dwa (unicycle only) clones the dynamic-window controller made for that robot
 (config.robot.scripted_dwa at policy_factory.DWA_DEFAULTS) instead of ORCA or the social force behind the tracking law.
+--head lattice (unicycle only) gives every policy of the run the 64-way categorical head over that controller's grid
+of actions (config.robot.action_head; policy.LatticeCategorical) in place of the Gaussian: dwa's labels are its
+candidates themselves, a continuous label (ORCA or the social force through the law) is scored at its nearest one.
 --fov F sets robot.FOV (in units of pi; the default config's is 2.0, the full circle) for training and evaluation
 alike; --visible-masks (DSRNN only) also runs all of it on envs with sim.visible_masks and sim.visible_masks_scripted:
 the rollouts record the 'visible_masks' rows (cn_rollout_masked) and the policy attends to the visible humans only.
@@ -27,7 +30,7 @@ Needs a GPU.
 
 Usage: python tools/imitation_pretrain.py [--policy srnn|convgru] [--expert orca] [--updates 3000] [--envs 1024] [--steps 32] [--epochs 1]
            [--mini-batch 2] [--lr 1e-3] [--value-coef 0.5] [--sigma-frac 0 0.1 0.3] [--humans 5] [--seed 0]
-           [--human-nums 5 10 [--unseen 7]] [--kinematics holonomic|unicycle [--sigma 0 0.03]]
+           [--human-nums 5 10 [--unseen 7]] [--kinematics holonomic|unicycle [--sigma 0 0.03] [--head gaussian|lattice]]
            [--fov F] [--visible-masks] [--eval-envs 100] [--test-size 500] [--log-every K] [--out policy.pt]
            [--json FILE]
 """
@@ -76,6 +79,9 @@ def main():
     ap.add_argument("--sigma", type=float, nargs="+", default=[0.0, 0.03],
                     help="with --kinematics unicycle: the noise half-widths, absolute, in action units (0.1 is the "
                          "whole range of an action component); replaces --sigma-frac there")
+    ap.add_argument("--head", default="gaussian", choices=Policy.HEADS,
+                    help="the policy's action head; lattice (with --kinematics unicycle): a categorical over the 64 "
+                         "unicycle actions the dwa expert chooses from")
     ap.add_argument("--humans", type=int, default=5)
     ap.add_argument("--human-nums", type=int, nargs="+", default=None,
                     help="clone on an env of varying human count; every row per density")
@@ -104,6 +110,9 @@ def main():
     c.action_space.kinematics = args.kinematics
     uni = args.kinematics == "unicycle"
     c.robot.scripted_unicycle = uni
+    if args.head == "lattice" and not uni:
+        raise SystemExit("imitation_pretrain: --head lattice needs --kinematics unicycle")
+    c.robot.action_head = args.head
     if args.fov is not None:
         c.robot.FOV = args.fov
     if args.visible_masks:
@@ -132,7 +141,7 @@ def main():
         ct.sim.human_nums_scripted = True
 
     def emit(row):
-        row = dict(row, fov=float(c.robot.FOV), visible_masks=bool(args.visible_masks))
+        row = dict(row, fov=float(c.robot.FOV), visible_masks=bool(args.visible_masks), head=args.head)
         lines.append(json.dumps(row))
         print(lines[-1], flush=True)
 
