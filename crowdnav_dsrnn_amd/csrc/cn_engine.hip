@@ -66,12 +66,20 @@ __device__ unsigned long long cn_stamp_x[8192 * 4];
         if ((k) == 0) { cn_stamp_x[blockIdx.x * 4] = CN_GETREG32(20); cn_stamp_x[blockIdx.x * 4 + 1] = CN_GETREG32(4); } \
         cn_stamp_x[blockIdx.x * 4 + 2 + (k)] = __builtin_amdgcn_s_memtime(); \
         cn_stamp_r[blockIdx.x * 2 + (k)] = __builtin_amdgcn_s_memrealtime(); } } while (0)
-#define STAMP_A(k) do { const unsigned sb_ = (unsigned)sb; if (threadIdx.x == 0 && sb_ < 4096) cn_stamp_a[sb_ * CN_NSTAMP + (k)] = clock64(); } while (0)
-#define STAMP_B(w, k) do { if ((threadIdx.x & 63) == 0 && (w) < 8192) cn_stamp_b[(w) * CN_NSTAMP + (k)] = clock64(); } while (0)
+// -DCN_STAMP_STEP=k: the stamps of cn_step_kernel's workgroups and of their phase-5 items record step k of a
+// multi-step launch instead of its last step (which alone stores the outputs and computes the info row); the
+// items of the other steps pass -1 for their env (STAMP_B, WRng::edbg)
+#ifndef CN_STAMP_STEP
+#define CN_STAMP_STEP -1
+#endif
+#define CN_STAMP_ON (CN_STAMP_STEP < 0 || step == CN_STAMP_STEP)
+#define STAMP_A(k) do { const unsigned sb_ = (unsigned)sb; if (threadIdx.x == 0 && sb_ < 4096 && CN_STAMP_ON) cn_stamp_a[sb_ * CN_NSTAMP + (k)] = clock64(); } while (0)
+#define STAMP_B(w, k) do { if ((threadIdx.x & 63) == 0 && (unsigned long long)(w) < 8192) cn_stamp_b[(w) * CN_NSTAMP + (k)] = clock64(); } while (0)
 // stamp k by thread t (a lane of another wave than thread 0's)
-#define STAMP_T(k, t) do { const unsigned sb_ = (unsigned)sb; if (threadIdx.x == (t) && sb_ < 4096) cn_stamp_a[sb_ * CN_NSTAMP + (k)] = clock64(); } while (0)
+#define STAMP_T(k, t) do { const unsigned sb_ = (unsigned)sb; if (threadIdx.x == (t) && sb_ < 4096 && CN_STAMP_ON) cn_stamp_a[sb_ * CN_NSTAMP + (k)] = clock64(); } while (0)
 #else
 #define CN_LABEL_ROT 0
+#define CN_STAMP_ON true
 #define STAMP_T(k, t) do { } while (0)
 #define STAMP_A(k) do { } while (0)
 #define STAMP_B(w, k) do { } while (0)
@@ -156,6 +164,12 @@ struct StepPlan {
 // of DESIGN.md §4)
 #define CN_SEQ_INFO_LAST 1
 #endif
+#ifndef CN_SEQ_GOAL_EARLY
+// multi-step launches of plain quad-path engines (SEQ && !ROBOT && !KD && !MIX) run the goal changes of the envs
+// that go on with their episode on waves 2 and 3 from phase 2's closing barrier on, beside the state stores of waves
+// 0 and 1, and phase 5 serves the resets alone (0: all of it in phase 5; the A/B of DESIGN.md §4)
+#define CN_SEQ_GOAL_EARLY 1
+#endif
 #define CN_GRID 16
 #define CN_GRID_LDS (96 * 8 + CN_GRID * CN_GRID * 4 + 4 * 8 + 4 * 8)   // + spawn DiscGrid: agent table, masks, cover, box
 
@@ -225,6 +239,17 @@ __host__ __device__ inline StepPlan cn_step_plan(int N, int robot_visible)
     p.o_app = p.total;
     p.total = cn_align16(p.total + 2 * p.EPB * 4);
     return p;
+}
+
+// CN_SEQ_GOAL_EARLY's condition on a quad-path plan: waves 2 and 3 run goal items in their RNG regions while waves
+// 0 and 1 store the state, so the two regions must lie clear of what the store block reads: human_post's staged
+// values (o_hst; everything else it reads lies below o_lines). It holds for every quad-path plan (N = 1..10 with
+// and without robot_visible: the staged values end at most at o_lines + 19,200, region 2 starts at o_lines +
+// 19,712); cn_create refuses an engine whose plan breaks it.
+__host__ __device__ inline bool cn_goal_early_ok(const StepPlan &p)
+{
+    const int lo = p.o_lines + 2 * p.rng_stride, hi = p.o_lines + 4 * p.rng_stride;
+    return !p.kd && p.rng_waves == 4 && (p.o_hst + 7 * p.H * 8 <= lo || p.o_hst >= hi);
 }
 
 // kernel-A LDS views
@@ -2251,14 +2276,14 @@ __device__ __forceinline__ void goal_changes(const cn_config &c, const cn_state_
     uint32_t ovf = S.overflow[e];
     const int sc = S.scenario[e];
     wsync();
-    STAMP_B(e, 1);
+    STAMP_B(m.edbg, 1);
     int dbg0 = 0, dbg1 = 0;
-    if (rgoal) dbg0 = goal_pass<0, GRID>(c, en, m, ovf, sc, sp, e);
-    STAMP_B(e, 2);
-    if (egoal) dbg1 = goal_pass<1, GRID>(c, en, m, ovf, sc, sp, e);
-    STAMP_B(e, 3);
+    if (rgoal) dbg0 = goal_pass<0, GRID>(c, en, m, ovf, sc, sp, m.edbg);
+    STAMP_B(m.edbg, 2);
+    if (egoal) dbg1 = goal_pass<1, GRID>(c, en, m, ovf, sc, sp, m.edbg);
+    STAMP_B(m.edbg, 3);
 #ifdef CN_STAMPS
-    if (lane == 0 && e < 8192) { cn_stamp_b[e * CN_NSTAMP + 6] = dbg0; cn_stamp_b[e * CN_NSTAMP + 7] = dbg1; }
+    if (lane == 0 && (unsigned long long)m.edbg < 8192) { cn_stamp_b[m.edbg * CN_NSTAMP + 6] = dbg0; cn_stamp_b[m.edbg * CN_NSTAMP + 7] = dbg1; }
 #endif
     (void)dbg0; (void)dbg1;
     // numpy twists lazily: a stream that consumed exactly the 624 words is (old key, pos 624)
@@ -2271,7 +2296,7 @@ __device__ __forceinline__ void goal_changes(const cn_config &c, const cn_state_
         for (int k = lane; k < CN_MT_N; k += 64) S.mt[e * CN_MT_N + k] = m.blk(in1 ? 1 : 0)[k];
     if (lane == 0) { S.mt_pos[e] = in1 ? m.p - CN_MT_N : m.p; S.overflow[e] = ovf; }
     wsync();
-    STAMP_B(e, 4);
+    STAMP_B(m.edbg, 4);
 }
 
 // Auto-reset of env e (VecEnv worker, shmem_vec_env.py:164-168 -> CrowdSimDict.reset): copy the pending
@@ -2854,6 +2879,9 @@ __global__ void __launch_bounds__(CN_BLK, 3) cn_step_kernel(StepArgs g, cn_confi
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const OutView ov = MIX ? g.ov : OutView{nullptr, c.human_num};
+    // the goal changes beside the state stores (CN_SEQ_GOAL_EARLY): these instantiations alone, the others compile
+    // as without it
+    constexpr bool GOAL_EARLY = CN_SEQ_GOAL_EARLY && SEQ && !ROBOT && !KD && !MIX;
     // this launch's spawn / parked-spawn lists (triple-buffered: launch t appends to t % 3, reads (t - 1) % 3,
     // zeroes (t + 1) % 3) and id, from the device-side step counter
     const uint32_t ns = DEVSEQ ? g.ctl[CN_CTL_NSTEP] : 0u;
@@ -3920,23 +3948,91 @@ __global__ void __launch_bounds__(CN_BLK, 3) cn_step_kernel(StepArgs g, cn_confi
             }
         }
         // random numbers needed? (crowd_sim_dict.py:260-269, shmem_vec_env.py:166-167)
-        const bool done = sl.rflag[EPB + re] != 0;
-        const bool rgoal = c.random_goal_changing && np_mod(gt, 5.0) == 0.0;
-        const bool egoal = c.end_goal_changing && endg;
-        sl.rflag[EPB + re] = (done ? 1u : 0u) | (rgoal ? 2u : 0u) | (egoal ? 4u : 0u);
+        // GOAL_EARLY: the word stays "done" (waves 2 and 3 are reading it for their goal items; phase 5 serves the
+        // done envs alone)
+        if constexpr (!GOAL_EARLY) {
+            const bool done = sl.rflag[EPB + re] != 0;
+            const bool rgoal = c.random_goal_changing && np_mod(gt, 5.0) == 0.0;
+            const bool egoal = c.end_goal_changing && endg;
+            sl.rflag[EPB + re] = (done ? 1u : 0u) | (rgoal ? 2u : 0u) | (egoal ? 4u : 0u);
+        }
     }
     if ((tid >> 6) == 1) {   // the env lanes' wave: one mask of the envs with RNG work, for phase 5's item split
-        const uint64_t bm = __ballot(rl && (sl.rflag[EPB + re] & 7u) != 0u);
+        const uint64_t bm = __ballot(rl && (GOAL_EARLY ? sl.rflag[EPB + re] : sl.rflag[EPB + re] & 7u) != 0u);
         if (tid == 64) { sl.rflag[3 * EPB] = (uint32_t)bm; sl.rflag[3 * EPB + 1] = (uint32_t)(bm >> 32); }
     }
+    if constexpr (GOAL_EARLY) {
+        // ---- waves 2 and 3, idle until the barrier below: the goal changes of the envs that go on with their episode,
+        // beside the stores above. What decides them is final since phase 2's closing barrier: done (the ladder's
+        // word, which the env lanes leave as it is), gtime as the ladder advanced it, the humans' LF_ENDGOAL. An item
+        // reads the post-move positions, the humans' goals / radii / v_pref / headings and the robot's R_NX, R_NY,
+        // R_GX, R_GY, R_RAD and the env's stream; it writes the goals, radii, v_pref (LDS and state) and the stream:
+        // none of these is read or written by the stores above. Both waves work out the same list of envs and take
+        // every other item of it, each in its own RNG region (2 and 3: over phase 2's neighbour distances and
+        // linearProgram3 tables, clear of the staged values wave 0 is reading, cn_goal_early_ok). No wave waits
+        // for another one but at the barriers.
+        if ((tid >> 6) >= 2) {
+            const int w = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+            bool gneed = false, grand = false;
+            if (lane < nenv_here) {
+                bool endg = false;
+                for (int k = 0; k < N; ++k) endg |= (sl.eg[lane * N + k] & LF_ENDGOAL) != 0;
+                grand = c.random_goal_changing && np_mod(RF(sl, R_GT, lane, EPB), 5.0) == 0.0;
+                gneed = sl.rflag[EPB + lane] == 0u && (grand || (c.end_goal_changing && endg));
+            }
+            const uint64_t gm = __ballot(gneed), grm = __ballot(grand);
+            uint64_t mym = 0;
+            {
+                int jj = 0;
+                for (uint64_t mm = gm; mm; mm &= mm - 1, ++jj)
+                    if ((jj & 1) == w - 2) mym |= mm & (~mm + 1);
+            }
+            if (mym) {
+                char *wb = smem + P.o_lines + w * P.rng_stride;
+                WRng m;
+                m.w = (uint32_t *)wb; m.off = 0; m.lane = lane; m.phx = PHX; m.edbg = -1;
+                m.grid = P.rng_stride > CN_PEND_LDS ? wb + CN_PEND_LDS : nullptr;
+                m.sl = (double *)(wb + 2 * CN_MT_N * 4 + 7 * 32 * 8);
+                double *hb = (double *)(wb + 2 * CN_MT_N * 4);
+                for (uint64_t mm = mym; mm; mm &= mm - 1) {
+                    const int q = __builtin_ctzll(mm);
+                    // (the kernel arguments from the kernarg segment, as in phase 5's loop below and for its reasons)
+                    typedef const __attribute__((address_space(4))) char *KArgs;
+                    typedef const __attribute__((address_space(4))) StepArgs *GArgs;
+                    typedef const __attribute__((address_space(4))) cn_config *CArgs;
+                    KArgs ks = (KArgs)__builtin_amdgcn_kernarg_segment_ptr();
+                    asm volatile("" : "+s"(ks));
+                    GArgs gq = (GArgs)ks;
+                    CArgs cq = (CArgs)(ks + ((sizeof(StepArgs) + alignof(cn_config) - 1) & ~(alignof(cn_config) - 1)));
+                    const StepArgs &G = *(const StepArgs *)gq;
+                    const cn_config &C = *(const cn_config *)cq;
+                    const int64_t e = e0 + q;
+                    const int64_t se = CN_STAMP_ON ? e : -1;
+                    (void)se;
+                    STAMP_B(se, 0);
+                    Env1 en;
+                    const int b = q * N;
+                    en.hpx = sl.npx + b; en.hpy = sl.npy + b; en.hgx = &HF(sl, H_GX, b);
+                    en.hgy = &HF(sl, H_GY, b); en.hr = &HF(sl, H_R, b); en.hvp = &HF(sl, H_VP, b); en.hth = &HF(sl, H_TH, b);
+                    en.rpx = RF(sl, R_NX, q, EPB); en.rpy = RF(sl, R_NY, q, EPB);
+                    en.rgx = RF(sl, R_GX, q, EPB); en.rgy = RF(sl, R_GY, q, EPB); en.rr = RF(sl, R_RAD, q, EPB);
+                    m.edbg = se;
+                    goal_changes<KD>(C, G.s, e, en, m, ((grm >> q) & 1ull) != 0, C.end_goal_changing != 0, hb);
+                }
+            }
+        }
+    }
+    STAMP_A(4);        // waves 0 and 1 at the barrier: their stores are issued (the barrier waits for them)
+    STAMP_T(11, 64);
     __syncthreads();
-    STAMP_A(4);
     STAMP_A(5);
 
     // ---- phase 5: this workgroup's RNG work, one wave per env needing it --------------------------
     // Done envs auto-reset (VecEnv worker, shmem_vec_env.py:164-168) from the pending spawn drawn by an
     // earlier launch (reset_env: two slots per env, consumed only when an earlier launch completed the entry);
     // after cn_reset / cn_set_state, while this launch's spawn waves draw every env's entries, they draw inline.
+    // GOAL_EARLY: the done envs alone (the mask holds no other), the goal changes having run beside the stores.
+    bool rng_any = true;   // GOAL_EARLY: some env of the workgroup resets in this step (workgroup-uniform)
     {
         // the wave index is wave-uniform: readfirstlane keeps it (and every LDS pointer derived from it) in
         // SGPRs -- as a VGPR value the RNG block's preheader spilled it to scratch (HBM writes every launch)
@@ -3962,6 +4058,7 @@ __global__ void __launch_bounds__(CN_BLK, 3) cn_step_kernel(StepArgs g, cn_confi
             for (uint64_t mm = rm; mm; mm &= mm - 1, ++jj)
                 if (jj % nw == w) mym |= mm & (~mm + 1);
         }
+        if constexpr (GOAL_EARLY) rng_any = rm != 0;
         STAMP_T(22, 0);
         if (mym) {
         for (uint64_t mm = mym; mm; mm &= mm - 1) {
@@ -3987,9 +4084,11 @@ __global__ void __launch_bounds__(CN_BLK, 3) cn_step_kernel(StepArgs g, cn_confi
                 o.robot_node += orw_o * 7; o.temporal += orw_o * 2; o.spatial += orw_o * ov.NS * 2;
             }
             if (SEQ && !emit_obs) o.robot_node = nullptr;   // (write_reset<OBS_OPT>: no first observation)
-            const uint32_t need = sl.rflag[EPB + q] & 7u;
+            const uint32_t need = GOAL_EARLY ? 1u : sl.rflag[EPB + q] & 7u;
             const int64_t e = e0 + q;
-            STAMP_B(e, 0);
+            const int64_t se = CN_STAMP_ON ? e : -1;   // (the stamps' env: this step's items only)
+            (void)se;
+            STAMP_B(se, 0);
             Env1 en;
             if (need & 1u) {
                 en.hpx = hb; en.hpy = hb + 32; en.hgx = hb + 64; en.hgy = hb + 96; en.hr = hb + 128; en.hvp = hb + 160;
@@ -4030,7 +4129,7 @@ __global__ void __launch_bounds__(CN_BLK, 3) cn_step_kernel(StepArgs g, cn_confi
                         q[2] = (uint32_t)(uint64_t)ccn; q[3] = (uint32_t)((uint64_t)ccn >> 32);
                     }
                 }
-                STAMP_B(e, 5);
+                STAMP_B(se, 5);
             } else {
                 const int b = q * N;
                 en.hpx = sl.npx + b; en.hpy = sl.npy + b; en.hgx = &HF(sl, H_GX, b);
@@ -4039,7 +4138,7 @@ __global__ void __launch_bounds__(CN_BLK, 3) cn_step_kernel(StepArgs g, cn_confi
                 en.rgx = RF(sl, R_GX, q, EPB); en.rgy = RF(sl, R_GY, q, EPB); en.rr = RF(sl, R_RAD, q, EPB);
                 // update_human_goal checks every human AFTER the random changes (a new random goal may
                 // land within reach of its own human), so it runs whenever end goal changing is on
-                m.edbg = e;
+                m.edbg = se;
                 goal_changes<KD>(C, G.s, e, en, m, (need & 2u) != 0, C.end_goal_changing != 0, hb);
             }
         }
@@ -4049,7 +4148,12 @@ __global__ void __launch_bounds__(CN_BLK, 3) cn_step_kernel(StepArgs g, cn_confi
     }
     // the next step's phase 0 reads the state (and the RNG streams) this step's resets and goal changes wrote
     // through other waves, and rewrites the LDS their RNG regions and agent tables use
-    if constexpr (SEQ) __syncthreads();
+    // GOAL_EARLY: without a reset in this step (the mask every wave read after the barrier above) phase 5 was empty and
+    // that barrier, which every wave passed after its last goal item and its last store, already is this one
+    if constexpr (SEQ) { if (!GOAL_EARLY || rng_any) __syncthreads(); }
+#if defined(CN_STAMPS) && CN_STAMP_STEP >= 0
+    if constexpr (SEQ) STAMP_A(6);   // the chosen step's end (the stamp behind the loop is the launch's)
+#endif
     if constexpr (REC) {
         if (step == g.nsteps - 1) {
             const RolloutRows rr = *(const RolloutRows *)(g.pend.stats + (CN_ROWS_W - 8));

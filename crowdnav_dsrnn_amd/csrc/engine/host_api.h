@@ -185,6 +185,12 @@ int cn_create(const cn_config *cfg, int device, cn_engine **out)
         return set_err(CN_EHIP, "hipMemcpyToSymbol failed");
     }
     if (g->a_lds > 160 * 1024) { cn_destroy(g); return set_err(CN_EUNSUPPORTED, "LDS plan exceeds 160 KiB"); }
+#if CN_SEQ_GOAL_EARLY
+    if (!g->plan.kd && !cn_goal_early_ok(g->plan)) {   // (no plan of today's: the multi-step kernels rely on it)
+        cn_destroy(g);
+        return set_err(CN_EUNSUPPORTED, "LDS plan: the RNG regions of waves 2 and 3 overlap the staged human state");
+    }
+#endif
     if (g->a_lds > 64 * 1024)
         for (const StepKernelEntry &k : step_kernels)
             (void)hipFuncSetAttribute((const void *)k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, g->a_lds);

@@ -76,7 +76,7 @@ def run(variant, E=4096, N=10, steps=300):
     d = np.diff(A[:, :7], axis=1)
     print("[%s] kernel A avg %.1f us, kernel B avg %.1f us over %d steps" % (variant, ta.value * 1e3 / n.value,
                                                                           tb.value * 1e3 / n.value, n.value))
-    names = ["load", "visibility", "policy+reward terms", "reward ladder", "kinematics+obs", "rng work (phase 5)"]
+    names = ["load", "visibility", "policy+reward terms", "stores issued (wave 0)", "wave 0 at the barrier", "rng work (phase 5)"]
     tot = (A[:, 6] - A[:, 0])
     print("  kernel A cycles per workgroup (last step): total median %d max %d" % (np.median(tot), tot.max()))
     for k, nm in enumerate(names):
@@ -136,7 +136,7 @@ def run(variant, E=4096, N=10, steps=300):
                                               for k in last))
     B = b.reshape(-1, 24).astype(np.int64)[:E]
     t0 = A[:, 0].min()
-    sub = [("p0 human loads", A[:, 12] - A[:, 0]), ("p0 env loads", A[:, 13] - A[:, 12]), ("p0 clip", A[:, 10] - A[:, 13]), ("p0 robot VR", A[:, 11] - A[:, 10]), ("p0 barrier", A[:, 1] - A[:, 11]),
+    sub = [("p0 human loads", A[:, 12] - A[:, 0]), ("p0 env loads", A[:, 13] - A[:, 12]), ("p0 clip", A[:, 10] - A[:, 13]), ("p0 barrier", A[:, 1] - A[:, 10]),
            ("lines+sort", A[:, 7] - A[:, 2]), ("LP2", A[:, 8] - A[:, 7]), ("LP3", A[:, 9] - A[:, 8]), ("VR+terms", A[:, 3] - A[:, 9])]
     if (A[:, 14] > A[:, 2]).all():
         sub += [("kd: table", A[:, 15] - A[:, 2]), ("kd: walk", A[:, 14] - A[:, 15]),
@@ -215,15 +215,17 @@ def run(variant, E=4096, N=10, steps=300):
     eng.close()
 
 
-def run_xcd(rot=0, launches=60, warm=130, chunk=32, E=4096, N=10):
+def run_xcd(rot=0, step=None, launches=60, warm=130, chunk=32, E=4096, N=10):
     """Where the step workgroups of C2's multi-step launches run and how long they take: per workgroup label
     (step workgroup index & 7: the workgroups that share an XCD under round-robin dispatch), per XCC id, and per
     place in their CU's residency order.
 
-        CN_LIB_PATH=<stamps build> python tools/probe_stamps.py xcd [rot]
+        CN_LIB_PATH=<stamps build> python tools/probe_stamps.py xcd [rot [step]]
 
     rot: the CN_LABEL_ROT the library was built with (the labels' env ranges in the order of (label + rot) & 7), so
     that a slowness that stays with the label can be told from one that moves with the env range.
+    step: the CN_STAMP_STEP the library was built with (the step of a launch its phase stamps record; default: the
+    launch's last step, the one that stores the outputs), which adds step_detail's report of that step.
     Durations on the device-wide 100 MHz clock (s_memrealtime); a workgroup's clock is its shader-clock span
     (s_memtime) over that."""
     c = clone_config(Config())
@@ -333,17 +335,91 @@ def run_xcd(rot=0, launches=60, warm=130, chunk=32, E=4096, N=10):
     A = a.reshape(-1, 24)[:nstep].astype(np.int64)
     d = np.diff(A[:, :7], axis=1)
     tot = A[:, 6] - A[:, 0]
-    names = ["load", "visibility", "policy+reward terms", "kinematics+stores", "-", "rng work (phase 5)"]
-    print("  last step of the last launch, cycles per workgroup: total median %d max %d" % (np.median(tot), tot.max()))
+    names = ["load", "visibility", "policy+reward terms", "stores issued (wave 0)", "wave 0 at the barrier", "rng work (phase 5)"]
+    which = "last step" if step is None else "step %d" % step
+    print("  %s of the last launch, cycles per workgroup: total median %d max %d" % (which, np.median(tot), tot.max()))
     for k, nm in enumerate(names):
-        if nm != "-":
-            print("    %-26s median %8d  max %8d" % (nm, np.median(d[:, k]), d[:, k].max()))
+        print("    %-26s median %8d  max %8d" % (nm, np.median(d[:, k]), d[:, k].max()))
+    if step is not None:
+        step_detail(A, b.reshape(-1, 24).astype(np.int64)[:E], E, epb, kern.mean() / allm)
     eng.close()
+
+
+def step_detail(A, B, E, epb, launch_over_wg):
+    """One step of a multi-step launch (a -DCN_STAMP_STEP=k build): the per-wave ends, the window between phase 2's
+    closing barrier and the next one, the step's goal items and resets per workgroup, and what the chain would
+    save if the goal items ran on waves 2 and 3 inside that window."""
+    nstep = len(A)
+    per = [("p0 wave1 env load+clip", A[:, 16] - A[:, 0]), ("p1 wave0 visibility", A[:, 19] - A[:, 1]),
+           ("p1 wave1 reward terms", A[:, 17] - A[:, 1]), ("p1 wave2 robot terms", A[:, 18] - A[:, 1]),
+           ("p2 wave1 quads done", A[:, 21] - A[:, 2]), ("p2 wave1 +ladder", A[:, 20] - A[:, 2]),
+           ("window: wave 0 stores issued", A[:, 4] - A[:, 3]), ("window: wave 1 at the barrier", A[:, 11] - A[:, 3]),
+           ("window: barrier to barrier", A[:, 5] - A[:, 3])]
+    for nm, v in per:
+        print("      %-30s median %8d  max %8d" % (nm, np.median(v), v.max()))
+    tot = A[:, 6] - A[:, 0]
+    window = A[:, 5] - A[:, 3]
+    p5 = A[:, 6] - A[:, 5]
+    xq, xr = nstep >> 3, nstep & 7
+    k = np.arange(nstep)
+    blk = (k & 7) * xq + np.minimum(k & 7, xr) + (k >> 3)   # the kernel's XCD-aware env placement
+    wg_of_env = np.empty(E, int)
+    for kk in range(nstep):
+        wg_of_env[blk[kk] * epb:min((blk[kk] + 1) * epb, E)] = kk
+    a0, a6 = A[wg_of_env, 0], A[wg_of_env, 6]
+    cur = (B[:, 0] >= a0) & (B[:, 0] <= a6)            # items of this step (a workgroup's stamps share its XCD's clock)
+    is_res = cur & (B[:, 5] >= B[:, 0]) & (B[:, 5] <= a6)
+    is_goal = cur & ~is_res & (B[:, 4] >= B[:, 0])
+    ng = np.bincount(wg_of_env[is_goal], minlength=nstep)
+    nr = np.bincount(wg_of_env[is_res], minlength=nstep)
+    print("  step items: %d goal items, %d resets; workgroups with >= 1 goal item %.3f, with >= 3 %.3f, with a reset %.3f, "
+          "with neither %.3f" % (is_goal.sum(), is_res.sum(), (ng >= 1).mean(), (ng >= 3).mean(), (nr >= 1).mean(),
+                                 ((ng == 0) & (nr == 0)).mean()))
+    gdur = B[:, 4] - B[:, 0]
+    if is_goal.any():
+        gg = np.diff(B[is_goal][:, :5], axis=1)
+        v = gdur[is_goal]
+        print("  goal items: mt load %d  random %d  end %d  write %d (median); total median %d p90 %d max %d" % (
+            *np.median(gg, axis=0), np.median(v), np.percentile(v, 90), v.max()))
+        # an item that starts before the window's closing barrier (an early item): still running at that barrier?
+        early = is_goal & (B[:, 0] < A[wg_of_env, 5])
+        if early.any():
+            late = early & (B[:, 4] > A[wg_of_env, 5])
+            over = (B[:, 4] - A[wg_of_env, 5])[late]
+            print("  early goal items: %d, still running when waves 0 / 1 passed the barrier: %d (outlasting it by median %d "
+                  "p90 %d max %d cycles)" % (early.sum(), late.sum(), np.median(over) if len(over) else 0,
+                                             np.percentile(over, 90) if len(over) else 0, over.max() if len(over) else 0))
+    if is_res.any():
+        v = (B[:, 5] - B[:, 0])[is_res]
+        print("  resets: cycles median %d p90 %d max %d" % (np.median(v), np.percentile(v, 90), v.max()))
+    for nm, sel in (("no item", (ng == 0) & (nr == 0)), ("goal items only", (ng > 0) & (nr == 0)), ("a reset", nr > 0)):
+        if sel.any():
+            print("    workgroups with %-16s %4d: step median %6d  window %6d  phase 5 median %6d max %6d" % (
+                nm + ":", sel.sum(), np.median(tot[sel]), np.median(window[sel]), np.median(p5[sel]), p5[sel].max()))
+    # prediction: a workgroup without a reset runs its goal items on waves 2 and 3 from the window's start, item j on
+    # wave 2 + (j & 1), in env order; what outlasts the window stays on the chain. (a) the issue's formula,
+    # min(item, window) with item = the workgroup's phase 5 today; (b) with the two waves' serial chains.
+    save_a = np.zeros(nstep)
+    save_b = np.zeros(nstep)
+    left_b = np.zeros(nstep)
+    for kk in np.nonzero((ng > 0) & (nr == 0))[0]:
+        envs = np.nonzero(is_goal & (wg_of_env == kk))[0]
+        ch = [gdur[envs[0::2]].sum(), gdur[envs[1::2]].sum()]
+        save_a[kk] = min(p5[kk], window[kk])
+        left_b[kk] = max(0, max(ch) - window[kk])
+        save_b[kk] = p5[kk] - left_b[kk]
+    sel = (ng > 0) & (nr == 0)
+    print("  predicted saving of goal items inside the window (workgroups without a reset), share of the sum of step "
+          "durations: (a) min(phase 5, window) %.4f; (b) phase 5 - what the two waves' chains outlast the window by "
+          "%.4f (remainder median %d p90 %d max %d over those workgroups)" % (
+              save_a.sum() / tot.sum(), save_b.sum() / tot.sum(), np.median(left_b[sel]) if sel.any() else 0,
+              np.percentile(left_b[sel], 90) if sel.any() else 0, left_b.max()))
+    print("  launch / mean step workgroup %.3f" % launch_over_wg)
 
 
 if __name__ == "__main__":
     if sys.argv[1:2] == ["xcd"]:
-        run_xcd(int(sys.argv[2]) if len(sys.argv) > 2 else 0)
+        run_xcd(int(sys.argv[2]) if len(sys.argv) > 2 else 0, int(sys.argv[3]) if len(sys.argv) > 3 else None)
         sys.exit(0)
     for v in (sys.argv[1:] or ["c2", "nogoal", "sf"]):
         run(v)
