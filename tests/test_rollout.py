@@ -216,14 +216,14 @@ def _rollout(c, E, name, T, chunk=None, budget=None, graph=False, warm=0, **kw):
 @pytest.mark.parametrize("N", [1, 5, 9])
 @pytest.mark.parametrize("rng", ["mt19937", "philox"])
 @pytest.mark.parametrize("name", NAMES)
-def test_gpu_fused_rollout_equals_pairs(name, rng, N, chunk):
+def test_gpu_fused_rollout_equals_pairs(name, rng, N, chunk, visible=False):
     """E = 13 leaves every workgroup partial (16, 12, 7 envs per workgroup at N = 1, 5, 9); T = 37 = the single
     first step after cn_reset (a pair) + a full default chunk of 32 + a remainder of 4. time_limit 2 at time_step
     0.25: every env times out every few steps, so it auto-resets several times inside a launch and the
-    controller acts on the new episode in the same launch."""
+    controller acts on the new episode in the same launch. `visible` (tests/test_step_matrix.py): robot.visible."""
     E, T = 13, 37
-    c = _config(N, rng=rng, time_limit=2)
-    ref = _ref(("fused", name, rng, N), lambda: _pairs(c, E, name, T))
+    c = _config(N, rng=rng, time_limit=2, visible=visible)
+    ref = _ref(("fused", name, rng, N) + (("visible",) if visible else ()), lambda: _pairs(c, E, name, T))
     got, nl = _rollout(c, E, name, T, chunk=chunk)
     C = 32 if chunk is None else chunk
     assert nl == 2 + math.ceil((T - 1) / C), nl

@@ -41,7 +41,7 @@ LIDARS = {"b180_r5": dict(beams=180, max_range=5.0, robot_radius=0.3),
 CAP = 0.005   # tests/test_lidar_live.py's share of unstable beams
 
 
-def _config(N, kin="holonomic", policy="srnn", live=None, fov=2.0):
+def _config(N, kin="holonomic", policy="srnn", live=None, fov=2.0, rng=None):
     c = clone_config(Config())
     c.sim.human_num = N
     c.robot.FOV = fov
@@ -51,6 +51,8 @@ def _config(N, kin="holonomic", policy="srnn", live=None, fov=2.0):
     c.humans.policy = "orca"
     c.env.time_limit = 2.0
     c.env.time_step = 0.25
+    if rng is not None:
+        c.env.rng = rng
     if live is not None:
         c.lidar.enable = True
         c.lidar.live = live
@@ -185,12 +187,12 @@ def _keys(noisy):
     return tuple(k for k in ROWS if noisy or k != "executed") + STATE_ROWS + ("lidar", "state")
 
 
-def _rollout(name, N, fov, lk, noisy, calls=((T, STEP0),), chunk=None, graph=False):
+def _rollout(name, N, fov, lk, noisy, calls=((T, STEP0),), chunk=None, graph=False, rng=None):
     """A fresh engine from cn_reset, then rollout(Tk, lidar=) per call: host rows (concatenated along the step
     axis), the launches per call and the state blob."""
     from crowdnav_dsrnn_amd.engine import RolloutNoise
 
-    eng = _engine(_config(N, fov=fov), chunk=chunk)
+    eng = _engine(_config(N, fov=fov, rng=rng), chunk=chunk)
     eng.reset()
     if graph:
         eng.set_graph_mode(True)
@@ -209,12 +211,12 @@ def _rollout(name, N, fov, lk, noisy, calls=((T, STEP0),), chunk=None, graph=Fal
     return got, nls
 
 
-def _eager(name, N, fov, noisy):
+def _eager(name, N, fov, noisy, rng=None):
     """The reference: a = robot_act(); x = restatement(a) (noisy) or a; step(x); lidar_scan at both settings into a
     row of its own; the blob's twelve fields read after the step. Also the belief (for the premise)."""
     import torch
 
-    eng = _engine(_config(N, fov=fov))
+    eng = _engine(_config(N, fov=fov, rng=rng))
     eng.reset()
     rows = {k: [] for k in ROWS if noisy or k != "executed"}
     scans = {lk: [] for lk in LIDARS}
@@ -259,19 +261,23 @@ def _cached(key, make):
     return _CACHE[key]
 
 
-def _eager_cached(name, N, fov, noisy):
-    return _cached(("eager", name, N, fov, noisy), lambda: _eager(name, N, fov, noisy))
+def _rng_key(rng):
+    return () if rng is None else (rng,)
 
 
-def _ref(name, N, fov, lk, noisy):
+def _eager_cached(name, N, fov, noisy, rng=None):
+    return _cached(("eager", name, N, fov, noisy) + _rng_key(rng), lambda: _eager(name, N, fov, noisy, rng))
+
+
+def _ref(name, N, fov, lk, noisy, rng=None):
     """The eager reference with `lidar` of one setting (one eager loop serves both settings)."""
-    ref = dict(_eager_cached(name, N, fov, noisy))
+    ref = dict(_eager_cached(name, N, fov, noisy, rng))
     ref["lidar"] = ref["lidar"][lk]
     return ref
 
 
-def _fused(name, N, fov, lk, noisy=True):
-    return _cached(("fused", name, N, fov, lk, noisy), lambda: _rollout(name, N, fov, lk, noisy))
+def _fused(name, N, fov, lk, noisy=True, rng=None):
+    return _cached(("fused", name, N, fov, lk, noisy) + _rng_key(rng), lambda: _rollout(name, N, fov, lk, noisy, rng=rng))
 
 
 def _launches(name, N, T1, noisy, first_after_reset=True, chunk=32, graph=False):
@@ -305,11 +311,12 @@ def _walls_only_differs(ref, lk):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("name,N,fov", CASES)
-def test_gpu_premises_hold_on_the_reference_run(name, N, fov):
+def test_gpu_premises_hold_on_the_reference_run(name, N, fov, rng=None, lks=None):
     """No case is vacuous: every env auto-resets at least four times, humans are in sight in at least half of the rows,
-    and the robot's belief differs from the humans' positions."""
+    and the robot's belief differs from the humans' positions. (`rng`: tests/test_step_matrix.py runs this at
+    other human counts and under Philox, with `lks` the one LiDAR setting it compares at.)"""
     for noisy in (False, True):
-        ref = _eager_cached(name, N, fov, noisy)
+        ref = _eager_cached(name, N, fov, noisy, rng)
         assert (ref["done"].sum(0) >= 4).all(), ref["done"].sum(0)
         differs = (ref["belief"] != ref["human_state"][:2]).any(0)   # (T, E, N)
         print(name, N, fov, "humans whose belief is not their position: %.3f of the rows" % differs.mean())
@@ -317,8 +324,8 @@ def test_gpu_premises_hold_on_the_reference_run(name, N, fov):
             assert differs.any()   # some human in some row
         else:
             assert not differs.any()   # the full circle: what the module docstring says of these cases
-    ref = _eager_cached(name, N, fov, True)
-    for lk in LIDARS:
+    ref = _eager_cached(name, N, fov, True, rng)
+    for lk in lks or LIDARS:
         share = _walls_only_differs(ref, lk).mean()
         print(name, N, lk, "rows with a human in the scan: %.3f" % share)
         assert share >= 0.5, (lk, share)
@@ -328,12 +335,12 @@ def test_gpu_premises_hold_on_the_reference_run(name, N, fov):
 @pytest.mark.parametrize("lk", sorted(LIDARS))
 @pytest.mark.parametrize("noisy", [False, True])
 @pytest.mark.parametrize("name,N,fov", CASES)
-def test_gpu_rows_equal_the_eager_loop(name, N, fov, noisy, lk):
-    got, nls = _fused(name, N, fov, lk, noisy)
+def test_gpu_rows_equal_the_eager_loop(name, N, fov, noisy, lk, rng=None):
+    got, nls = _fused(name, N, fov, lk, noisy, rng)
     assert nls == [_launches(name, N, T, noisy)], nls
     if not (name == "orca" and N + 1 > 10):
         assert nls[0] < T   # (the eager triple robot_act -> step -> lidar_scan issues 3 T)
-    ref = _ref(name, N, fov, lk, noisy)
+    ref = _ref(name, N, fov, lk, noisy, rng)
     _same(got, ref, "%s N=%d %s vs robot_act -> step -> lidar_scan" % (name, N, lk), _keys(noisy))
     assert ("executed" in got) == noisy
     if fov < 2.0:   # a scan taken from the belief would differ: the humans' true positions are recorded
@@ -379,12 +386,12 @@ def test_gpu_sigma_zero_is_the_clean_rollout_plus_the_copy():
 @pytest.mark.gpu
 @pytest.mark.parametrize("lk", sorted(LIDARS))
 @pytest.mark.parametrize("name,N,fov", CASES)
-def test_gpu_fused_equals_chunk_one_equals_chunk_five(name, N, fov, lk):
-    got, _ = _fused(name, N, fov, lk)
-    one, nls = _rollout(name, N, fov, lk, True, chunk=1)
+def test_gpu_fused_equals_chunk_one_equals_chunk_five(name, N, fov, lk, rng=None):
+    got, _ = _fused(name, N, fov, lk, rng=rng)
+    one, nls = _rollout(name, N, fov, lk, True, chunk=1, rng=rng)
     assert nls == [_launches(name, N, T, True, chunk=1)], nls
     _same(got, one, "%s N=%d %s fused vs chunk 1" % (name, N, lk), _keys(True))
-    five, nls = _rollout(name, N, fov, lk, True, chunk=5)
+    five, nls = _rollout(name, N, fov, lk, True, chunk=5, rng=rng)
     assert nls == [_launches(name, N, T, True, chunk=5)], nls
     _same(got, five, "%s N=%d %s fused vs chunk 5" % (name, N, lk), _keys(True))
 

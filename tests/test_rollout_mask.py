@@ -46,7 +46,7 @@ PLAIN = [k for k in CASES if k != "mixed"]
 FUSED = [k for k, v in CASES.items() if v[4] == "fused"]
 
 
-def _config(N=5, fov=0.5, kin="holonomic", name="orca", masks=False, scripted=False):
+def _config(N=5, fov=0.5, kin="holonomic", name="orca", masks=False, scripted=False, rng=None):
     c = clone_config(Config())
     c.sim.human_num = N
     c.robot.FOV = fov
@@ -55,6 +55,8 @@ def _config(N=5, fov=0.5, kin="holonomic", name="orca", masks=False, scripted=Fa
     c.humans.policy = "orca"
     c.env.time_limit = 2.0
     c.env.time_step = 0.25
+    if rng is not None:
+        c.env.rng = rng
     if kin == "unicycle":
         c.robot.scripted_unicycle = name != "dwa"
         c.robot.scripted_dwa = True if name == "dwa" else None
@@ -124,17 +126,20 @@ def test_config_only_checks_pass_with_both_keys():
 
 
 # ---- GPU ----------------------------------------------------------------------------------------
-def _engine(case, chunk=None):
+def _engine(case, chunk=None, N=None, rng=None):
+    """`N`, `rng` (tests/test_step_matrix.py): the plain case at another human count / under another RNG."""
     from crowdnav_dsrnn_amd.engine import CrowdNavEngine
 
-    name, N, fov, kin, _ = CASES[case]
+    name, n_case, fov, kin, _ = CASES[case]
+    assert N is None or n_case is not None
+    N = n_case if N is None else N
     if N is None:
         c = _config(max(NUMS), fov, kin, name)
         c.sim.human_nums = list(NUMS)
         cfgs, eg = make_varied_cn_configs(c, NUMS, E, env_offset=OFFSET, nenv=NENV, phase="train")
         eng = CrowdNavEngine.mixed(cfgs, eg, DEV, scripted=True)
     else:
-        eng = CrowdNavEngine(make_cn_config(_config(N, fov, kin, name), num_envs=E, env_offset=OFFSET, nenv=NENV,
+        eng = CrowdNavEngine(make_cn_config(_config(N, fov, kin, name, rng=rng), num_envs=E, env_offset=OFFSET, nenv=NENV,
                                             phase="train"), DEV, scripted_unicycle=kin == "unicycle" and name != "dwa",
                              scripted_dwa=True if name == "dwa" else None)
     if chunk is not None:
@@ -175,14 +180,18 @@ def _cached(key, make):
     return _CACHE[key]
 
 
-def _eager(case, noisy):
+def _variant(N, rng):
+    return () if N is None and rng is None else (N, rng)
+
+
+def _eager(case, noisy, N=None, rng=None):
     """The reference: a = robot_act(); x = restatement(a) (noisy) or a; step(x); visible_mask() -- every step's
     outputs cloned into row t, the blob at the end. Also the figures of the premises, from this run alone."""
     import torch
 
     def make():
         name = CASES[case][0]
-        eng = _engine(case)
+        eng = _engine(case, N=N, rng=rng)
         eng.reset()
         rows = {k: [] for k in ROWS}
         real = eng.human_mask.cpu().numpy()
@@ -220,16 +229,17 @@ def _eager(case, noisy):
         out["premises"] = prem
         return out
 
-    return _cached(("eager", case, noisy), make)
+    return _cached(("eager", case, noisy) + _variant(N, rng), make)
 
 
-def _rollout(case, noisy=True, calls=((T, STEP0),), chunk=None, graph=False, every=True, sigma=SIGMA, mask=True):
+def _rollout(case, noisy=True, calls=((T, STEP0),), chunk=None, graph=False, every=True, sigma=SIGMA, mask=True,
+             N=None, rng=None):
     """A fresh engine from cn_reset, then one rollout per call (noise continued at step0): host rows (concatenated),
     the launches per call and the state blob. The mask buffer is poisoned first, so an unwritten slot shows."""
     import torch
 
     name = CASES[case][0]
-    eng = _engine(case, chunk=chunk)
+    eng = _engine(case, chunk=chunk, N=N, rng=rng)
     eng.reset()
     if graph:
         eng.set_graph_mode(True)
@@ -252,17 +262,17 @@ def _rollout(case, noisy=True, calls=((T, STEP0),), chunk=None, graph=False, eve
     return got, nls
 
 
-def _default(case, noisy):
-    return _cached(("rollout", case, noisy), lambda: _rollout(case, noisy))
+def _default(case, noisy, N=None, rng=None):
+    return _cached(("rollout", case, noisy) + _variant(N, rng), lambda: _rollout(case, noisy, N=N, rng=rng))
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("case", list(CASES))
-def test_gpu_premises_hold_on_the_eager_run(case):
+def test_gpu_premises_hold_on_the_eager_run(case, N=None, rng=None):
     """Asserted on the eager reference alone: the shapes exercise what the comparisons below are about."""
     fov = CASES[case][2]
     for noisy in (True, False):
-        p = _eager(case, noisy)["premises"]
+        p = _eager(case, noisy, N, rng)["premises"]
         print(case, "noisy" if noisy else "clean", "resets min", int(p["resets"].min()), "visible share", p["share"],
               "done rows whose mask changed", p["done_rows_changed"], "invisible slots with an exact belief",
               p["stale_exact"])
@@ -279,9 +289,9 @@ def test_gpu_premises_hold_on_the_eager_run(case):
 @pytest.mark.gpu
 @pytest.mark.parametrize("noisy", [True, False], ids=["noisy", "clean"])
 @pytest.mark.parametrize("case", list(CASES))
-def test_gpu_rows_equal_the_eager_loop(case, noisy):
-    got, _ = _default(case, noisy)
-    ref = _eager(case, noisy)
+def test_gpu_rows_equal_the_eager_loop(case, noisy, N=None, rng=None):
+    got, _ = _default(case, noisy, N, rng)
+    ref = _eager(case, noisy, N, rng)
     assert set(np.unique(got["visible_masks"])) <= {0.0, 1.0}
     keys = [k for k in ROWS if noisy or k != "executed"]
     _same_rows(got, ref, "%s vs robot_act -> step -> visible_mask" % case, keys)
@@ -302,9 +312,9 @@ def test_gpu_every_row_cn_rollout_records_is_unchanged(case):
 @pytest.mark.gpu
 @pytest.mark.parametrize("chunk", [1, 5])
 @pytest.mark.parametrize("case", list(CASES))
-def test_gpu_chunks_give_the_same_rows(case, chunk):
-    got, _ = _default(case, True)
-    other, nls = _rollout(case, True, chunk=chunk)
+def test_gpu_chunks_give_the_same_rows(case, chunk, N=None, rng=None):
+    got, _ = _default(case, True, N, rng)
+    other, nls = _rollout(case, True, chunk=chunk, N=N, rng=rng)
     _same_rows(got, other, "%s default chunk vs %d" % (case, chunk))
     assert got["state"] == other["state"]
     if chunk == 1 and case != "mixed":

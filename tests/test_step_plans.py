@@ -210,18 +210,20 @@ QUAD_PLANS = [(N, False) for N in range(1, 11)] + [(N, True) for N in range(1, 1
 KD_SEQ_PLANS = [(10, True), (31, True)]
 
 
-def _seq_case(N, vis):
+def _seq_case(N, vis, rng=None):
     kin, scen, fov = _rule(N)
     base = clone_config(Config())
     base.robot.visible = vis
+    if rng is not None:
+        base.env.rng = rng
     return SC._cfg(N, kin, E, fov=fov, time_limit=2, base=base, sims=[scen]), kin
 
 
-def _seq_check(N, vis, chunks):
+def _seq_check(N, vis, chunks, rng=None):
     """step_seq over T = 37 steps at each chunk length against chunk 1: the nine outputs and the state blob, bit
     for bit; every env resets inside launches, and at FOV pi the carried belief is not the position."""
     T = 37
-    cfg, kin = _seq_case(N, vis)
+    cfg, kin = _seq_case(N, vis, rng)
     assert cfg.robot_visible == vis and cfg.human_num == N
     acts = SC._actions(T, E, kin, 100 + N)
     ref, sv = SC._run(cfg, acts, [("seq", 0, T)], chunk=1)
