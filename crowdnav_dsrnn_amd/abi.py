@@ -130,6 +130,17 @@ class DwaParams(ctypes.Structure):
     ]
 
 
+class CnMixCtl(ctypes.Structure):
+    """struct cn_mix_ctl (include/crowdnav.h): cn_robot_mix's device block (16 bytes), the argument of
+    cn_mix_ctl_set."""
+
+    _fields_ = [
+        ("beta", ctypes.c_float),
+        ("seed", ctypes.c_uint32),
+        ("step0", ctypes.c_int64),
+    ]
+
+
 # --- state blob (include/crowdnav_state.h) ---------------------------------------------------------
 CNT_ENV, CNT_HUM, CNT_PERM, CNT_MT = 0, 1, 2, 3
 _T = {0: np.float64, 1: np.float32, 2: np.int64, 3: np.int32, 4: np.uint32, 5: np.uint8}

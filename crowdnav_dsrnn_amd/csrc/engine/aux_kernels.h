@@ -1,7 +1,7 @@
 // aux_kernels.h -- the small stand-alone kernels: the debug / predictor kernels that expose the step kernel's
 // device functions on caller-given inputs (cn_disc_quad, cn_copy64, cn_orca, cn_orca_kd with RVO2's sequential
 // KdTree, cn_sf_predict, cn_dwa_predict), cn_robot_act's kernels (ORCA, social force, the dynamic window), cn_rollout_noisy's (cn_action_noise_kernel,
-// cn_noise_set_kernel, cn_copy32_kernel), cn_rollout_lidar's (cn_rows_set_kernel, cn_state_rows_kernel), and the
+// cn_noise_set_kernel, cn_copy32_kernel), cn_robot_mix's (cn_robot_mix_kernel, cn_mix_ctl_set_kernel), cn_rollout_lidar's (cn_rows_set_kernel, cn_state_rows_kernel), and the
 // two stream-ordered helpers of the host API (cn_ctl_set_kernel, cn_keysnap_kernel). Part of cn_engine.hip's translation unit: included there after the device core, whose
 // geometry, ORCA and scripted-robot functions these kernels call.
 #pragma once
@@ -546,6 +546,34 @@ __global__ void __launch_bounds__(64) cn_action_noise_kernel(const float *__rest
 // cn_rollout_noisy's device block for the fused launches that follow on the stream (a kernel for the reason
 // cn_ctl_set_kernel is one)
 __global__ void cn_noise_set_kernel(RolloutNoise *w, RolloutNoise v)
+{
+    if (threadIdx.x == 0) *w = v;
+}
+
+// cn_robot_mix: the coin between the learner's action and the controller's label, one lane per env of all E rows (a
+// mixed engine: after the groups' join, its rows are the global order already). `ctl` is the caller's device block:
+// the address is a kernel argument, so the three words arrive as wave-uniform (scalar) loads; only t is baked
+// into a captured launch. The coin is word z of rollout_noise's Philox block (x and y are the noise's), the pairs
+// move as 8-byte words (bits, no arithmetic). No LDS, no cross-lane reads, no barrier.
+__global__ void __launch_bounds__(256) cn_robot_mix_kernel(const uint2 *__restrict__ learner,
+                                                           const cn_mix_ctl *__restrict__ ctl, int32_t t, uint32_t G0,
+                                                           int E, const uint2 *__restrict__ label,
+                                                           uint2 *__restrict__ executed, uint8_t *__restrict__ flags)
+{
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= E) return;
+    const float beta = ctl->beta;
+    const uint32_t seed = ctl->seed, k = (uint32_t)(uint64_t)(ctl->step0 + t);
+    const uint4 w = philox4x32_10(k, seed, G0 + (uint32_t)e);
+    const float u = (float)(w.z >> 8) * 5.9604644775390625e-08f;   // 2^-24: exact, in [0, 1)
+    const bool took = u < beta;
+    const uint2 l = label[e], a = learner[e];
+    executed[e] = took ? l : a;
+    flags[e] = (uint8_t)((took ? 1u : 0u) | ((l.x == a.x && l.y == a.y) ? 2u : 0u));
+}
+
+// cn_mix_ctl_set: the caller's device block from the stream (a kernel for the reason cn_ctl_set_kernel is one)
+__global__ void cn_mix_ctl_set_kernel(cn_mix_ctl *w, cn_mix_ctl v)
 {
     if (threadIdx.x == 0) *w = v;
 }

@@ -919,6 +919,36 @@ int cn_robot_act(cn_engine *g, void *stream, int policy, float *actions)
     return rc ? rc : rj;
 }
 
+// By value through a kernel, as cn_rollout_noisy hands its block over: stream-ordered, a kernel node when captured.
+int cn_mix_ctl_set(void *stream, cn_mix_ctl *dev, const cn_mix_ctl *value)
+{
+    if (!dev || !value) return set_err(CN_EINVAL, "cn_mix_ctl_set: dev and value required");
+    if (!(value->beta >= 0.0f && value->beta <= 1.0f))   // (a NaN fails both)
+        return set_err(CN_EINVAL, "cn_mix_ctl_set: beta in [0, 1] required");
+    (void)hipGetLastError();   // a stale error of an earlier call (any library) is not this launch's
+    hipLaunchKernelGGL(cn_mix_ctl_set_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, dev, *value);
+    HIPCHK(hipGetLastError());
+    return CN_OK;
+}
+
+// cn_robot_act into `label` (its checks, its launches, a mixed engine's fork and join), then one launch over all E
+// rows on the caller's stream.
+int cn_robot_mix(cn_engine *g, void *stream, int policy, const float *learner, const cn_mix_ctl *ctl, int32_t t,
+                 float *label, float *executed, uint8_t *flags)
+{
+    if (!g) return set_err(CN_EINVAL, "null engine");
+    if (!learner || !ctl || !label || !executed || !flags || t < 0)
+        return set_err(CN_EINVAL, "cn_robot_mix: learner, ctl, label, executed, flags and t >= 0 required");
+    const int rc = cn_robot_act(g, stream, policy, label);   // (every check of it comes before its first launch)
+    if (rc) return rc;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(cn_robot_mix_kernel, dim3((unsigned)((g->E + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const uint2 *)learner, ctl, t, (uint32_t)(uint64_t)g->c.env_offset, (int)g->E,
+                       (const uint2 *)label, (uint2 *)executed, flags);
+    HIPCHK(hipGetLastError());
+    return CN_OK;
+}
+
 // cn_visible_mask's launch for a plain engine or a group of a mixed engine (its envs' rows of the [E][NS] buffer)
 static int visible_mask_launch(const cn_engine *g, hipStream_t st, float *mask)
 {

@@ -312,6 +312,66 @@ class CrowdNavEngine:
             _lib.check(_lib.lib().cn_robot_act(self._h, self._stream(), self.ROBOT_POLICIES[policy], out.data_ptr()))
         return out
 
+    def mix_ctl(self):
+        """A fresh 16-byte device block for robot_mix (cn_mix_ctl: beta, seed, step0), zeroed: beta 0, the learner
+        alone. Fill it with set_mix_ctl."""
+        return self.torch.zeros((16,), dtype=self.torch.uint8, device=self.device)
+
+    def _is_mix_ctl(self, ctl):
+        t = self.torch
+        return (isinstance(ctl, t.Tensor) and ctl.dtype == t.uint8 and ctl.device == self.device
+                and ctl.is_contiguous() and ctl.numel() == 16 and ctl.data_ptr() % 8 == 0)
+
+    def set_mix_ctl(self, ctl, beta, seed=0, step0=0):
+        """cn_mix_ctl_set: (beta, seed, step0) into the device block `ctl` (mix_ctl()) by one small launch on the
+        current stream; no host sync. A captured graph of robot_mix calls reads whatever was set before its replay.
+        beta: a finite probability in [0, 1]."""
+        beta = float(beta)
+        if not 0.0 <= beta <= 1.0:   # (a NaN fails both)
+            raise ValueError("set_mix_ctl: beta in [0, 1] required, got %r" % (beta,))
+        if not self._is_mix_ctl(ctl):
+            raise ValueError("set_mix_ctl: ctl must be the 16-byte uint8 block of mix_ctl() on %s" % self.device)
+        v = abi.CnMixCtl(beta, int(seed) & 0xFFFFFFFF, int(step0))
+        with self.torch.cuda.device(self.device):
+            _lib.check(_lib.lib().cn_mix_ctl_set(self._stream(), ctl.data_ptr(), ctypes.byref(v)))
+        return ctl
+
+    def robot_mix(self, policy, learner, ctl, t, label=None, executed=None, flags=None):
+        """The learner in the loop (cn_robot_mix): label = robot_act(policy) of the engine's current state, and per
+        env a coin of probability ctl.beta -- word z of philox(counter step0 + t, key (seed, global env index)),
+        policy_factory.mix_coin -- picks executed = label (taken) or `learner` (E, 2) float32, copied as bits.
+        flags (E,) uint8: bit 0 = the label was taken, bit 1 = learner == label as bits. Returns (label, executed,
+        flags), each into the tensor given or a fresh one. beta, seed and step0 are read on the device when the
+        launch runs (set_mix_ctl); t >= 0 is the launch's own. robot_act's launch(es) + one more; no host sync."""
+        tc = self.torch
+        if policy not in self.ROBOT_POLICIES:
+            raise ValueError("robot_mix: policy %r (one of %s)" % (policy, sorted(self.ROBOT_POLICIES)))
+        t = int(t)
+        if t < 0:
+            raise ValueError("robot_mix: t >= 0 required, got %d" % t)
+        if not self._is_mix_ctl(ctl):
+            raise ValueError("robot_mix: ctl must be the 16-byte uint8 block of mix_ctl() on %s" % self.device)
+        E = self.E
+        if label is None:
+            label = tc.zeros((E, 2), dtype=tc.float32, device=self.device)
+        if executed is None:
+            executed = tc.zeros((E, 2), dtype=tc.float32, device=self.device)
+        if flags is None:
+            flags = tc.zeros((E,), dtype=tc.uint8, device=self.device)
+        for name, x in (("learner", learner), ("label", label), ("executed", executed)):
+            if (not isinstance(x, tc.Tensor) or x.dtype != tc.float32 or x.device != self.device
+                    or not x.is_contiguous() or x.numel() != E * 2 or x.data_ptr() % 8):
+                raise ValueError("robot_mix: %s must be a contiguous float32 (E, 2) tensor on %s" % (name, self.device))
+        if flags.dtype != tc.uint8 or flags.device != self.device or not flags.is_contiguous() or flags.numel() != E:
+            raise ValueError("robot_mix: flags must be a contiguous uint8 (E,) tensor on %s" % self.device)
+        if len({learner.data_ptr(), label.data_ptr(), executed.data_ptr()}) != 3:
+            raise ValueError("robot_mix: learner, label and executed must be three different buffers")
+        with tc.cuda.device(self.device):
+            _lib.check(_lib.lib().cn_robot_mix(self._h, self._stream(), self.ROBOT_POLICIES[policy], learner.data_ptr(),
+                                               ctl.data_ptr(), t, label.data_ptr(), executed.data_ptr(),
+                                               flags.data_ptr()))
+        return label, executed, flags
+
     @staticmethod
     def _lidar_args(lidar):
         """(beams, max_range, robot_radius) of rollout's `lidar` (a dict with those keys)."""

@@ -390,6 +390,16 @@ class CrowdNavVecEnv:
         _no_varied(self.config, "robot_act")
         return self.engine.robot_act(policy)
 
+    def robot_mix(self, policy, learner, ctl, t, label=None, executed=None, flags=None):
+        """The learner in the loop (CrowdNavEngine.robot_mix -> cn_robot_mix): robot_act(policy) of the state the last
+        reset / step returned as `label`, and per env a coin of probability beta -- the device block `ctl`
+        (engine.mix_ctl() / set_mix_ctl) -- that makes `executed` the label or the `learner`'s (E, 2) action, what
+        step_device then takes. Returns (label, executed, flags); no host synchronisation. The envs it serves are
+        robot_act's: the same opt-ins, the same UnsupportedConfig on an env of varying human count without
+        sim.human_nums_scripted."""
+        _no_varied(self.config, "robot_mix")
+        return self.engine.robot_mix(policy, learner, ctl, t, label=label, executed=executed, flags=flags)
+
     def rollout(self, policy, T, obs_every_step=True, out=None, noise=None):
         """T closed-loop steps of the scripted robot ('orca' / 'social_force') from the state the last reset / step
         left, every step recorded (CrowdNavEngine.rollout: a dict of (T, E, ...) tensors on the engine's GPU, no

@@ -370,6 +370,44 @@ def dwa_predict(self_state, v, others, time_step, params=None, detail=False):
     return actions, choice, costs
 
 
+def _philox4x32_10(c0, k0, k1):
+    """Philox4x32-10 (Salmon et al., SC'11; the Random123 constants) of counter (c0, 0, 0, 0) under key (k0, k1),
+    broadcast over numpy arrays, in uint64 arithmetic: the four output words as uint64 arrays < 2^32. The block of
+    cn_rollout_noisy and cn_robot_mix (include/crowdnav.h)."""
+    m32 = np.uint64(0xFFFFFFFF)
+    c0, k0, k1 = np.broadcast_arrays(*[np.asarray(v, np.int64).astype(np.uint64) & m32 for v in (c0, k0, k1)])
+    x0, x1, x2, x3 = c0, np.zeros_like(c0), np.zeros_like(c0), np.zeros_like(c0)
+    for _ in range(10):
+        p0, p1 = np.uint64(0xD2511F53) * x0, np.uint64(0xCD9E8D57) * x2   # 32 x 32 -> 64 bits: no overflow
+        x0, x1, x2, x3 = (p1 >> np.uint64(32)) ^ x1 ^ k0, p1 & m32, (p0 >> np.uint64(32)) ^ x3 ^ k1, p0 & m32
+        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & m32, (k1 + np.uint64(0xBB67AE85)) & m32
+    return x0, x1, x2, x3
+
+
+def mix_coin(seed, k, G):
+    """cn_robot_mix's coin on the host (numpy): u = (float32)(w.z >> 8) * 2^-24 in [0, 1), w = philox4x32_10(counter
+    (uint32)k, key ((uint32)seed, (uint32)G)); k = step0 + t of the caller's coin sequence, G the env's global index
+    (env_offset + e). k and G broadcast; float32 out. The expert's action is executed where u < beta."""
+    z = _philox4x32_10(k, np.int64(int(seed) & 0xFFFFFFFF), G)[2]
+    return ((z >> np.uint64(8)).astype(np.float32) * np.float32(2.0 ** -24)).astype(np.float32)
+
+
+def robot_mix_ref(label, learner, beta, seed, k, G):
+    """cn_robot_mix's select on the host (numpy), include/crowdnav.h restated: for labels and learner actions
+    (..., 2) float32 with k and G broadcasting over the leading axes, (executed (..., 2) float32, flags (...) uint8):
+    took = mix_coin(seed, k, G) < (float32)beta; executed = label where took, else learner, copied as bits; flags bit
+    0 = took, bit 1 = learner equals label in both components as bits."""
+    lab = np.ascontiguousarray(label, np.float32)
+    lea = np.ascontiguousarray(learner, np.float32)
+    if lab.shape != lea.shape or lab.shape[-1:] != (2,):
+        raise ValueError("robot_mix_ref: label and learner of one shape (..., 2) required")
+    took = np.broadcast_to(mix_coin(seed, k, G) < np.float32(beta), lab.shape[:-1])
+    lb, le = lab.view(np.uint32), lea.view(np.uint32)
+    executed = np.where(took[..., None], lb, le).astype(np.uint32).view(np.float32)
+    same = (lb == le).all(axis=-1)
+    return executed, (took.astype(np.uint8) | (same.astype(np.uint8) << 1)).astype(np.uint8)
+
+
 class _ScriptedBase:
     """The one attribute evaluate() reads of an actor's `base` (it sizes the edge RNN state by it)."""
 

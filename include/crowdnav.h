@@ -37,6 +37,8 @@
  *                   unicycle robot's own action space; the opt-in makes it cn_robot_act's policy CN_ROBOT_DWA
  *   cn_robot_act     ⟵ Robot.act of a scripted ('orca' / 'social_force') robot on its belief
  *                   (crowd_sim/envs/utils/robot.py:9-15, crowd_sim.py:1113-1114,1185-1188), every env in one launch
+ *   cn_robot_mix / cn_mix_ctl_set ⟵ (no reference counterpart) cn_robot_act as the labeller of a learner that drives
+ *                   the envs: a per-env coin picks the executed action (DAgger's mixture policy), read from device memory
  *   cn_rollout       ⟵ the closed loop `action = robot.act(ob); ob, ... = env.step(action)` of a scripted robot
  *                   over T steps (crowd_nav test loop / expert demonstrations), every step recorded, in
  *                   multi-step launches with the controller inside the step kernel
@@ -622,6 +624,38 @@ int cn_robot_act(cn_engine *eng, void *stream, int policy, float *actions);
  * no launch. CN_EINVAL: eng NULL or bad parameters (cn_dwa_predict's rule); CN_EUNSUPPORTED: p != NULL on an engine
  * with holonomic envs (the controller emits (dv, dtheta)). */
 int cn_scripted_dwa(cn_engine *eng, const cn_dwa_params *p);
+
+/* The learner in the loop (DAgger, Ross et al. 2011): the scripted controller labels the engine's current state and
+ * a per-env coin decides whether its action or the learner's is the one to execute. For env e (global index
+ * G = env_offset + e; a mixed engine: its row, as cn_rollout_noisy keys its noise) and k = (uint32)(ctl->step0 + t):
+ *   label[e]    = what cn_robot_act(eng, stream, policy, label) writes, bit for bit (it IS that call)
+ *   w           = philox4x32_10(counter k, key (seed, (uint32)G))      (cn_rollout_noisy's block)
+ *   u           = (float)(w.z >> 8) * 2^-24                            (exact in float32, in [0, 1))
+ *   took        = u < beta                                             (beta = 0: never; beta = 1: always, exactly)
+ *   executed[e] = took ? label[e] : learner[e]                         (copied as bits: a -0.0f keeps its sign)
+ *   flags[e]    = took | (learner[e] == label[e] in both components, as bits) << 1
+ * Word z, because x and y are cn_rollout_noisy's: a noisy rollout and a mixed one on the same seed stay independent.
+ * Bit 1 is the closed-loop agreement: with a lattice head and CN_ROBOT_DWA, the classifier's on-policy accuracy.
+ * beta, seed and step0 are read from DEVICE memory when the kernel runs; only t is a launch argument. A captured
+ * graph of calls at t = 0..T-1 therefore replays with whatever cn_mix_ctl_set wrote before the replay.
+ * cn_mix_ctl_set: *dev = *value by one small launch on the stream (by value: no host memory is read later, no
+ * memset or memcpy node when captured). CN_EINVAL: dev or value NULL, beta outside [0, 1] or not finite.
+ * cn_robot_mix: cn_robot_act's launch(es) into `label` (a mixed engine: one per group, joined), then ONE launch over
+ * all E rows: a lane per env in 256-lane workgroups, 8-byte loads and stores of the action pairs (learner, label
+ * and executed 8-byte aligned; the three and flags must not overlap), the block read wave-uniformly; no LDS, no
+ * atomics. Stream-ordered; no allocation, no synchronisation, no memset; capturable. No engine state changes.
+ * CN_EINVAL: a NULL pointer, t < 0, an unknown policy (CN_ROBOT_DWA without cn_scripted_dwa included);
+ * CN_EUNSUPPORTED: cn_robot_act's (a mixed engine without cn_mixed_scripted, a unicycle engine without
+ * cn_scripted_unicycle). All are checked before any launch. */
+typedef struct cn_mix_ctl {   /* 16 bytes, lives in DEVICE memory, owned by the caller */
+    float    beta;    /* probability that the expert's action is the one executed; 0 <= beta <= 1 */
+    uint32_t seed;
+    int64_t  step0;   /* index of step t = 0 in the caller's coin sequence */
+} cn_mix_ctl;
+int cn_mix_ctl_set(void *stream, cn_mix_ctl *dev, const cn_mix_ctl *value);
+int cn_robot_mix(cn_engine *eng, void *stream, int policy, const float *learner /*[E][2]*/,
+                 const cn_mix_ctl *ctl /*device*/, int32_t t,
+                 float *label /*[E][2]*/, float *executed /*[E][2]*/, uint8_t *flags /*[E]*/);
 
 /* Which humans the robot sees in the state the engine now holds (after cn_reset / cn_step / cn_step_seq /
  * cn_set_state): mask [E][NS] float32, NS = the padded human stride of the observation (N; a mixed engine: its

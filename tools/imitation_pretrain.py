@@ -26,12 +26,15 @@ candidates themselves, a continuous label (ORCA or the social force through the 
 --fov F sets robot.FOV (in units of pi; the default config's is 2.0, the full circle) for training and evaluation
 alike; --visible-masks (DSRNN only) also runs all of it on envs with sim.visible_masks and sim.visible_masks_scripted:
 the rollouts record the 'visible_masks' rows (cn_rollout_masked) and the policy attends to the visible humans only.
+--dagger replaces the rows per sigma by ONE row "dagger": the same fresh policy trained with learner.DAgger -- the learner
+drives the envs, the expert labels every state it runs into -- with --beta (the probability that the expert's action is
+the one executed in the first chunk), --beta-decay (its factor per chunk) and --aggregate (chunks held for the fit).
 Needs a GPU.
 
 Usage: python tools/imitation_pretrain.py [--policy srnn|convgru] [--expert orca] [--updates 3000] [--envs 1024] [--steps 32] [--epochs 1]
            [--mini-batch 2] [--lr 1e-3] [--value-coef 0.5] [--sigma-frac 0 0.1 0.3] [--humans 5] [--seed 0]
            [--human-nums 5 10 [--unseen 7]] [--kinematics holonomic|unicycle [--sigma 0 0.03] [--head gaussian|lattice]]
-           [--fov F] [--visible-masks] [--eval-envs 100] [--test-size 500] [--log-every K] [--out policy.pt]
+           [--fov F] [--visible-masks] [--dagger [--beta 1.0] [--beta-decay 0.5] [--aggregate 1]] [--eval-envs 100] [--test-size 500] [--log-every K] [--out policy.pt]
            [--json FILE]
 """
 import argparse
@@ -48,7 +51,7 @@ import torch  # noqa: E402
 from crowdnav_dsrnn_amd.config import Config, clone_config  # noqa: E402
 from crowdnav_dsrnn_amd.envs import CrowdNavVecEnv  # noqa: E402
 from crowdnav_dsrnn_amd.evaluation import evaluate, evaluate_scripted  # noqa: E402
-from crowdnav_dsrnn_amd.learner import BehaviourCloning  # noqa: E402
+from crowdnav_dsrnn_amd.learner import BehaviourCloning, DAgger  # noqa: E402
 from crowdnav_dsrnn_amd.policy import Policy  # noqa: E402
 from crowdnav_dsrnn_amd.policy_factory import ScriptedRobot  # noqa: E402
 
@@ -89,6 +92,11 @@ def main():
     ap.add_argument("--fov", type=float, default=None, help="robot.FOV in units of pi (default: the config's 2.0)")
     ap.add_argument("--visible-masks", action="store_true",
                     help="envs with sim.visible_masks + sim.visible_masks_scripted: the masked spatial attention")
+    ap.add_argument("--dagger", action="store_true",
+                    help="train with learner.DAgger (the learner in the loop) instead of BehaviourCloning: one row")
+    ap.add_argument("--beta", type=float, default=1.0, help="with --dagger: the first chunk's expert probability")
+    ap.add_argument("--beta-decay", type=float, default=0.5, help="with --dagger: beta's factor per chunk")
+    ap.add_argument("--aggregate", type=int, default=1, help="with --dagger: chunks held for the fit")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--eval-envs", type=int, default=100)
     ap.add_argument("--test-size", type=int, default=500)
@@ -194,7 +202,37 @@ def main():
     evaluate_policy(fresh_policy(spaces, action_space, cpol), {"row": "untrained", "policy": args.policy,
                                                                "kinematics": args.kinematics,
                                                                "episodes": args.test_size})
-    for sigma, frac in sigmas:
+    if args.dagger:
+        pol = fresh_policy(spaces, action_space, cpol)
+        envs = CrowdNavVecEnv(ct, E, args.seed, DEV, allow_early_resets=True, nenv=E, phase="train")
+        dg = DAgger(ct, envs, pol, expert=args.expert, beta=args.beta, beta_decay=args.beta_decay, seed=args.seed,
+                    epochs=args.epochs, lr=args.lr, value_coef=args.value_coef, aggregate=args.aggregate)
+        torch.cuda.synchronize()
+        t0 = time.time()
+        gpu_roll = gpu_upd = 0.0
+        first = st = None
+        for u in range(args.updates):
+            st = dg.update()
+            first = first or st
+            if args.log_every and (u + 1) % args.log_every == 0:
+                print("dagger update %d beta %.4g nll %.4f value_loss %.4f agree %.4f took_expert %.4f"
+                      % (u + 1, st["beta"], st["nll"], st["value_loss"], st["agree"], st["took_expert"]),
+                      file=sys.stderr, flush=True)
+            gpu_roll += st["rollout_s"]
+            gpu_upd += st["update_s"]
+        wall = time.time() - t0
+        envs.close()
+        evaluate_policy(pol, {"row": "dagger", "policy": args.policy, "expert": args.expert, "beta": args.beta,
+                              "beta_decay": args.beta_decay, "aggregate": args.aggregate, "graphs": dg.graphs,
+                              "kinematics": args.kinematics, "updates": args.updates, "envs": E, "steps": args.steps,
+                              "epochs": args.epochs, "lr": args.lr, "env_steps": dg.env_steps,
+                              "nll_first": round(first["nll"], 4), "nll_last": round(st["nll"], 4),
+                              "value_loss_last": round(st["value_loss"], 4), "agree_first": round(first["agree"], 4),
+                              "agree_last": round(st["agree"], 4), "took_expert_last": round(st["took_expert"], 4),
+                              "beta_last": st["beta"], "train_wall_s": round(wall, 2),
+                              "rollout_gpu_s": round(gpu_roll, 3), "update_gpu_s": round(gpu_upd, 3),
+                              "episodes": args.test_size})
+    for sigma, frac in ([] if args.dagger else sigmas):
         pol = fresh_policy(spaces, action_space, cpol)
         envs = CrowdNavVecEnv(ct, E, args.seed, DEV, allow_early_resets=True, nenv=E, phase="train")
         bc = BehaviourCloning(ct, envs, pol, expert=args.expert, sigma=sigma, seed=args.seed,
