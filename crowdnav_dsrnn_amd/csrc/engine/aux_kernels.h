@@ -608,7 +608,7 @@ __global__ void cn_ctl_set_kernel(uint32_t *w, uint32_t v)
     if (threadIdx.x == 0) *w = v;
 }
 
-// Key snapshot for a PEND_BOTH launch (after cn_set_state, and the quad path's cn_reset): every env's
+// Key snapshot for a PEND_BOTH launch (after cn_set_state): every env's
 // {e, reset_count, case_counter lo, hi} into the spawn list the next step launch reads (kr = (t + 2) % 3 for
 // launch t: the host's sequence number, or graph mode's device word). That launch's spawn waves key both of an
 // env's pending spawns from this entry, not from the state its own step workgroups rewrite when a terminal env
@@ -645,5 +645,5 @@ __global__ void __launch_bounds__(64) cn_visible_mask_kernel(cn_state_ptrs S, in
     if (e >= E) return;
     const int k = (int)(i - e * NS);
     const int64_t o = MIX ? (int64_t)rows[e] : e;
-    mask[o * NS + k] = visible_mask_slot(S, e, k, N, holo, fov, cth);   // (cn_engine.hip: the rollout kernels' too)
+    mask[o * NS + k] = visible_mask_slot(S, e, k, N, holo, fov, cth);   // (robot.h: the rollout kernels' too)
 }

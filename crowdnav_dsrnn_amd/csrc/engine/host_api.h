@@ -176,7 +176,7 @@ int cn_create(const cn_config *cfg, int device, cn_engine **out)
         // that read them from the state could see a later reset of the same env and queue a key that the next
         // launch queued again: two writers of one pending slot, one of them resuming from it -- 5 of 149 C3 runs
         // departed; 0 of 149 with keyed entries). The quad path parks after CN_QUAD_BUDGET cycles (round 6).
-        g->spawn_budget = g->plan.kd ? 600000 : (CN_QUAD_PARK ? CN_QUAD_BUDGET : 0);
+        g->spawn_budget = g->plan.kd ? 600000 : CN_QUAD_BUDGET;
         g->seq_chunk = CN_SEQ_CHUNK;
     }
     cn_state_bind(&g->s, g->state, g->E, g->N, cfg->robot_visible);
@@ -185,12 +185,10 @@ int cn_create(const cn_config *cfg, int device, cn_engine **out)
         return set_err(CN_EHIP, "hipMemcpyToSymbol failed");
     }
     if (g->a_lds > 160 * 1024) { cn_destroy(g); return set_err(CN_EUNSUPPORTED, "LDS plan exceeds 160 KiB"); }
-#if CN_SEQ_GOAL_EARLY
     if (!g->plan.kd && !cn_goal_early_ok(g->plan)) {   // (no plan of today's: the multi-step kernels rely on it)
         cn_destroy(g);
         return set_err(CN_EUNSUPPORTED, "LDS plan: the RNG regions of waves 2 and 3 overlap the staged human state");
     }
-#endif
     if (g->a_lds > 64 * 1024)
         for (const StepKernelEntry &k : step_kernels)
             (void)hipFuncSetAttribute((const void *)k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, g->a_lds);
@@ -426,20 +424,14 @@ int cn_reset(cn_engine *g, void *stream, float *robot_node, float *temporal, flo
     a.o.ov.row = g->rows; a.o.ov.NS = g->NS;
     a.pend = g->pend; a.E = g->E; a.counter_offset = g->counter_offset;
     // the reset kernel draws the next two spawns too, so the first step launches (whose spawns would otherwise
-    // run inline in step workgroups until the budgeted spawn waves catch up) find them drawn (PEND_FRESH);
-    // without quad-path parking the quad path's first launch draws them (PEND_BOTH, as after cn_set_state)
-    a.draw_next = (g->plan.kd || CN_QUAD_PARK) ? 1 : 0;
+    // run inline in step workgroups until the budgeted spawn waves catch up) find them drawn (PEND_FRESH)
+    a.draw_next = 1;
     (void)hipGetLastError();   // a stale error of an earlier call (any library) is not this launch's
     hipLaunchKernelGGL(cn_reset_kernel, dim3(g->rng_grid), dim3(64), 0, st, a, g->c);
     HIPCHK(hipGetLastError());
-    // every env starts a new episode (kd-tree path: with its next two spawns drawn): the next step launch
-    // draws them (none) and ignores the earlier launches' lists (host flag; graph mode: the device flag,
-    // stream-ordered)
-    g->pend_all = a.draw_next ? PEND_FRESH : PEND_BOTH;
-    if (!a.draw_next) {   // PEND_BOTH keys its items from a snapshot of the counters the reset kernel wrote
-        const int rk = keysnap(g, st);
-        if (rk) return rk;
-    }
+    // every env starts a new episode with its next two spawns drawn: the next step launch draws them (none)
+    // and ignores the earlier launches' lists (host flag; graph mode: the device flag, stream-ordered)
+    g->pend_all = PEND_FRESH;
     if (g->devseq) return ctl_set(g->work_count + CN_CTL_ALL, (uint32_t)g->pend_all, st);
     return CN_OK;
 }
@@ -681,9 +673,6 @@ int cn_debug_stamps_r(unsigned long long *r, unsigned long long *sp)
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpyFromSymbol(r, HIP_SYMBOL(cn_stamp_r), sizeof(unsigned long long) * 8192 * 2));
     if (sp) HIPCHK(hipMemcpyFromSymbol(sp, HIP_SYMBOL(cn_stamp_s), sizeof(unsigned long long) * 8192 * 16));
-    unsigned long long l3[14];
-    HIPCHK(hipMemcpyFromSymbol(l3, HIP_SYMBOL(cn_lp3_cnt), sizeof(l3)));
-    for (int k = 0; k < 14; ++k) r[8192 * 2 - 14 + k] = l3[k];   // (the last workgroup slots: never a real grid here)
     return CN_OK;
 }
 
@@ -708,7 +697,7 @@ int cn_debug_set_spawn_budget(cn_engine *g, long long cycles)
 {
     if (!g || cycles < 0) return set_err(CN_EINVAL, "cn_debug_set_spawn_budget: engine and cycles >= 0 required");
     for (int k = 0; k < g->ngroups; ++k) cn_debug_set_spawn_budget(g->grp[k], cycles);
-    if (!g->ngroups && (g->plan.kd || CN_QUAD_PARK)) g->spawn_budget = cycles;   // (parking paths only)
+    if (!g->ngroups) g->spawn_budget = cycles;
     return CN_OK;
 }
 

@@ -117,7 +117,7 @@ class CrowdNavEngine:
         self._step_args = None   # cached output pointers of step() (the buffers above are never reallocated)
         self._seq_fn = None
         self._visible = None     # visible_mask()'s own output, allocated at its first call
-        self.seq_chunk = 32   # steps per multi-step launch (the library's CN_SEQ_CHUNK; set_seq_chunk)
+        self.seq_chunk = 32   # steps per multi-step launch (the library's CN_SEQ_CHUNK, csrc/engine/plan.h; set_seq_chunk)
 
     @classmethod
     def mixed(cls, cfgs, env_group, device=None, scripted=False, scripted_unicycle=False, scripted_dwa=None):

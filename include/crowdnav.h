@@ -817,7 +817,7 @@ int cn_rollout_masked(cn_engine *eng, void *stream, int policy, int T, const cn_
 int cn_debug_set_spawn_budget(cn_engine *eng, long long cycles);
 int cn_debug_spawn_stats(cn_engine *eng, uint32_t *out);
 
-/* Steps per launch of cn_step_seq's multi-step launches (default: the library's CN_SEQ_CHUNK). n = 1 issues one
+/* Steps per launch of cn_step_seq's multi-step launches (default: the library's CN_SEQ_CHUNK, csrc/engine/plan.h). n = 1 issues one
  * cn_step launch per step through the single-step kernels: the in-library A/B and the reference of
  * tests/test_step_seq_fused.py. Results do not depend on n. */
 int cn_debug_set_seq_chunk(cn_engine *eng, int n);

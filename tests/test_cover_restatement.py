@@ -1,4 +1,4 @@
-"""CPU check of the candidate-box cover's arithmetic (GoalCover in csrc/cn_engine.hip: goal_cover_build /
+"""CPU check of the candidate-box cover's arithmetic (GoalCover in csrc/engine/spawn.h: goal_cover_build /
 goal_cover_hit), restated in numpy float32 exactly as the kernel computes it, on crowded square_crossing states
 of the oracle: a cell marked covered must never hold a try the exact test (norm < min_dist) accepts, and
 arow[iy] & acol[ix] must hold every agent whose disc holds the try. The kernel's results are pinned by the GPU

@@ -59,7 +59,7 @@ def _cases(n=60000, seed=0):
 
 
 def _zone_cases(n=40000, seed=1):
-    """The norm zones' own geometry (crowd_sim.py norm-zone penalty; cn_engine.hip:norm_zone): a rectangle
+    """The norm zones' own geometry (crowd_sim.py norm-zone penalty; csrc/engine/geometry.h:norm_zone): a rectangle
     whose corner sits ON the robot's circle at the heading (perturbed radially by up to +-1e-3 r, and
     exactly on it for a quarter of the cases), extending sideways (either side, width 3 r) and forwards
     (1.8 m) -- the configuration where the 64-gon's vertices decide the answer."""

@@ -1,4 +1,4 @@
-"""Multi-step launches whose goal changes run on waves 2 and 3 beside the state stores (CN_SEQ_GOAL_EARLY in
+"""Multi-step launches whose goal changes run on waves 2 and 3 beside the state stores (GOAL_EARLY in
 cn_step_kernel's SEQ instantiations) against the same engine at set_seq_chunk(1): the single-step
 kernels, which keep the goal changes in phase 5 and which the rest of the suite pins to the oracle. The nine outputs
 of the last step and the whole state blob, bit for bit.

@@ -1,4 +1,5 @@
-"""Diagnostic: GPU timeline of the last C4 update from a rocprofv3 kernel trace (tools/gpu_r04s.sh).
+"""Diagnostic: GPU timeline of the last C4 update from a rocprofv3 kernel trace
+(the kernel_trace.csv of a `rocprofv3 --kernel-trace` run of the C4 training).
 
     python tools/c4_timeline.py gpurun_out/r04/c4kt/.../kt_kernel_trace.csv [window_ms]
 

@@ -1,4 +1,4 @@
-// Check of cn_engine.hip's fdiv_lp (the linear programs' short IEEE division) and of fsqrt_lp (the same
+// Check of engine/orca_lp.h's fdiv_lp (the linear programs' short IEEE division) and of fsqrt_lp (the same
 // idea for sqrt: exact, but C2-neutral, not kept) against the compiler's correctly rounded f32 division
 // and sqrt, bit for bit. Division, over random operands with both signs:
 //   sweep 1: numerators with random exponents in [2^-40, 2^40] and zeros, divisors |b| in (RVO_EPSILON, 2^40];
@@ -23,7 +23,7 @@ __device__ __forceinline__ float fdiv_lp_unguarded(float a, float b)
     return __builtin_fmaf(__builtin_fmaf(-b, q1, a), y1, q1);
 }
 
-// as in cn_engine.hip
+// as in engine/orca_lp.h
 __device__ __forceinline__ float fdiv_lp(float a, float b)
 {
     if (__builtin_expect(__builtin_fabsf(a) < 0x1p-96f, 0)) return a / b;

@@ -109,8 +109,6 @@ def run(variant, E=4096, N=10, steps=300):
     L.cn_debug_stamps_r.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
     r = np.zeros(8192 * 2, np.uint64)
     L.cn_debug_stamps_r(r.ctypes.data_as(ctypes.c_void_p), None)
-    print("  lp3 sub-problems over all launches: solved %d, visited by RVO2's loop %d" % (int(r[-14]), int(r[-13])))
-    r[-14:] = 0
     R = r.reshape(-1, 2).astype(np.int64)
     live = np.nonzero(R[:, 1] > 0)[0]
     if len(live):

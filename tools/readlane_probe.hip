@@ -1,12 +1,12 @@
 // Minimal reproduction attempt for the v_readlane broadcast failure noted in DESIGN.md §4 (VERDICT r01
-// item 9). The goal pass of cn_engine.hip walks humans h in index order (a wave-uniform loop), and for a
+// item 9). The goal pass of engine/spawn.h walks humans h in index order (a wave-uniform loop), and for a
 // changing human evaluates J tries at once as (try t, agent a) lanes: the candidate (gx, gy) is computed
 // only on valid lanes (t < J), a ballot of the per-agent hits selects the first try without a hit (win,
 // a loop-carried wave-uniform value), and the winning try's goal is broadcast to the wave. Here the same
 // structure runs three broadcasts of the winner's f64 goal side by side:
 //   (a) __builtin_amdgcn_readlane on the two 32-bit halves (lane = win * NA), the original form;
 //   (b) __shfl (ds_bpermute);
-//   (c) an LDS store by the winning lane + wave barrier + load (the form cn_engine.hip uses).
+//   (c) an LDS store by the winning lane + wave barrier + load (the form engine/spawn.h uses).
 // Every lane checks (a) and (b) against (c); mismatches are counted per wave.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -o /tmp/readlane_probe tools/readlane_probe.hip
 //   /tmp/readlane_probe
