@@ -192,6 +192,15 @@ def lib():
         L.cn_mix_ctl_set.restype = i32
         L.cn_robot_mix.argtypes = [vp, vp, ctypes.c_int, vp, vp, i32, vp, vp, vp]
         L.cn_robot_mix.restype = i32
+    if hasattr(L, "cn_robot_act_regret") or not os.environ.get("CN_LIB_PATH"):   # (an older A/B library lacks them)
+        L.cn_robot_act_regret.argtypes = [vp, vp, ctypes.c_int, vp, vp]
+        L.cn_robot_act_regret.restype = i32
+        L.cn_robot_mix_regret.argtypes = [vp, vp, ctypes.c_int, vp, vp, i32, vp, vp, vp, vp]
+        L.cn_robot_mix_regret.restype = i32
+        L.cn_lattice_soft_fwd.argtypes = [vp, i64, vp, vp, ctypes.c_float, vp, vp, vp]
+        L.cn_lattice_soft_fwd.restype = i32
+        L.cn_lattice_soft_bwd.argtypes = [vp, i64, vp, vp, ctypes.c_float, vp, vp]
+        L.cn_lattice_soft_bwd.restype = i32
     L.cn_attn_pool_fwd.argtypes = [vp, i64, ctypes.c_int, ctypes.c_int] + [vp] * 3
     L.cn_attn_pool_bwd.argtypes = [vp, i64, ctypes.c_int, ctypes.c_int] + [vp] * 5
     try:
@@ -276,6 +285,7 @@ EXPORTED = ["cn_last_error", "cn_version", "cn_config_validate", "cn_create", "c
             "cn_set_graph_mode", "cn_graph_node_counts", "cn_lidar_obs", "cn_lidar_scan", "cn_robot_act", "cn_rollout",
             "cn_rollout_noisy", "cn_rollout_lidar", "cn_rollout_masked", "cn_visible_mask", "cn_spatial_attn_mask_fwd", "cn_spatial_attn_mask_bwd",
             "cn_lattice_act", "cn_lattice_eval_fwd", "cn_lattice_eval_bwd", "cn_mix_ctl_set", "cn_robot_mix",
+            "cn_robot_act_regret", "cn_robot_mix_regret", "cn_lattice_soft_fwd", "cn_lattice_soft_bwd",
             "cn_debug_disc_quad",
             "cn_debug_orca", "cn_debug_copy64", "cn_orca_predict", "cn_orca_predict_kd", "cn_social_force_predict",
             "cn_debug_set_spawn_budget", "cn_debug_spawn_stats", "cn_debug_set_seq_chunk"]

@@ -1,7 +1,8 @@
 // The lattice action head of the unicycle robot (cn_lattice_act / cn_lattice_eval_fwd / cn_lattice_eval_bwd): a
-// categorical distribution over cn_dwa_predict's 64 candidate actions, defined in include/crowdnav.h.
+// categorical distribution over cn_dwa_predict's 64 candidate actions, defined in include/crowdnav.h; and its soft-label
+// loss against the controller's regret rows (cn_lattice_soft_fwd / cn_lattice_soft_bwd).
 //
-// One shape for the three kernels: a 64-lane wavefront owns a row of 64 logits, lane c holds candidate c; a 256-thread
+// One shape for the five kernels: a 64-lane wavefront owns a row of 64 logits, lane c holds candidate c; a 256-thread
 // workgroup serves 4 consecutive rows. Maximum, sum and entropy are xor butterflies (every lane ends with the same
 // bits: each level adds the same two partial sums in both partners), the inclusive prefix sums a 6-step shuffle
 // scan, the lowest / highest lane of a predicate a ballot. No LDS, no scratch, no atomics, no memset; a row's wave
@@ -152,6 +153,69 @@ __global__ __launch_bounds__(256) void cn_lattice_eval_bwd_kernel(int64_t B, con
     dlogits[e * 64 + lane] = d;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Soft labels (cn_lattice_soft_fwd / cn_lattice_soft_bwd, include/crowdnav.h): the cross-entropy of the row's softmax
+// against the target the expert's 64 regrets define at temperature tau, q = softmax(-(r - min r) / tau). The same
+// shape as the three kernels above, which they follow in this file so that those keep their places in the code object.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ float wave_min(float v)
+{
+#pragma unroll
+    for (int o = 32; o; o >>= 1) v = fminf(v, __shfl_xor(v, o));
+    return v;
+}
+
+// the target's pieces in lane `lane`: a = r - min r, x = -(a * inv_tau), t = expf(x), Zt = sum t, q = t / Zt
+struct Target {
+    float a, x, Zt, q;
+};
+
+__device__ __forceinline__ Target target_row(float r, float inv_tau)
+{
+    Target g;
+    g.a = r - wave_min(r);
+    g.x = -(g.a * inv_tau);
+    const float t = expf(g.x);
+    g.Zt = wave_sum(t);
+    g.q = t / g.Zt;
+    return g;
+}
+
+__global__ __launch_bounds__(256) void cn_lattice_soft_fwd_kernel(int64_t B, const float *__restrict__ logits,
+                                                                  const float *__restrict__ regret, float inv_tau,
+                                                                  float *__restrict__ ce, float *__restrict__ kl,
+                                                                  float *__restrict__ logp_best)
+{
+    const int lane = (int)threadIdx.x & 63;
+    const int64_t e = (int64_t)blockIdx.x * ROWS + ((int)threadIdx.x >> 6);
+    if (e >= B) return;   // wave-uniform
+    const Row r = softmax_row(logits[e * 64 + lane]);
+    const Target g = target_row(regret[e * 64 + lane], inv_tau);
+    const bool on = g.q > 0.0f;
+    const float c = -wave_sum(on ? g.q * r.logp : 0.0f);
+    const float Hq = -wave_sum(on ? g.q * (g.x - logf(g.Zt)) : 0.0f);
+    const uint64_t zero = __ballot(g.a == 0.0f);
+    const float lb = __shfl(r.logp, zero ? lowest(zero) : 0);   // (a NaN row has no best candidate)
+    if (lane == 0) {
+        ce[e] = c;
+        if (kl) kl[e] = c - Hq;
+        if (logp_best) logp_best[e] = lb;
+    }
+}
+
+__global__ __launch_bounds__(256) void cn_lattice_soft_bwd_kernel(int64_t B, const float *__restrict__ logits,
+                                                                  const float *__restrict__ regret, float inv_tau,
+                                                                  const float *__restrict__ g_ce,
+                                                                  float *__restrict__ dlogits)
+{
+    const int lane = (int)threadIdx.x & 63;
+    const int64_t e = (int64_t)blockIdx.x * ROWS + ((int)threadIdx.x >> 6);
+    if (e >= B) return;   // wave-uniform
+    const Row r = softmax_row(logits[e * 64 + lane]);
+    const Target g = target_row(regret[e * 64 + lane], inv_tau);
+    dlogits[e * 64 + lane] = g_ce[e] * (r.p / r.Z - g.q);
+}
+
 int lattice_check(const char *who, int64_t rows, std::initializer_list<const void *> need)
 {
     if (rows <= 0 || rows > (int64_t)0x7fffffff * ROWS) return cn_set_error(CN_EINVAL, who);
@@ -204,6 +268,33 @@ int cn_lattice_eval_bwd(void *stream, int64_t B, const float *logits, const int3
     (void)hipGetLastError();
     hipLaunchKernelGGL(cn_lattice_eval_bwd_kernel, dim3(grid_for(B)), dim3(256), 0, (hipStream_t)stream, B, logits,
                        choice, g_logp, g_entropy, dlogits);
+    return launched();
+}
+
+int cn_lattice_soft_fwd(void *stream, int64_t B, const float *logits, const float *regret, float inv_tau, float *ce,
+                        float *kl, float *logp_best)
+{
+    if (lattice_check("cn_lattice_soft_fwd: B > 0 and non-null logits, regret, ce required", B, {logits, regret, ce}))
+        return CN_EINVAL;
+    if (!(inv_tau > 0.0f && inv_tau < __builtin_inff()))   // (a NaN fails both)
+        return cn_set_error(CN_EINVAL, "cn_lattice_soft_fwd: a finite inv_tau > 0 required");
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(cn_lattice_soft_fwd_kernel, dim3(grid_for(B)), dim3(256), 0, (hipStream_t)stream, B, logits,
+                       regret, inv_tau, ce, kl, logp_best);
+    return launched();
+}
+
+int cn_lattice_soft_bwd(void *stream, int64_t B, const float *logits, const float *regret, float inv_tau,
+                        const float *g_ce, float *dlogits)
+{
+    if (lattice_check("cn_lattice_soft_bwd: B > 0 and non-null logits, regret, g_ce, dlogits required", B,
+                      {logits, regret, g_ce, dlogits}))
+        return CN_EINVAL;
+    if (!(inv_tau > 0.0f && inv_tau < __builtin_inff()))
+        return cn_set_error(CN_EINVAL, "cn_lattice_soft_bwd: a finite inv_tau > 0 required");
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(cn_lattice_soft_bwd_kernel, dim3(grid_for(B)), dim3(256), 0, (hipStream_t)stream, B, logits,
+                       regret, inv_tau, g_ce, dlogits);
     return launched();
 }
 

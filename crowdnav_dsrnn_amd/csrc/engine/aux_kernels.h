@@ -2,7 +2,7 @@
 // device functions on caller-given inputs (cn_disc_quad, cn_copy64, cn_orca, cn_orca_kd with RVO2's sequential
 // KdTree, cn_sf_predict, cn_dwa_predict), cn_robot_act's kernels (ORCA, social force, the dynamic window), cn_rollout_noisy's (cn_action_noise_kernel,
 // cn_noise_set_kernel, cn_copy32_kernel), cn_robot_mix's (cn_robot_mix_kernel, cn_mix_ctl_set_kernel), cn_rollout_lidar's (cn_rows_set_kernel, cn_state_rows_kernel), and the
-// two stream-ordered helpers of the host API (cn_ctl_set_kernel, cn_keysnap_kernel). Part of cn_engine.hip's translation unit: included there after the device core, whose
+// two stream-ordered helpers of the host API (cn_ctl_set_kernel, cn_keysnap_kernel), cn_visible_mask's, and last cn_robot_act_regret's two (the dynamic window with its regret row). Part of cn_engine.hip's translation unit: included there after the device core, whose
 // geometry, ORCA and scripted-robot functions these kernels call.
 #pragma once
 
@@ -492,21 +492,30 @@ __global__ void __launch_bounds__(64 * CN_DWA_WAVES) cn_dwa_predict_kernel(int64
 
 // cn_robot_act's: the controller on the engine's state, read in place (the robot's FullState with v = r_dv and the N
 // belief humans); a plain kernel and the twin of a mixed engine's group, whose action goes to row rows[e]
-template <bool MIX>
+// REGRET (cn_robot_act_regret's two kernels, at the end of this file): every lane also stores its candidate's regret
+// (float)(J - J_best) to row o of `regret`, one coalesced 256-byte store per wave. J_best is the chosen lane's own J,
+// read by one shuffle at the wave-uniform `best` (every lane of the wave is active: the wave past the last env left
+// whole above), so the chosen lane subtracts its J from itself: +0.0 exactly. Without REGRET nothing is added.
+template <bool MIX, bool REGRET>
 __device__ __forceinline__ void robot_dwa_body(const cn_state_ptrs &S, int E, int N, double dt, const cn_dwa_params &p,
-                                               float *__restrict__ actions, const int32_t *__restrict__ rows)
+                                               float *__restrict__ actions, const int32_t *__restrict__ rows,
+                                               float *__restrict__ regret)
 {
     const int lane = threadIdx.x & 63;
     const int64_t e = (int64_t)blockIdx.x * CN_DWA_WAVES + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     if (e >= E) return;
     const int64_t h0 = e * N;
     int best;
-    dwa_choose(
+    const double J = dwa_choose(
         [&](int k, double &bx, double &by, double &bvx, double &bvy, double &br) {
             bx = S.b_px[h0 + k]; by = S.b_py[h0 + k]; bvx = S.b_vx[h0 + k]; bvy = S.b_vy[h0 + k]; br = S.b_r[h0 + k];
         },
         N, S.r_px[e], S.r_py[e], S.r_theta[e], S.r_dv[e], S.r_radius[e], S.r_gx[e], S.r_gy[e], S.r_vpref[e], dt, p, lane,
         best);
+    if (REGRET) {
+        const int64_t o = MIX ? (int64_t)rows[e] : e;
+        regret[64 * o + lane] = (float)(J - __shfl(J, best, 64));
+    }
     if (lane == 0) {
         const int64_t o = MIX ? (int64_t)rows[e] : e;
         actions[2 * o] = (float)dwa_grid(best >> 3); actions[2 * o + 1] = (float)dwa_grid(best & 7);
@@ -515,13 +524,13 @@ __device__ __forceinline__ void robot_dwa_body(const cn_state_ptrs &S, int E, in
 __global__ void __launch_bounds__(64 * CN_DWA_WAVES) cn_robot_dwa_kernel(cn_state_ptrs S, int E, int N, double dt,
                                                                         cn_dwa_params p, float *__restrict__ actions)
 {
-    robot_dwa_body<false>(S, E, N, dt, p, actions, nullptr);
+    robot_dwa_body<false, false>(S, E, N, dt, p, actions, nullptr, nullptr);
 }
 __global__ void __launch_bounds__(64 * CN_DWA_WAVES) cn_robot_dwa_mix_kernel(cn_state_ptrs S, int E, int N, double dt,
                                                                             cn_dwa_params p, float *__restrict__ actions,
                                                                             const int32_t *__restrict__ rows)
 {
-    robot_dwa_body<true>(S, E, N, dt, p, actions, rows);
+    robot_dwa_body<true, false>(S, E, N, dt, p, actions, rows, nullptr);
 }
 
 // cn_rollout_noisy outside the fused launches: the perturbation between cn_robot_act's kernel and the step. `act` is
@@ -646,4 +655,28 @@ __global__ void __launch_bounds__(64) cn_visible_mask_kernel(cn_state_ptrs S, in
     const int k = (int)(i - e * NS);
     const int64_t o = MIX ? (int64_t)rows[e] : e;
     mask[o * NS + k] = visible_mask_slot(S, e, k, N, holo, fov, cth);   // (robot.h: the rollout kernels' too)
+}
+
+// ------------------------------------------------------------------------------------------------
+// cn_robot_act_regret's: cn_robot_dwa_kernel / cn_robot_dwa_mix_kernel with the regret row beside the action
+// (robot_dwa_body with REGRET: the same dwa_choose, so the action is the plain kernels' bit for bit). The wave of env
+// e (a group of a mixed engine: of row rows[e]) writes the 64 floats regret[64 * row .. 64 * row + 63] and nothing
+// else of that buffer. The shape rules are the controller's: a wave past the last env leaves whole before any
+// cross-lane read; no LDS, no atomics, no barrier. Last in the file: the kernels above keep their places in the
+// code object.
+// ------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(64 * CN_DWA_WAVES) cn_robot_dwa_regret_kernel(cn_state_ptrs S, int E, int N, double dt,
+                                                                               cn_dwa_params p,
+                                                                               float *__restrict__ actions,
+                                                                               float *__restrict__ regret)
+{
+    robot_dwa_body<false, true>(S, E, N, dt, p, actions, nullptr, regret);
+}
+__global__ void __launch_bounds__(64 * CN_DWA_WAVES) cn_robot_dwa_regret_mix_kernel(cn_state_ptrs S, int E, int N,
+                                                                                   double dt, cn_dwa_params p,
+                                                                                   float *__restrict__ actions,
+                                                                                   const int32_t *__restrict__ rows,
+                                                                                   float *__restrict__ regret)
+{
+    robot_dwa_body<true, true>(S, E, N, dt, p, actions, rows, regret);
 }

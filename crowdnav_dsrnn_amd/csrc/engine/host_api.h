@@ -797,8 +797,9 @@ int cn_lidar_scan(cn_engine *g, void *stream, int beams, double max_range, doubl
 }
 
 // cn_robot_act's launch for a plain engine or a group of a mixed engine (its own count picks the kernel; its envs'
-// actions go to their rows of the caller's buffer)
-static int robot_act_launch(const cn_engine *g, hipStream_t st, int policy, float *actions)
+// actions go to their rows of the caller's buffer). regret != NULL (cn_robot_act_regret, CN_ROBOT_DWA only): the
+// controller's regret kernel in place of the plain one, the envs' regret rows at the same rows of that buffer.
+static int robot_act_launch(const cn_engine *g, hipStream_t st, int policy, float *actions, float *regret = nullptr)
 {
     const cn_config &c = g->c;
     const int32_t *const rows = g->rows;   // a group: the *_mix_kernel twins (the same bodies, the actions at rows[e])
@@ -808,7 +809,13 @@ static int robot_act_launch(const cn_engine *g, hipStream_t st, int policy, floa
     (void)hipGetLastError();   // a stale error of an earlier call (any library) is not this launch's
     if (policy == CN_ROBOT_DWA) {   // (cn_scripted_dwa let it through: a unicycle engine) a wave per env
         const dim3 waves((unsigned)((g->E + CN_DWA_WAVES - 1) / CN_DWA_WAVES)), wg(64 * CN_DWA_WAVES);
-        if (rows)
+        if (regret && rows)
+            hipLaunchKernelGGL(cn_robot_dwa_regret_mix_kernel, waves, wg, 0, st, g->s, g->E, g->N, c.time_step, g->dwa_p,
+                               actions, rows, regret);
+        else if (regret)
+            hipLaunchKernelGGL(cn_robot_dwa_regret_kernel, waves, wg, 0, st, g->s, g->E, g->N, c.time_step, g->dwa_p,
+                               actions, regret);
+        else if (rows)
             hipLaunchKernelGGL(cn_robot_dwa_mix_kernel, waves, wg, 0, st, g->s, g->E, g->N, c.time_step, g->dwa_p, actions,
                                rows);
         else
@@ -887,10 +894,10 @@ int cn_scripted_dwa(cn_engine *g, const cn_dwa_params *p)
 }
 
 // A mixed engine (after cn_mixed_scripted): one controller launch per group, side by side like the groups' step
-// launches.
-int cn_robot_act(cn_engine *g, void *stream, int policy, float *actions)
+// launches. regret != NULL: cn_robot_act_regret, which has checked its own arguments and that the policy is the
+// dynamic window.
+static int robot_act_checked(cn_engine *g, void *stream, int policy, float *actions, float *regret)
 {
-    if (!g) return set_err(CN_EINVAL, "null engine");
     const bool dwa = policy == CN_ROBOT_DWA && g->dwa;   // (without cn_scripted_dwa the id is unknown, as ever)
     if ((policy != CN_ROBOT_ORCA && policy != CN_ROBOT_SOCIAL_FORCE && !dwa) || !actions)
         return set_err(CN_EINVAL, "cn_robot_act: policy CN_ROBOT_ORCA / CN_ROBOT_SOCIAL_FORCE and actions required");
@@ -900,12 +907,39 @@ int cn_robot_act(cn_engine *g, void *stream, int policy, float *actions)
         return set_err(CN_EUNSUPPORTED, g->ngroups ? "cn_robot_act: not on a unicycle mixed engine (the controllers return ActionXY)"
                                                    : "cn_robot_act: the controllers return ActionXY (holonomic engines only)");
     const hipStream_t st = (hipStream_t)stream;
-    if (!g->ngroups) return robot_act_launch(g, st, policy, actions);
+    if (!g->ngroups) return robot_act_launch(g, st, policy, actions, regret);
     int rc = mix_fork(g, st);
     if (rc) return rc;
-    for (int k = 0; k < g->ngroups && !rc; ++k) rc = robot_act_launch(g->grp[k], mix_stream(g, k, st), policy, actions);
+    for (int k = 0; k < g->ngroups && !rc; ++k)
+        rc = robot_act_launch(g->grp[k], mix_stream(g, k, st), policy, actions, regret);
     const int rj = mix_join(g, st);
     return rc ? rc : rj;
+}
+
+int cn_robot_act(cn_engine *g, void *stream, int policy, float *actions)
+{
+    if (!g) return set_err(CN_EINVAL, "null engine");
+    return robot_act_checked(g, stream, policy, actions, nullptr);
+}
+
+// cn_robot_act_regret's and cn_robot_mix_regret's rule for the policy: only the dynamic window has a candidate set
+static int regret_policy_check(const cn_engine *g, int policy)
+{
+    if (policy == CN_ROBOT_ORCA || policy == CN_ROBOT_SOCIAL_FORCE)
+        return set_err(CN_EUNSUPPORTED, "regret rows: ORCA and the social force have no candidate set (CN_ROBOT_DWA only)");
+    if (policy != CN_ROBOT_DWA || !g->dwa)
+        return set_err(CN_EINVAL, "regret rows: policy CN_ROBOT_DWA on an engine cn_scripted_dwa enabled it for required");
+    return CN_OK;
+}
+
+// cn_robot_act with the controller's regret kernel in place of the plain one: the same launch count.
+int cn_robot_act_regret(cn_engine *g, void *stream, int policy, float *actions, float *regret)
+{
+    if (!g) return set_err(CN_EINVAL, "null engine");
+    if (!actions || !regret) return set_err(CN_EINVAL, "cn_robot_act_regret: actions and regret required");
+    const int rc = regret_policy_check(g, policy);
+    if (rc) return rc;
+    return robot_act_checked(g, stream, policy, actions, regret);
 }
 
 // By value through a kernel, as cn_rollout_noisy hands its block over: stream-ordered, a kernel node when captured.
@@ -922,13 +956,12 @@ int cn_mix_ctl_set(void *stream, cn_mix_ctl *dev, const cn_mix_ctl *value)
 
 // cn_robot_act into `label` (its checks, its launches, a mixed engine's fork and join), then one launch over all E
 // rows on the caller's stream.
-int cn_robot_mix(cn_engine *g, void *stream, int policy, const float *learner, const cn_mix_ctl *ctl, int32_t t,
-                 float *label, float *executed, uint8_t *flags)
+static int robot_mix_checked(cn_engine *g, void *stream, int policy, const float *learner, const cn_mix_ctl *ctl,
+                             int32_t t, float *label, float *executed, uint8_t *flags, float *regret)
 {
-    if (!g) return set_err(CN_EINVAL, "null engine");
     if (!learner || !ctl || !label || !executed || !flags || t < 0)
         return set_err(CN_EINVAL, "cn_robot_mix: learner, ctl, label, executed, flags and t >= 0 required");
-    const int rc = cn_robot_act(g, stream, policy, label);   // (every check of it comes before its first launch)
+    const int rc = robot_act_checked(g, stream, policy, label, regret);   // (every check of it comes before its first launch)
     if (rc) return rc;
     (void)hipGetLastError();
     hipLaunchKernelGGL(cn_robot_mix_kernel, dim3((unsigned)((g->E + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
@@ -936,6 +969,26 @@ int cn_robot_mix(cn_engine *g, void *stream, int policy, const float *learner, c
                        (const uint2 *)label, (uint2 *)executed, flags);
     HIPCHK(hipGetLastError());
     return CN_OK;
+}
+
+int cn_robot_mix(cn_engine *g, void *stream, int policy, const float *learner, const cn_mix_ctl *ctl, int32_t t,
+                 float *label, float *executed, uint8_t *flags)
+{
+    if (!g) return set_err(CN_EINVAL, "null engine");
+    return robot_mix_checked(g, stream, policy, learner, ctl, t, label, executed, flags, nullptr);
+}
+
+// cn_robot_mix with cn_robot_act_regret's launch(es) in place of cn_robot_act's
+int cn_robot_mix_regret(cn_engine *g, void *stream, int policy, const float *learner, const cn_mix_ctl *ctl, int32_t t,
+                        float *label, float *executed, uint8_t *flags, float *regret)
+{
+    if (!g) return set_err(CN_EINVAL, "null engine");
+    if (!regret) return set_err(CN_EINVAL, "cn_robot_mix_regret: regret required");
+    if (!learner || !ctl || !label || !executed || !flags || t < 0)
+        return set_err(CN_EINVAL, "cn_robot_mix_regret: learner, ctl, label, executed, flags and t >= 0 required");
+    const int rc = regret_policy_check(g, policy);
+    if (rc) return rc;
+    return robot_mix_checked(g, stream, policy, learner, ctl, t, label, executed, flags, regret);
 }
 
 // cn_visible_mask's launch for a plain engine or a group of a mixed engine (its envs' rows of the [E][NS] buffer)

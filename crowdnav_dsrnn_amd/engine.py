@@ -295,11 +295,23 @@ class CrowdNavEngine:
 
     ROBOT_POLICIES = {"orca": 0, "social_force": 1, "dwa": 2}   # CN_ROBOT_ORCA / CN_ROBOT_SOCIAL_FORCE / CN_ROBOT_DWA
 
-    def robot_act(self, policy, out=None):
+    def _regret_arg(self, who, regret):
+        """robot_act's / robot_mix's `regret`: a contiguous float32 (E, 64) tensor on the engine's device."""
+        t = self.torch
+        if (not isinstance(regret, t.Tensor) or regret.dtype != t.float32 or regret.device != self.device
+                or not regret.is_contiguous() or regret.numel() != self.E * 64):
+            raise ValueError("%s: regret must be a contiguous float32 (E, 64) tensor on %s" % (who, self.device))
+        return regret
+
+    def robot_act(self, policy, out=None, regret=None):
         """The scripted robot's action for the engine's current state (cn_robot_act): (E, 2) float32 on the
         device, what a fresh policy_factory['orca' | 'social_force'] object predicts from the robot's state and
         its belief of the humans ('dwa', after scripted_dwa: what policy_factory.dwa_predict chooses for them). Into `out` when given, else into a buffer the engine owns (overwritten by the
-        next call). One launch, no host sync."""
+        next call). One launch, no host sync.
+        regret: an (E, 64) float32 tensor that receives, beside the action, the controller's regret row of every env
+        (cn_robot_act_regret; policy_factory.dwa_regret restates it): (float)(J_c - J_best) of the 64 candidates, 0 at
+        the choice. 'dwa' only -- the other two controllers have no candidate set and the engine refuses them. The
+        same single launch; the action is the one robot_act('dwa') writes, bit for bit."""
         t = self.torch
         if policy not in self.ROBOT_POLICIES:
             raise ValueError("robot_act: policy %r (one of %s)" % (policy, sorted(self.ROBOT_POLICIES)))
@@ -308,6 +320,12 @@ class CrowdNavEngine:
         elif (out.dtype != t.float32 or out.device != self.device or not out.is_contiguous()
                 or out.numel() != self.E * 2):
             raise ValueError("robot_act: out must be a contiguous float32 (E, 2) tensor on %s" % self.device)
+        if regret is not None:
+            self._regret_arg("robot_act", regret)
+            with t.cuda.device(self.device):
+                _lib.check(_lib.lib().cn_robot_act_regret(self._h, self._stream(), self.ROBOT_POLICIES[policy],
+                                                          out.data_ptr(), regret.data_ptr()))
+            return out
         with t.cuda.device(self.device):
             _lib.check(_lib.lib().cn_robot_act(self._h, self._stream(), self.ROBOT_POLICIES[policy], out.data_ptr()))
         return out
@@ -336,13 +354,15 @@ class CrowdNavEngine:
             _lib.check(_lib.lib().cn_mix_ctl_set(self._stream(), ctl.data_ptr(), ctypes.byref(v)))
         return ctl
 
-    def robot_mix(self, policy, learner, ctl, t, label=None, executed=None, flags=None):
+    def robot_mix(self, policy, learner, ctl, t, label=None, executed=None, flags=None, regret=None):
         """The learner in the loop (cn_robot_mix): label = robot_act(policy) of the engine's current state, and per
         env a coin of probability ctl.beta -- word z of philox(counter step0 + t, key (seed, global env index)),
         policy_factory.mix_coin -- picks executed = label (taken) or `learner` (E, 2) float32, copied as bits.
         flags (E,) uint8: bit 0 = the label was taken, bit 1 = learner == label as bits. Returns (label, executed,
         flags), each into the tensor given or a fresh one. beta, seed and step0 are read on the device when the
-        launch runs (set_mix_ctl); t >= 0 is the launch's own. robot_act's launch(es) + one more; no host sync."""
+        launch runs (set_mix_ctl); t >= 0 is the launch's own. robot_act's launch(es) + one more; no host sync.
+        regret: robot_act's -- an (E, 64) float32 tensor for the controller's regret rows ('dwa' only), written by the
+        labelling launch itself (cn_robot_mix_regret); label, executed and flags are what they are without it."""
         tc = self.torch
         if policy not in self.ROBOT_POLICIES:
             raise ValueError("robot_mix: policy %r (one of %s)" % (policy, sorted(self.ROBOT_POLICIES)))
@@ -366,6 +386,13 @@ class CrowdNavEngine:
             raise ValueError("robot_mix: flags must be a contiguous uint8 (E,) tensor on %s" % self.device)
         if len({learner.data_ptr(), label.data_ptr(), executed.data_ptr()}) != 3:
             raise ValueError("robot_mix: learner, label and executed must be three different buffers")
+        if regret is not None:
+            self._regret_arg("robot_mix", regret)
+            with tc.cuda.device(self.device):
+                _lib.check(_lib.lib().cn_robot_mix_regret(self._h, self._stream(), self.ROBOT_POLICIES[policy],
+                                                          learner.data_ptr(), ctl.data_ptr(), t, label.data_ptr(),
+                                                          executed.data_ptr(), flags.data_ptr(), regret.data_ptr()))
+            return label, executed, flags
         with tc.cuda.device(self.device):
             _lib.check(_lib.lib().cn_robot_mix(self._h, self._stream(), self.ROBOT_POLICIES[policy], learner.data_ptr(),
                                                ctl.data_ptr(), t, label.data_ptr(), executed.data_ptr(),

@@ -379,26 +379,32 @@ class CrowdNavVecEnv:
             out = (self._srnn_extras(out[0]),) + tuple(out[1:])
         return out
 
-    def robot_act(self, policy):
+    def robot_act(self, policy, regret=None):
         """The scripted robot's action ('orca' / 'social_force') for the state the last reset / step returned:
         (E, 2) float32 on the engine's GPU (CrowdNavEngine.robot_act; no host synchronisation). An env of varying
         human count (sim.human_nums) with sim.human_nums_scripted: every env by the controller of its own count;
         without that opt-in: UnsupportedConfig. A unicycle env with robot.scripted_unicycle: the unicycle action
         (dv, dtheta) the tracking law derives from the controller's velocity, what step_device takes; without that
         opt-in the engine refuses. 'dwa': a unicycle env with robot.scripted_dwa (the dynamic-window controller's own
-        unicycle action); without that opt-in the engine refuses it as an unknown policy."""
+        unicycle action); without that opt-in the engine refuses it as an unknown policy.
+        regret: an (E, 64) float32 tensor on the engine's GPU for the controller's regret rows ('dwa' only;
+        CrowdNavEngine.robot_act), written by the same launch."""
         _no_varied(self.config, "robot_act")
-        return self.engine.robot_act(policy)
+        if regret is None:
+            return self.engine.robot_act(policy)
+        return self.engine.robot_act(policy, regret=regret)
 
-    def robot_mix(self, policy, learner, ctl, t, label=None, executed=None, flags=None):
+    def robot_mix(self, policy, learner, ctl, t, label=None, executed=None, flags=None, regret=None):
         """The learner in the loop (CrowdNavEngine.robot_mix -> cn_robot_mix): robot_act(policy) of the state the last
         reset / step returned as `label`, and per env a coin of probability beta -- the device block `ctl`
         (engine.mix_ctl() / set_mix_ctl) -- that makes `executed` the label or the `learner`'s (E, 2) action, what
         step_device then takes. Returns (label, executed, flags); no host synchronisation. The envs it serves are
         robot_act's: the same opt-ins, the same UnsupportedConfig on an env of varying human count without
-        sim.human_nums_scripted."""
+        sim.human_nums_scripted. regret: robot_act's, the expert's regret rows beside its labels ('dwa' only)."""
         _no_varied(self.config, "robot_mix")
-        return self.engine.robot_mix(policy, learner, ctl, t, label=label, executed=executed, flags=flags)
+        if regret is None:
+            return self.engine.robot_mix(policy, learner, ctl, t, label=label, executed=executed, flags=flags)
+        return self.engine.robot_mix(policy, learner, ctl, t, label=label, executed=executed, flags=flags, regret=regret)
 
     def rollout(self, policy, T, obs_every_step=True, out=None, noise=None):
         """T closed-loop steps of the scripted robot ('orca' / 'social_force') from the state the last reset / step

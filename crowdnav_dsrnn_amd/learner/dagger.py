@@ -32,7 +32,21 @@ the value regression), the policy / observation pairs are the ones it accepts, a
 RolloutTrainer exactly as a cloned one does. An env with sim.visible_masks needs no sim.visible_masks_scripted here:
 the loop goes through step_device, which returns the mask. An env with sim.human_nums needs sim.human_nums_scripted
 (robot_act's rule) and runs eagerly (graph mode is the plain engine's).
+
+soft_tau = tau > 0 (expert 'dwa' with the lattice head; None, the default: the hard label above, with exactly the calls
+made without this option) fits the head to ALL 64 of the expert's candidate costs instead of its one choice. The
+labelling launch of every step also writes the expert's regret row (envs.robot_mix(..., regret=): (float)(J_c - J_best),
+0 at the choice) into a fixed (T, E, 64) buffer -- the captured chunk replays into it -- which _keep copies to the
+chunk's ring slot, and fit() minimises the cross-entropy against the target softmax(-regret / tau)
+(Policy.evaluate_soft -> cn_lattice_soft_fwd / _bwd) plus the same value regression. Many of the 64 candidates are
+near-ties, and among exact ties the hard label is "the lowest index": the soft target spreads its mass over every
+candidate within about tau of the best and tells the head which others are catastrophic. update() keeps 'nll' as the
+HARD label's negative log-likelihood (-logp of the expert's choice, from the same pass), so that column compares with
+hard runs, and adds 'soft_ce', 'kl' (KL(target || policy)) and 'soft_tau'. BehaviourCloning has no such option -- its
+data comes from cn_rollout*, which record no regret rows; DAgger(beta=1, beta_decay=1, soft_tau=tau) is the expert's
+clean rollout with soft labels.
 """
+import math
 import os
 import time
 import warnings
@@ -51,11 +65,20 @@ class DAgger(BehaviourCloning):
 
     def __init__(self, config, envs, actor_critic, expert="dwa", beta=1.0, beta_decay=0.5, beta_min=0.0, seed=0,
                  num_steps=None, num_mini_batch=None, epochs=1, lr=None, value_coef=0.5, aggregate=1,
-                 deterministic=True, graphs=None):
+                 deterministic=True, graphs=None, soft_tau=None):
         from ..config import UnsupportedConfig
         from ..policy_factory import ScriptedRobot
 
         ScriptedRobot.check(envs, expert)   # before anything touches the GPU, as everything down to the optimizer
+        if soft_tau is not None:
+            soft_tau = float(soft_tau)
+            if not (math.isfinite(soft_tau) and soft_tau > 0.0):
+                raise ValueError("DAgger: soft_tau must be a finite temperature > 0 (None: the hard label), got %r"
+                                 % (soft_tau,))
+            if expert != "dwa" or getattr(actor_critic, "head", None) != "lattice":
+                raise UnsupportedConfig("DAgger: soft_tau needs expert='dwa' (the one controller with a candidate set) "
+                                        "and a policy with the lattice head (robot.action_head = 'lattice')")
+        self.soft_tau = soft_tau
         for name, v in (("beta", beta), ("beta_decay", beta_decay), ("beta_min", beta_min)):
             if not 0.0 <= float(v) <= 1.0:   # (a NaN fails both)
                 raise ValueError("DAgger: %s in [0, 1] required, got %r" % (name, v))
@@ -108,6 +131,10 @@ class DAgger(BehaviourCloning):
         self.proposed = torch.zeros((T, E, 2), dtype=torch.float32, device=dev)   # the learner's own
         self.executed = torch.zeros((T, E, 2), dtype=torch.float32, device=dev)   # what the step took
         self.flags = torch.zeros((T, E), dtype=torch.uint8, device=dev)           # bit 0 took the expert, bit 1 agree
+        if self.soft_tau is not None:   # the expert's regret rows: the live chunk's (fixed addresses), and per ring slot
+            self.regret = torch.zeros((T, E, 64), dtype=torch.float32, device=dev)
+            self.ring_regret = ([self.regret] if self.aggregate == 1
+                                else [torch.zeros_like(self.regret) for _ in range(self.aggregate)])
         self.done = torch.zeros((T, E), dtype=torch.uint8, device=dev)
         self.event = torch.zeros((T, E), dtype=torch.int8, device=dev)
         self._ones = torch.ones((E, 1), device=dev)
@@ -144,8 +171,12 @@ class DAgger(BehaviourCloning):
             value, action, logp, hxs = self.ac.act(obs_s, r.hidden(t), r.masks[t], deterministic=self.deterministic,
                                                    **({"out_hxs": r.hidden_slot()} if self.srnn else {}))
             action = action.contiguous()
-            self.envs.robot_mix(self.expert, action, self.ctl, t, label=self.labels[t], executed=self.executed[t],
-                                flags=self.flags[t])
+            if self.soft_tau is None:
+                self.envs.robot_mix(self.expert, action, self.ctl, t, label=self.labels[t], executed=self.executed[t],
+                                    flags=self.flags[t])
+            else:   # the same launches, the labelling one writing the regret rows too
+                self.envs.robot_mix(self.expert, action, self.ctl, t, label=self.labels[t], executed=self.executed[t],
+                                    flags=self.flags[t], regret=self.regret[t])
             obs, reward, done, event, _, _, _ = self.envs.step_device(self.executed[t])
             masks = torch.rsub(done.unsqueeze(1), 1.0)   # 1 - done as float32 (one kernel)
             r.insert(obs, hxs, self.labels[t], logp, value, reward.unsqueeze(1), masks, self._ones)
@@ -203,6 +234,13 @@ class DAgger(BehaviourCloning):
             return [self.rollouts]
         return [self.ring[j % K] for j in range(max(0, n - K), n)]
 
+    def held_regret(self):
+        """soft_tau: the (T, E, 64) regret rows of the chunks held(), in its order."""
+        K, n = self.aggregate, self.chunks
+        if K == 1:
+            return [self.regret]
+        return [self.ring_regret[j % K] for j in range(max(0, n - K), n)]
+
     @torch.no_grad()
     def _keep(self):
         """The chunk just collected (returns computed) into its ring slot: what recurrent_generator and the loss
@@ -221,10 +259,51 @@ class DAgger(BehaviourCloning):
         s.masks.copy_(r.masks)
         s.actions.copy_(r.actions)
         s.returns.copy_(r.returns)
+        if self.soft_tau is not None:
+            self.ring_regret[(self.chunks - 1) % self.aggregate].copy_(self.regret)
+
+    @torch.no_grad()
+    def chunk_soft_ce(self):
+        """soft_tau: the live chunk's mean soft cross-entropy under the current weights (device scalar); chunk_nll()'s
+        counterpart."""
+        r, T, E = self.rollouts, self.num_steps, self.envs.num_envs
+        with self._sequence_shape(E):
+            obs = self._obs(lambda v: v[:-1].reshape(T * E, *v.shape[2:]))
+            hxs = self._hxs(lambda v: v[0])
+            return self.ac.evaluate_soft(obs, hxs, r.masks[:-1].reshape(T * E, 1), self.regret.reshape(T * E, 64),
+                                         self.soft_tau)[1].mean()
+
+    def _fit_soft(self, epochs=None):
+        """fit() with soft labels: the same walk with each minibatch's env indices (with_ind: the same randperm draw),
+        which select the chunk's regret rows in the minibatch's (step, env) order; minimises ce.mean() + value_coef *
+        value_loss. Device tensor [sum of hard nll, sum of value_loss, sum of soft ce, sum of kl], and the number."""
+        acc, n = torch.zeros(4, dtype=torch.float64, device=self.device), 0
+        B = self.envs.num_envs // self.num_mini_batch
+        with self._sequence_shape(B):
+            for _ in range(self.epochs if epochs is None else int(epochs)):
+                for s, reg in zip(self.held(), self.held_regret()):
+                    for obs_b, hxs_b, _, _, return_b, masks_b, _, _, ind in s.recurrent_generator(
+                            s.returns[:-1], self.num_mini_batch, with_ind=True):
+                        regret_b = reg.index_select(1, ind).reshape(-1, 64)
+                        values, ce, kl, logp_best, _ = self.ac.evaluate_soft(obs_b, hxs_b, masks_b, regret_b,
+                                                                             self.soft_tau)
+                        soft_ce = ce.mean()
+                        value_loss = 0.5 * (values - return_b).pow(2).mean()
+                        self.optimizer.zero_grad()
+                        (soft_ce + self.value_coef * value_loss if self.value_coef else soft_ce).backward()
+                        nn.utils.clip_grad_norm_(self.ac.parameters(), self.max_grad_norm)
+                        self.optimizer.step()
+                        acc += torch.stack([-logp_best.mean(), value_loss.detach(), soft_ce.detach(),
+                                            kl.mean()]).double()
+                        n += 1
+        return acc, n
 
     def fit(self, epochs=None):
         """`epochs` passes over every chunk held, oldest first (recurrent_generator's minibatches of each): device
-        tensor [sum of nll, sum of value_loss] over the minibatches, and their number."""
+        tensor [sum of nll, sum of value_loss] over the minibatches, and their number. With soft_tau: _fit_soft, whose
+        tensor carries two more sums."""
+        if self.soft_tau is not None:
+            return self._fit_soft(epochs)
         acc, n = torch.zeros(2, dtype=torch.float64, device=self.device), 0
         B = self.envs.num_envs // self.num_mini_batch
         with self._sequence_shape(B):
@@ -245,7 +324,9 @@ class DAgger(BehaviourCloning):
         """One chunk under the mixture policy + `epochs` passes over the chunks held: BehaviourCloning.update()'s dict
         plus 'beta' (the chunk's), 'took_expert' (share of env-steps whose executed action was the expert's) and
         'agree' (share whose learner action equalled the label bit for bit). rollout_s / update_s are GPU time
-        between HIP events on the current stream; one host synchronisation, at the end."""
+        between HIP events on the current stream; one host synchronisation, at the end. With soft_tau: 'nll' stays the
+        hard label's (-logp of the expert's choice), and the dict gains 'soft_ce' (the loss fitted), 'kl' and
+        'soft_tau'."""
         c = self.config
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if self.device.type == "cuda" else None
         t0 = time.perf_counter()
@@ -276,6 +357,11 @@ class DAgger(BehaviourCloning):
         else:
             rollout_s, update_s = t1 - t0, t2 - t1
         steps = float(self.flags.numel())
-        return {"nll": vals[0], "value_loss": vals[1], "episodes": int(vals[2]), "success": int(vals[3]),
-                "collision": int(vals[4]), "timeout": int(vals[5]), "rollout_s": rollout_s, "update_s": update_s,
-                "host_s": t2 - t0, "beta": self.beta, "took_expert": vals[6] / steps, "agree": vals[7] / steps}
+        soft = {}
+        if self.soft_tau is not None:   # acc is [nll, value_loss, soft_ce, kl]: the counts follow those four
+            soft = {"soft_ce": vals[2], "kl": vals[3], "soft_tau": self.soft_tau}
+            vals = vals[:2] + vals[4:]
+        return dict({"nll": vals[0], "value_loss": vals[1], "episodes": int(vals[2]), "success": int(vals[3]),
+                     "collision": int(vals[4]), "timeout": int(vals[5]), "rollout_s": rollout_s, "update_s": update_s,
+                     "host_s": t2 - t0, "beta": self.beta, "took_expert": vals[6] / steps, "agree": vals[7] / steps},
+                    **soft)

@@ -179,9 +179,11 @@ class SRNNRolloutStorage:
                 else:
                     ret[s] = ret[s + 1] * gamma * m[s + 1] + r[s]
 
-    def recurrent_generator(self, advantages, num_mini_batch):
+    def recurrent_generator(self, advantages, num_mini_batch, with_ind=False):
         """storage.py:223-292: minibatches of whole environments, (T*N, ...) in (step, env) order and the
-        step-0 hidden states."""
+        step-0 hidden states. with_ind: the minibatch's env indices `ind` (n,), on the storage's device, are appended
+        to each tuple -- x.index_select(1, ind) flattened is the row order of a (T, E, ...) record kept beside the
+        storage; the randperm draw is the same either way."""
         E = self.rewards.size(1)
         assert E >= num_mini_batch, "PPO requires num_processes >= num_mini_batch"
         n = E // num_mini_batch
@@ -191,13 +193,14 @@ class SRNNRolloutStorage:
             ind = perm[start:start + n].to(self.rewards.device)
             obs_b = {k: v[:-1].index_select(1, ind) for k, v in self.obs.items()}
             hxs_b = {k: v[0].index_select(0, ind) for k, v in self.recurrent_hidden_states.items()}
-            yield (_flatten_helper(T, n, obs_b), hxs_b,
-                   _flatten_helper(T, n, self.actions.index_select(1, ind)),
-                   _flatten_helper(T, n, self.value_preds[:-1].index_select(1, ind)),
-                   _flatten_helper(T, n, self.returns[:-1].index_select(1, ind)),
-                   _flatten_helper(T, n, self.masks[:-1].index_select(1, ind)),
-                   _flatten_helper(T, n, self.action_log_probs.index_select(1, ind)),
-                   _flatten_helper(T, n, advantages.index_select(1, ind)))
+            batch = (_flatten_helper(T, n, obs_b), hxs_b,
+                     _flatten_helper(T, n, self.actions.index_select(1, ind)),
+                     _flatten_helper(T, n, self.value_preds[:-1].index_select(1, ind)),
+                     _flatten_helper(T, n, self.returns[:-1].index_select(1, ind)),
+                     _flatten_helper(T, n, self.masks[:-1].index_select(1, ind)),
+                     _flatten_helper(T, n, self.action_log_probs.index_select(1, ind)),
+                     _flatten_helper(T, n, advantages.index_select(1, ind)))
+            yield batch + (ind,) if with_ind else batch
 
     def feed_forward_generator(self, advantages, num_mini_batch=None, mini_batch_size=None):
         """storage.py:179-221 (non-recurrent policies)."""
@@ -276,8 +279,9 @@ class RolloutStorage(SRNNRolloutStorage):
         self.masks[0].copy_(self.masks[-1])
         self.bad_masks[0].copy_(self.bad_masks[-1])
 
-    def recurrent_generator(self, advantages, num_mini_batch):
-        """storage.py:449-508 (same torch.randperm draw as the reference)."""
+    def recurrent_generator(self, advantages, num_mini_batch, with_ind=False):
+        """storage.py:449-508 (same torch.randperm draw as the reference). with_ind: as SRNNRolloutStorage's, the
+        minibatch's env indices appended to each tuple."""
         E = self.rewards.size(1)
         assert E >= num_mini_batch, "PPO requires num_processes >= num_mini_batch"
         n = E // num_mini_batch
@@ -285,14 +289,15 @@ class RolloutStorage(SRNNRolloutStorage):
         T = self.num_steps
         for start in range(0, E, n):
             ind = perm[start:start + n].to(self.rewards.device)
-            yield (_flatten_helper(T, n, self.obs[:-1].index_select(1, ind)),
-                   self.recurrent_hidden_states[0].index_select(0, ind),
-                   _flatten_helper(T, n, self.actions.index_select(1, ind)),
-                   _flatten_helper(T, n, self.value_preds[:-1].index_select(1, ind)),
-                   _flatten_helper(T, n, self.returns[:-1].index_select(1, ind)),
-                   _flatten_helper(T, n, self.masks[:-1].index_select(1, ind)),
-                   _flatten_helper(T, n, self.action_log_probs.index_select(1, ind)),
-                   _flatten_helper(T, n, advantages.index_select(1, ind)))
+            batch = (_flatten_helper(T, n, self.obs[:-1].index_select(1, ind)),
+                     self.recurrent_hidden_states[0].index_select(0, ind),
+                     _flatten_helper(T, n, self.actions.index_select(1, ind)),
+                     _flatten_helper(T, n, self.value_preds[:-1].index_select(1, ind)),
+                     _flatten_helper(T, n, self.returns[:-1].index_select(1, ind)),
+                     _flatten_helper(T, n, self.masks[:-1].index_select(1, ind)),
+                     _flatten_helper(T, n, self.action_log_probs.index_select(1, ind)),
+                     _flatten_helper(T, n, advantages.index_select(1, ind)))
+            yield batch + (ind,) if with_ind else batch
 
     def feed_forward_generator(self, advantages, num_mini_batch=None, mini_batch_size=None):
         """storage.py:408-447."""

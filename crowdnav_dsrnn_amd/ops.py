@@ -15,9 +15,13 @@ masked_gru(...)     — the mask-segmented GRU of the three DSRNN RNNs over a (T
 lattice_act(...) / lattice_evaluate(...) — the lattice action head of the unicycle robot: sample or mode with its
                       log-probability (cn_lattice_act), log-probability and entropy of given actions with their
                       gradient (cn_lattice_eval_fwd / _bwd); CPU tensors run the torch restatements (*_torch).
+lattice_soft_ce(...) — the head's cross-entropy against the soft target the DWA expert's 64 regrets define
+                      (cn_lattice_soft_fwd / _bwd); CPU tensors: lattice_soft_ce_torch.
 gru_infer_step(...) — one no-autograd step of the same GRU for act(): reads the state through strided views
                       and writes the new state straight into the (B, N + 1, H) layout (cn_gru_fwd_fused).
 """
+import math
+
 import numpy as np
 import torch
 
@@ -642,6 +646,83 @@ def lattice_evaluate(logits, actions):
         return lattice_evaluate_torch(logits, actions)
     logp, ent, _ = _LatticeEvaluate.apply(logits, actions)
     return logp, ent
+
+
+def _soft_inv_tau(tau):
+    """1 / tau as the float32 the kernels take; tau and it finite and > 0 (tau -> 0 is the hard label's own path)."""
+    tau = float(tau)
+    inv = 1.0 / tau if math.isfinite(tau) and tau > 0.0 else 0.0
+    inv = float(np.float32(inv)) if inv <= float(np.finfo(np.float32).max) else math.inf
+    if not (math.isfinite(inv) and inv > 0.0):
+        raise ValueError("lattice_soft_ce: a finite tau > 0 (with a finite float32 1 / tau > 0) required, got %r" % (tau,))
+    return inv
+
+
+def lattice_soft_ce_torch(logits, regret, tau):
+    """The torch restatement of cn_lattice_soft_fwd (autograd supplies cn_lattice_soft_bwd): logits (B, 64), regret
+    (B, 64) float32 rows of the expert's regrets, tau > 0 -> (ce, kl, logp_best), each (B,), include/crowdnav.h's
+    definition in float32: the target q = softmax(-(r - min r) / tau), ce = H(q, softmax l), kl = ce - H(q), logp_best
+    the log-probability of the lowest candidate of regret min r. Candidates of zero target probability add nothing
+    (no 0 * -inf). The gradient reaches the logits through ce alone; the target carries none."""
+    inv_tau = torch.tensor(_soft_inv_tau(tau), dtype=torch.float32, device=logits.device)
+    lsm = torch.log_softmax(logits.float(), -1)
+    with torch.no_grad():
+        r = regret.float()
+        a = r - r.min(-1, keepdim=True).values
+        x = -(a * inv_tau)
+        t = torch.exp(x)
+        Zt = t.sum(-1, keepdim=True)
+        q = t / Zt
+        on = q > 0
+        Hq = -torch.where(on, q * (x - torch.log(Zt)), torch.zeros_like(q)).sum(-1)
+        lane = torch.arange(LATTICE, device=logits.device)
+        best = torch.where(a == 0, lane, LATTICE).amin(-1).clamp(max=LATTICE - 1)
+    ce = -torch.where(on, q * lsm, torch.zeros_like(q)).sum(-1)
+    return ce, (ce - Hq).detach(), lsm.detach().gather(1, best.unsqueeze(1)).squeeze(1)
+
+
+class _LatticeSoftCE(torch.autograd.Function):
+    """cn_lattice_soft_fwd / cn_lattice_soft_bwd: only the logits and the regrets are kept for the backward, which
+    recomputes both softmaxes."""
+
+    @staticmethod
+    def forward(ctx, logits, regret, inv_tau):
+        logits, regret = _c(logits), _c(regret)
+        B, dev = logits.shape[0], logits.device
+        ce, kl, best = (torch.empty((B,), dtype=torch.float32, device=dev) for _ in range(3))
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().cn_lattice_soft_fwd(_stream(dev), B, logits.data_ptr(), regret.data_ptr(), inv_tau,
+                                                      ce.data_ptr(), kl.data_ptr(), best.data_ptr()))
+        ctx.save_for_backward(logits, regret)
+        ctx.inv_tau = inv_tau
+        ctx.mark_non_differentiable(kl, best)
+        return ce, kl, best
+
+    @staticmethod
+    def backward(ctx, g_ce, _g_kl, _g_best):
+        logits, regret = ctx.saved_tensors
+        B, dev = logits.shape[0], logits.device
+        g_ce = _c(g_ce).reshape(B)
+        dlogits = torch.empty_like(logits)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().cn_lattice_soft_bwd(_stream(dev), B, logits.data_ptr(), regret.data_ptr(), ctx.inv_tau,
+                                                      g_ce.data_ptr(), dlogits.data_ptr()))
+        return dlogits, None, None
+
+
+def lattice_soft_ce(logits, regret, tau):
+    """Soft labels for the lattice head: logits (B, 64), regret (B, 64) float32 (CrowdNavEngine.robot_act's / robot_mix's
+    regret rows), tau > 0 -> (ce (B,), kl (B,), logp_best (B,)): the cross-entropy against the target
+    softmax(-regret / tau) with its gradient to the logits (cn_lattice_soft_fwd / _bwd, one launch each), and two
+    reported values without gradient: KL(target || policy) and the log-probability of the expert's own choice (the
+    hard label's -nll). CPU tensors: lattice_soft_ce_torch."""
+    if (logits.dim() != 2 or logits.shape[1] != LATTICE or regret.shape != logits.shape
+            or regret.dtype != torch.float32 or regret.device != logits.device):
+        raise ValueError("lattice_soft_ce: logits (B, %d) and float32 regret of the same shape and device required"
+                         % LATTICE)
+    if not logits.is_cuda:
+        return lattice_soft_ce_torch(logits, regret, tau)
+    return _LatticeSoftCE.apply(logits, regret, _soft_inv_tau(tau))
 
 
 class _AttnPool(torch.autograd.Function):

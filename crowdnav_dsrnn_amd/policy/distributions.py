@@ -75,6 +75,11 @@ class FixedLattice:
     def entropy(self):
         return ops.lattice_evaluate(self.logits, self.logits.new_zeros((self.logits.shape[0], 2)))[1]
 
+    def soft_cross_entropy(self, regret, tau):
+        """(ce (B,), kl (B,), logp_best (B,)) against the target softmax(-regret / tau) of the expert's regret rows
+        (B, 64) (ops.lattice_soft_ce: the gradient reaches the logits through ce)."""
+        return ops.lattice_soft_ce(self.logits, regret, tau)
+
 
 class LatticeCategorical(nn.Module):
     """The opt-in action head of the unicycle robot (robot.action_head = 'lattice'): 64 logits from a linear layer

@@ -97,3 +97,15 @@ class Policy(nn.Module):
         action_log_probs = dist.log_probs(action)
         dist_entropy = dist.entropy().mean()
         return value, action_log_probs, dist_entropy, rnn_hxs
+
+    def evaluate_soft(self, inputs, rnn_hxs, masks, regret, tau):
+        """evaluate_actions against soft labels (the lattice head only): regret (B, 64) float32, the expert's regret
+        row of every state (CrowdNavEngine.robot_mix's `regret`), tau > 0 -> value, ce (B, 1) the cross-entropy
+        against softmax(-regret / tau) with its gradient, kl (B, 1) and logp_best (B, 1) the log-probability of the
+        expert's own choice, both reported without gradient (ops.lattice_soft_ce), rnn_hxs."""
+        if self.head != "lattice":
+            raise UnsupportedConfig("Policy.evaluate_soft: soft labels are a distribution over the lattice head's 64 "
+                                    "candidates; this policy's head is %r" % (self.head,))
+        value, actor_features, rnn_hxs = self.base(inputs, rnn_hxs, masks)
+        ce, kl, logp_best = self.dist(actor_features).soft_cross_entropy(regret, tau)
+        return value, ce.unsqueeze(1), kl.unsqueeze(1), logp_best.unsqueeze(1), rnn_hxs

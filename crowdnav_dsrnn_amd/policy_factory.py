@@ -370,6 +370,18 @@ def dwa_predict(self_state, v, others, time_step, params=None, detail=False):
     return actions, choice, costs
 
 
+def dwa_regret(costs, choice):
+    """cn_robot_act_regret's regret rows on the host (numpy), include/crowdnav.h restated: costs (n, 64) float64 and
+    choice (n,) -- dwa_predict's or cn_dwa_predict's -- -> (n, 64) float32, (float32)(J_c - J_choice) with the
+    subtraction in float64 and the rounding to float32 the only rounding: +0.0 at the choice and at every candidate tied
+    with it, >= 0 everywhere (the choice has the smallest cost)."""
+    J = np.asarray(costs, np.float64).reshape(-1, 64)
+    b = np.asarray(choice).reshape(-1).astype(np.int64)
+    if len(b) != len(J):
+        raise ValueError("dwa_regret: costs (n, 64) and choice (n,) required")
+    return (J - J[np.arange(len(J)), b][:, None]).astype(np.float32)
+
+
 def _philox4x32_10(c0, k0, k1):
     """Philox4x32-10 (Salmon et al., SC'11; the Random123 constants) of counter (c0, 0, 0, 0) under key (k0, k1),
     broadcast over numpy arrays, in uint64 arithmetic: the four output words as uint64 arrays < 2^32. The block of

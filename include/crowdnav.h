@@ -30,6 +30,9 @@
  *                   mode and the summed log-probability
  *   cn_lattice_act / cn_lattice_eval_fwd / cn_lattice_eval_bwd ⟵ (no reference counterpart) the opt-in lattice action
  *                   head of the unicycle robot: a categorical policy over cn_dwa_predict's 64 candidate actions
+ *   cn_robot_act_regret / cn_robot_mix_regret / cn_lattice_soft_fwd / cn_lattice_soft_bwd ⟵ (no reference
+ *                   counterpart) soft labels: the controller's regret row of all 64 candidates beside its action, and
+ *                   the lattice head's cross-entropy against the distribution those regrets define
  *   cn_gae         ⟵ RolloutStorage.compute_returns with use_gae (storage.py:132-177), one launch per rollout
  *   cn_orca_predict / cn_orca_predict_kd / cn_social_force_predict ⟵ the agent policy plugin
  *                   policy_factory[name](config).predict(JointState) (crowd_nav/policy/policy_factory.py:1-17)
@@ -398,6 +401,34 @@ int cn_lattice_eval_fwd(void *stream, int64_t B, const float *logits, const floa
 int cn_lattice_eval_bwd(void *stream, int64_t B, const float *logits, const int32_t *choice, const float *g_logp,
                         const float *g_entropy, float *dlogits);
 
+/* Soft labels for the lattice head (no reference counterpart: this project's definition). The target is the
+ * distribution the expert's regrets define at a temperature tau > 0 (inv_tau = 1 / tau): for one row l of 64 float32
+ * logits and one row r of 64 float32 regrets (cn_robot_act_regret's, or any row of non-negative costs), in float32:
+ *   a_j = r_j - min r,  x_j = -(a_j * inv_tau),  t_j = expf(x_j),  Zt = sum t_j,  q_j = t_j / Zt
+ *            (the shift makes a row from any source safe: the best candidate has t = 1, so Zt >= 1; it changes
+ *             nothing on an engine row, whose minimum is +0.0)
+ *   logp_j   cn_lattice_eval_fwd's:  m = max l,  p_j = expf(l_j - m),  Z = sum p_j,  logp_j = (l_j - m) - logf(Z)
+ *   ce       = -sum over q_j > 0 of q_j * logp_j                        (the cross-entropy H(q, softmax l))
+ *   Hq       = -sum over q_j > 0 of q_j * (x_j - logf(Zt)),  kl = ce - Hq   (KL(q || softmax l); >= 0 up to rounding)
+ *   logp_best = logp_j at the lowest j with a_j == 0: on an engine row the expert's label, so the hard-label
+ *            negative log-likelihood is reported by the same pass
+ *   backward with upstream g on ce:  dl_j = g * (p_j / Z - q_j). There is no gradient to the regrets, and kl and
+ *            logp_best are reported values without one.
+ * A candidate whose t_j underflows has q_j == 0 and adds nothing (no 0 * -inf). tau -> 0 is not served: inv_tau must
+ * be finite and > 0, and the hard label is cn_lattice_eval_fwd's path. The order of the 64-term sums is the kernels'
+ * own (xor butterflies), as for the three calls above.
+ * cn_lattice_soft_fwd: B rows, logits [B][64], regret [B][64] -> ce [B], kl [B] (may be NULL), logp_best [B] (may be
+ *   NULL).
+ * cn_lattice_soft_bwd: dlogits [B][64] from the same logits and regrets and g_ce [B] (nothing else is kept between
+ *   the two: both softmaxes are recomputed).
+ * One 64-lane wavefront per row, a lane per candidate, 4 rows per workgroup; no LDS, scratch, atomics or memset.
+ * Device pointers, stream-ordered. CN_EINVAL, before any launch: cn_lattice_eval_fwd's row rule, a NULL pointer other
+ * than kl / logp_best, an inv_tau that is not finite or not > 0. */
+int cn_lattice_soft_fwd(void *stream, int64_t B, const float *logits, const float *regret, float inv_tau, float *ce,
+                        float *kl, float *logp_best);
+int cn_lattice_soft_bwd(void *stream, int64_t B, const float *logits, const float *regret, float inv_tau,
+                        const float *g_ce, float *dlogits);
+
 /* One step of up to two GRUs of the same H in one launch (the act() path's temporal and spatial edge RNNs,
  * srnn_model.py:455-460 at T = 1): cn_gru_fwd_fused per GRU, with the input projection in the kernel when
  * x is given (gi NULL: x [B][F], w_ih [3H][F], b_ih [3H], F % 32 == 0; every GRU of a call in the same mode)
@@ -656,6 +687,28 @@ int cn_mix_ctl_set(void *stream, cn_mix_ctl *dev, const cn_mix_ctl *value);
 int cn_robot_mix(cn_engine *eng, void *stream, int policy, const float *learner /*[E][2]*/,
                  const cn_mix_ctl *ctl /*device*/, int32_t t,
                  float *label /*[E][2]*/, float *executed /*[E][2]*/, uint8_t *flags /*[E]*/);
+
+/* The controller's whole cost row beside its action (soft labels; cn_lattice_soft_fwd consumes it). For one env, with
+ * J_c the float64 costs of cn_dwa_predict's 64 candidates on the engine's current state (cn_dwa_predict's `costs`) and
+ * b its choice:
+ *   regret[c] = (float)(J_c - J_b)        the subtraction in float64, the rounding to float32 the only rounding
+ * so regret[b] == +0.0f exactly, every entry is >= 0 (b has the smallest J), and candidates tied with b are 0 as well.
+ * Subtracting before rounding keeps near-ties resolved where J itself is large (a forecast collision adds ~1000 to
+ * every candidate of an env alike). A row is 64 floats, 256 contiguous bytes: regret [E][64], env e's at row e.
+ * cn_robot_act_regret: cn_robot_act(eng, stream, policy, actions) with the controller's regret kernel in place of
+ *   the plain one -- the same launch count, not a second controller launch; `actions` is bit for bit what cn_robot_act
+ *   writes. Each wave stores its env's row as one coalesced 256-byte store.
+ * cn_robot_mix_regret: cn_robot_mix with that launch in place of cn_robot_act's; label, executed and flags are bit for
+ *   bit cn_robot_mix's.
+ * A mixed engine after cn_mixed_scripted: one launch per group, env r's row at row r of `regret`. Stream-ordered; no
+ * allocation, no synchronisation, no memset; capturable. No engine state changes. All checks come before any launch:
+ * CN_EINVAL: a NULL pointer, t < 0, an unknown policy, CN_ROBOT_DWA without cn_scripted_dwa;
+ * CN_EUNSUPPORTED: CN_ROBOT_ORCA or CN_ROBOT_SOCIAL_FORCE (they have no candidate set), and whatever cn_robot_act
+ * refuses (a mixed engine without cn_mixed_scripted). */
+int cn_robot_act_regret(cn_engine *eng, void *stream, int policy, float *actions /*[E][2]*/, float *regret /*[E][64]*/);
+int cn_robot_mix_regret(cn_engine *eng, void *stream, int policy, const float *learner /*[E][2]*/,
+                        const cn_mix_ctl *ctl /*device*/, int32_t t, float *label /*[E][2]*/,
+                        float *executed /*[E][2]*/, uint8_t *flags /*[E]*/, float *regret /*[E][64]*/);
 
 /* Which humans the robot sees in the state the engine now holds (after cn_reset / cn_step / cn_step_seq /
  * cn_set_state): mask [E][NS] float32, NS = the padded human stride of the observation (N; a mixed engine: its

@@ -29,12 +29,15 @@ the rollouts record the 'visible_masks' rows (cn_rollout_masked) and the policy 
 --dagger replaces the rows per sigma by ONE row "dagger": the same fresh policy trained with learner.DAgger -- the learner
 drives the envs, the expert labels every state it runs into -- with --beta (the probability that the expert's action is
 the one executed in the first chunk), --beta-decay (its factor per chunk) and --aggregate (chunks held for the fit).
+--soft-tau TAU (only with --dagger --expert dwa --head lattice) fits the head to the expert's 64 candidate costs -- the
+target softmax(-regret / TAU), learner.DAgger's soft_tau -- instead of its one choice; every row carries soft_tau (null:
+hard labels), the dagger row also the last update's soft_ce and kl, and its nll stays the hard label's.
 Needs a GPU.
 
 Usage: python tools/imitation_pretrain.py [--policy srnn|convgru] [--expert orca] [--updates 3000] [--envs 1024] [--steps 32] [--epochs 1]
            [--mini-batch 2] [--lr 1e-3] [--value-coef 0.5] [--sigma-frac 0 0.1 0.3] [--humans 5] [--seed 0]
            [--human-nums 5 10 [--unseen 7]] [--kinematics holonomic|unicycle [--sigma 0 0.03] [--head gaussian|lattice]]
-           [--fov F] [--visible-masks] [--dagger [--beta 1.0] [--beta-decay 0.5] [--aggregate 1]] [--eval-envs 100] [--test-size 500] [--log-every K] [--out policy.pt]
+           [--fov F] [--visible-masks] [--dagger [--beta 1.0] [--beta-decay 0.5] [--aggregate 1] [--soft-tau TAU]] [--eval-envs 100] [--test-size 500] [--log-every K] [--out policy.pt]
            [--json FILE]
 """
 import argparse
@@ -97,6 +100,9 @@ def main():
     ap.add_argument("--beta", type=float, default=1.0, help="with --dagger: the first chunk's expert probability")
     ap.add_argument("--beta-decay", type=float, default=0.5, help="with --dagger: beta's factor per chunk")
     ap.add_argument("--aggregate", type=int, default=1, help="with --dagger: chunks held for the fit")
+    ap.add_argument("--soft-tau", type=float, default=None,
+                    help="with --dagger --expert dwa --head lattice: fit the soft target softmax(-regret / TAU) of the "
+                         "expert's 64 candidate costs instead of its choice")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--eval-envs", type=int, default=100)
     ap.add_argument("--test-size", type=int, default=500)
@@ -104,6 +110,8 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
+    if args.soft_tau is not None and not (args.dagger and args.expert == "dwa" and args.head == "lattice"):
+        raise SystemExit("imitation_pretrain: --soft-tau needs --dagger --expert dwa --head lattice")
     if not torch.cuda.is_available():
         raise SystemExit("imitation_pretrain: needs a GPU")
     if args.human_nums and args.policy != "srnn":
@@ -149,7 +157,8 @@ def main():
         ct.sim.human_nums_scripted = True
 
     def emit(row):
-        row = dict(row, fov=float(c.robot.FOV), visible_masks=bool(args.visible_masks), head=args.head)
+        row = dict(row, fov=float(c.robot.FOV), visible_masks=bool(args.visible_masks), head=args.head,
+                   soft_tau=args.soft_tau)
         lines.append(json.dumps(row))
         print(lines[-1], flush=True)
 
@@ -206,7 +215,8 @@ def main():
         pol = fresh_policy(spaces, action_space, cpol)
         envs = CrowdNavVecEnv(ct, E, args.seed, DEV, allow_early_resets=True, nenv=E, phase="train")
         dg = DAgger(ct, envs, pol, expert=args.expert, beta=args.beta, beta_decay=args.beta_decay, seed=args.seed,
-                    epochs=args.epochs, lr=args.lr, value_coef=args.value_coef, aggregate=args.aggregate)
+                    epochs=args.epochs, lr=args.lr, value_coef=args.value_coef, aggregate=args.aggregate,
+                    soft_tau=args.soft_tau)
         torch.cuda.synchronize()
         t0 = time.time()
         gpu_roll = gpu_upd = 0.0
@@ -230,6 +240,9 @@ def main():
                               "value_loss_last": round(st["value_loss"], 4), "agree_first": round(first["agree"], 4),
                               "agree_last": round(st["agree"], 4), "took_expert_last": round(st["took_expert"], 4),
                               "beta_last": st["beta"], "train_wall_s": round(wall, 2),
+                              **({"soft_ce_first": round(first["soft_ce"], 4), "soft_ce_last": round(st["soft_ce"], 4),
+                                  "kl_first": round(first["kl"], 4), "kl_last": round(st["kl"], 4)}
+                                 if args.soft_tau is not None else {}),
                               "rollout_gpu_s": round(gpu_roll, 3), "update_gpu_s": round(gpu_upd, 3),
                               "episodes": args.test_size})
     for sigma, frac in ([] if args.dagger else sigmas):
