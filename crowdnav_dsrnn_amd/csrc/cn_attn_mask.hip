@@ -9,8 +9,8 @@
 // attn[r][n] and dhs[r][n][:] of masked slots are written as exact zeros; hs[r][n] and dattn[r][n] are never read
 // there. A row without a visible slot gives out = 0, attn = 0, du = 0, dc = 0, dhs = 0.
 //
-// A translation unit of its own: the code object of cn_gru.hip does not move (its kernels' placement has measured
-// 0.4 - 0.8 % on the training workload with byte-identical kernels).
+// A translation unit of its own, not a section of cn_gru.hip under policy/: the code object of cn_gru.hip does not
+// move (its kernels' placement has measured 0.4 - 0.8 % on the training workload with byte-identical kernels).
 //
 // Mapping as the _var pair: one thread per (row, 4 consecutive h), HQ = H / 4 lanes per row, rows never straddle a
 // wave, scores through LDS at the COMPACT index k (the k-th visible slot), the first NR VISIBLE vectors stay in
@@ -27,14 +27,11 @@
 #include <initializer_list>
 
 #include "../../include/crowdnav.h"
-
-int cn_set_error(int code, const char *msg);
+#include "cn_host.h"   // cn_set_error, grid_for, launch_status, CN_SA_LAUNCH (the (H, N) ladder of cn_gru.hip's kernels)
 
 namespace {
 
 #define CN_SAM_MAXN 64
-
-inline unsigned grid_for(int64_t B, int H) { return (unsigned)((B * (H / 4) + 255) / 256); }
 
 // visibility word of row r (all HQ lanes of the row return the same word); called by all 256 threads
 template <int HQ>
@@ -232,21 +229,9 @@ int cn_spatial_attn_mask_fwd(void *stream, int64_t R, int N, int H, const float 
         return CN_EINVAL;
     const unsigned grid = grid_for(R, H);
     (void)hipGetLastError();   // a stale error of an earlier call (any library) is not this launch's
-#define CN_SAM_FWD(HQ, NR) \
-    hipLaunchKernelGGL((cn_spatial_attn_mask_fwd_kernel<HQ, NR>), dim3(grid), dim3(256), 0, (hipStream_t)stream, R, N, \
-                       mask, row_scale, hs, u, c, out, attn)
-    if (N <= 10) {
-        if (H == 256) CN_SAM_FWD(64, 10);
-        else if (H == 128) CN_SAM_FWD(32, 10);
-        else CN_SAM_FWD(16, 10);
-    } else {
-        if (H == 256) CN_SAM_FWD(64, 16);
-        else if (H == 128) CN_SAM_FWD(32, 16);
-        else CN_SAM_FWD(16, 16);
-    }
-#undef CN_SAM_FWD
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? CN_OK : cn_set_error(CN_EHIP, hipGetErrorString(e));
+    CN_SA_LAUNCH(cn_spatial_attn_mask_fwd_kernel, H, N, grid, (hipStream_t)stream, R, N, mask, row_scale,
+                 hs, u, c, out, attn);
+    return launch_status();
 }
 
 int cn_spatial_attn_mask_bwd(void *stream, int64_t R, int N, int H, const float *mask, const float *row_scale,
@@ -259,21 +244,9 @@ int cn_spatial_attn_mask_bwd(void *stream, int64_t R, int N, int H, const float 
         return cn_set_error(CN_EINVAL, "cn_spatial_attn_mask_bwd: bad shape, stride or operand");
     const unsigned grid = grid_for(R, H);
     (void)hipGetLastError();   // a stale error of an earlier call (any library) is not this launch's
-#define CN_SAM_BWD(HQ, NR) \
-    hipLaunchKernelGGL((cn_spatial_attn_mask_bwd_kernel<HQ, NR>), dim3(grid), dim3(256), 0, (hipStream_t)stream, R, N, \
-                       mask, row_scale, hs, u, attn, dout, dattn, dhs, du, ldu, dc, ldc)
-    if (N <= 10) {
-        if (H == 256) CN_SAM_BWD(64, 10);
-        else if (H == 128) CN_SAM_BWD(32, 10);
-        else CN_SAM_BWD(16, 10);
-    } else {
-        if (H == 256) CN_SAM_BWD(64, 16);
-        else if (H == 128) CN_SAM_BWD(32, 16);
-        else CN_SAM_BWD(16, 16);
-    }
-#undef CN_SAM_BWD
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? CN_OK : cn_set_error(CN_EHIP, hipGetErrorString(e));
+    CN_SA_LAUNCH(cn_spatial_attn_mask_bwd_kernel, H, N, grid, (hipStream_t)stream, R, N, mask, row_scale,
+                 hs, u, attn, dout, dattn, dhs, du, ldu, dc, ldc);
+    return launch_status();
 }
 
 }  // extern "C"

@@ -16,8 +16,7 @@
 #include <initializer_list>
 
 #include "../../include/crowdnav.h"
-
-int cn_set_error(int code, const char *msg);
+#include "cn_host.h"   // cn_set_error, launch_status
 
 namespace {
 
@@ -224,13 +223,7 @@ int lattice_check(const char *who, int64_t rows, std::initializer_list<const voi
     return CN_OK;
 }
 
-inline unsigned grid_for(int64_t rows) { return (unsigned)((rows + ROWS - 1) / ROWS); }
-
-int launched()
-{
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? CN_OK : cn_set_error(CN_EHIP, hipGetErrorString(e));
-}
+inline unsigned row_grid(int64_t rows) { return (unsigned)((rows + ROWS - 1) / ROWS); }
 
 }  // namespace
 
@@ -242,9 +235,9 @@ int cn_lattice_act(void *stream, int64_t E, const float *logits, const float *u,
     if (lattice_check("cn_lattice_act: E > 0 and non-null logits, action, logp required", E, {logits, action, logp}))
         return CN_EINVAL;
     (void)hipGetLastError();   // a stale error of an earlier call (any library) is not this launch's
-    hipLaunchKernelGGL(cn_lattice_act_kernel, dim3(grid_for(E)), dim3(256), 0, (hipStream_t)stream, E, logits, u,
+    hipLaunchKernelGGL(cn_lattice_act_kernel, dim3(row_grid(E)), dim3(256), 0, (hipStream_t)stream, E, logits, u,
                        action, logp, choice);
-    return launched();
+    return launch_status();
 }
 
 int cn_lattice_eval_fwd(void *stream, int64_t B, const float *logits, const float *actions, float *logp,
@@ -254,9 +247,9 @@ int cn_lattice_eval_fwd(void *stream, int64_t B, const float *logits, const floa
                       {logits, actions, logp, entropy, choice}))
         return CN_EINVAL;
     (void)hipGetLastError();
-    hipLaunchKernelGGL(cn_lattice_eval_fwd_kernel, dim3(grid_for(B)), dim3(256), 0, (hipStream_t)stream, B, logits,
+    hipLaunchKernelGGL(cn_lattice_eval_fwd_kernel, dim3(row_grid(B)), dim3(256), 0, (hipStream_t)stream, B, logits,
                        actions, logp, entropy, choice);
-    return launched();
+    return launch_status();
 }
 
 int cn_lattice_eval_bwd(void *stream, int64_t B, const float *logits, const int32_t *choice, const float *g_logp,
@@ -266,9 +259,9 @@ int cn_lattice_eval_bwd(void *stream, int64_t B, const float *logits, const int3
                       {logits, choice, g_logp, g_entropy, dlogits}))
         return CN_EINVAL;
     (void)hipGetLastError();
-    hipLaunchKernelGGL(cn_lattice_eval_bwd_kernel, dim3(grid_for(B)), dim3(256), 0, (hipStream_t)stream, B, logits,
+    hipLaunchKernelGGL(cn_lattice_eval_bwd_kernel, dim3(row_grid(B)), dim3(256), 0, (hipStream_t)stream, B, logits,
                        choice, g_logp, g_entropy, dlogits);
-    return launched();
+    return launch_status();
 }
 
 int cn_lattice_soft_fwd(void *stream, int64_t B, const float *logits, const float *regret, float inv_tau, float *ce,
@@ -279,9 +272,9 @@ int cn_lattice_soft_fwd(void *stream, int64_t B, const float *logits, const floa
     if (!(inv_tau > 0.0f && inv_tau < __builtin_inff()))   // (a NaN fails both)
         return cn_set_error(CN_EINVAL, "cn_lattice_soft_fwd: a finite inv_tau > 0 required");
     (void)hipGetLastError();
-    hipLaunchKernelGGL(cn_lattice_soft_fwd_kernel, dim3(grid_for(B)), dim3(256), 0, (hipStream_t)stream, B, logits,
+    hipLaunchKernelGGL(cn_lattice_soft_fwd_kernel, dim3(row_grid(B)), dim3(256), 0, (hipStream_t)stream, B, logits,
                        regret, inv_tau, ce, kl, logp_best);
-    return launched();
+    return launch_status();
 }
 
 int cn_lattice_soft_bwd(void *stream, int64_t B, const float *logits, const float *regret, float inv_tau,
@@ -293,9 +286,9 @@ int cn_lattice_soft_bwd(void *stream, int64_t B, const float *logits, const floa
     if (!(inv_tau > 0.0f && inv_tau < __builtin_inff()))
         return cn_set_error(CN_EINVAL, "cn_lattice_soft_bwd: a finite inv_tau > 0 required");
     (void)hipGetLastError();
-    hipLaunchKernelGGL(cn_lattice_soft_bwd_kernel, dim3(grid_for(B)), dim3(256), 0, (hipStream_t)stream, B, logits,
+    hipLaunchKernelGGL(cn_lattice_soft_bwd_kernel, dim3(row_grid(B)), dim3(256), 0, (hipStream_t)stream, B, logits,
                        regret, inv_tau, g_ce, dlogits);
-    return launched();
+    return launch_status();
 }
 
 }  // extern "C"

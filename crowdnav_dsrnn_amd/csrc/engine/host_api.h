@@ -458,19 +458,13 @@ static int step_launch(cn_engine *g, void *stream, const float *actions, int nst
     const bool prof = g->prof_on && g->prof_n < g->prof_cap;
     if (prof && g->prof_n == 0) HIPCHK(hipEventRecord(g->ev[0], st));
     if (g->ngroups) {   // one step launch per group, concurrently (fork / join around the caller's stream)
-        if (g->ngroups > 1) HIPCHK(hipEventRecord(g->gev[0], st));
-        for (int k = 0; k < g->ngroups; ++k) {
-            hipStream_t sk = st;
-            if (k > 0) { sk = g->gstream[k]; HIPCHK(hipStreamWaitEvent(sk, g->gev[0], 0)); }
-            const int rc = cn_step(g->grp[k], (void *)sk, actions, robot_node, temporal, spatial, reward, done, event,
-                                   info, ep_return, ep_len);
-            if (rc) {   // join the groups already forked, so no side-stream work outlives the caller's order
-                for (int j = 1; j < k; ++j) (void)hipStreamWaitEvent(st, g->gev[j], 0);
-                return rc;
-            }
-            if (k > 0) HIPCHK(hipEventRecord(g->gev[k], sk));
-        }
-        for (int k = 1; k < g->ngroups; ++k) HIPCHK(hipStreamWaitEvent(st, g->gev[k], 0));
+        int rc = mix_fork(g, st);
+        if (rc) return rc;
+        for (int k = 0; k < g->ngroups && !rc; ++k)
+            rc = cn_step(g->grp[k], (void *)mix_stream(g, k, st), actions, robot_node, temporal, spatial, reward, done,
+                         event, info, ep_return, ep_len);
+        const int rj = mix_join(g, st);
+        if (rc || rj) return rc ? rc : rj;
         if (prof && ++g->prof_n == g->prof_cap) HIPCHK(hipEventRecord(g->ev[1], st));
         return CN_OK;
     }

@@ -199,6 +199,7 @@ def test_build_deps_cover_every_included_file():
             todo.append(os.path.join(os.path.dirname(f), inc))
     deps = [os.path.realpath(d) for d in build.DEPS]
     assert any(os.sep + "engine" + os.sep in f for f in reached)   # (the walk went into csrc/engine/)
+    assert any(os.sep + "csrc" + os.sep + "policy" + os.sep in f for f in reached)   # (and into csrc/policy/)
     assert reached <= set(deps), sorted(reached - set(deps))
     assert len(set(deps)) == len(deps)
     n = len(build.SOURCES)

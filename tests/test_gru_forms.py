@@ -1,4 +1,4 @@
-"""The GRU kernels of csrc/cn_gru.hip in every dispatch form and at every accepted size vs float64.
+"""The GRU kernels of csrc/cn_gru.hip (its sections csrc/policy/gru_*.h) in every dispatch form and at every accepted size vs float64.
 
 Each recurrent launch picks the 128-row kernels (cn_gru_fused_kernel / cn_gru_bwd_fused_kernel) when
 ceil(rows / 128) * (H / 32) >= the device's CU count and the 32-row split-K kernels (cn_gru_fused_sk_kernel /

@@ -388,12 +388,13 @@ def spatial_attention_ref(hs, te, ws, bs, scale):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("R,N,H", [(1, 1, 256), (37, 10, 256), (300, 25, 128), (5, 3, 64), (4099, 20, 256),
-                                   (9, 64, 64)])
+                                   (9, 64, 64), (3, 10, 128), (3, 11, 128)])
 def test_spatial_attention_kernels_vs_fp64(R, N, H):
     """cn_spatial_attn_fwd / _bwd (spatial_edge_layer folded into the score: reassociated) vs the
     reference's composition in float64: output, attention and the gradients of h_spatials, temporal_embed,
     the layer's weight and bias, with a gradient arriving on the returned attention too (N > 16 covers the
-    reloaded tail of a row). fp32 accumulation over H and N: atol 2e-5 x scale."""
+    reloaded tail of a row; the shapes reach every <HQ, NR> instantiation: H in {256, 128, 64} x N <= 10 / N > 10, and
+    the boundary N = 10 / 11). fp32 accumulation over H and N: atol 2e-5 x scale."""
     from crowdnav_dsrnn_amd import ops
 
     A = 64

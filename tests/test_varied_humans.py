@@ -16,7 +16,10 @@ from tests.helpers import make_policy
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 A = 64
-SHAPES = [(1, 1, 256), (37, 10, 256), (300, 25, 128), (5, 3, 64), (9, 64, 64), (4099, 20, 256)]
+# every <HQ, NR> of the kernels' (H, N) ladder: H in {256, 128, 64} x (N <= 10, N > 10); (3, 10, 128) is <32, 10>'s,
+# (3, 11, 128) the other side of the ladder's N <= 10
+SHAPES = [(1, 1, 256), (37, 10, 256), (300, 25, 128), (5, 3, 64), (9, 64, 64), (4099, 20, 256), (3, 10, 128),
+          (3, 11, 128)]
 ATOL, RTOL = 2e-5, 1e-4       # the DSRNN's pinned tolerance
 
 

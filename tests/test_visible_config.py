@@ -12,7 +12,9 @@ from crowdnav_dsrnn_amd import spaces
 from crowdnav_dsrnn_amd.config import Config, UnsupportedConfig, clone_config, visible_masks_on
 
 A = 64
-SHAPES = [(1, 1, 256), (37, 10, 256), (300, 25, 128), (5, 3, 64), (9, 64, 64), (4099, 20, 256)]   # test_varied_humans'
+# test_varied_humans': every <HQ, NR> of the kernels' (H, N) ladder, and both sides of its N <= 10 at H = 128
+SHAPES = [(1, 1, 256), (37, 10, 256), (300, 25, 128), (5, 3, 64), (9, 64, 64), (4099, 20, 256), (3, 10, 128),
+          (3, 11, 128)]
 PINNED = ("full", "first", "last", "empty", "prefix10", "prefix11", "prefix16", "prefix17", "alternate")
 
 

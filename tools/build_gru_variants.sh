@@ -1,4 +1,4 @@
-# diagnostic: libraries with cn_gru.hip compile-time variants (tools/probe_gru_seq.py via CN_LIB_PATH)
+# diagnostic: libraries with compile-time variants of the unit cn_gru.hip (its sections: csrc/policy/*.h) (tools/probe_gru_seq.py via CN_LIB_PATH)
 #   bash tools/build_gru_variants.sh name "-DGF_WPC=3 ..." [name "-D..."] ...
 set -e
 R=$(cd "$(dirname "$0")/.." && pwd)
