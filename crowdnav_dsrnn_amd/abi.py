@@ -1,8 +1,9 @@
 """ctypes mirror of include/crowdnav.h and include/crowdnav_state.h.
 
-Pure data definitions (no compute): the `cn_config` struct, the enum values, and the state-blob
-layout used by `cn_get_state` / `cn_set_state`. Shared by the product bindings
-(`crowdnav_dsrnn_amd._lib`) and the test harness.
+Pure data definitions (no compute): every struct of the header as a ctypes.Structure, the enum values, and
+the state-blob layout used by `cn_get_state` / `cn_set_state`. Shared by the product bindings
+(`crowdnav_dsrnn_amd._lib`, whose SIGNATURES table holds the functions) and the test harness;
+tests/test_abi.py compares structs and constants with the header.
 """
 import ctypes
 
@@ -139,6 +140,52 @@ class CnMixCtl(ctypes.Structure):
         ("seed", ctypes.c_uint32),
         ("step0", ctypes.c_int64),
     ]
+
+
+class GruStepSeg(ctypes.Structure):
+    """cn_gru_step_seg (include/crowdnav.h): one GRU of a cn_gru_fwd_step_group call (device pointers)."""
+    _fields_ = [("B", ctypes.c_int64), ("gi", ctypes.c_void_p), ("x", ctypes.c_void_p), ("w_ih", ctypes.c_void_p),
+                ("b_ih", ctypes.c_void_p), ("F", ctypes.c_int64), ("hm", ctypes.c_void_p), ("w_hh", ctypes.c_void_p),
+                ("b_hh", ctypes.c_void_p), ("h_out", ctypes.c_void_p), ("h_out2", ctypes.c_void_p),
+                ("g2", ctypes.c_int64), ("ld2", ctypes.c_int64)]
+
+
+class GruSeqFwd(ctypes.Structure):
+    """cn_gru_seq_fwd (include/crowdnav.h): one GRU of a cn_gru_fwd_seq call (device pointers)."""
+    _fields_ = [("B", ctypes.c_int64), ("gi", ctypes.c_void_p), ("w_hh", ctypes.c_void_p), ("b_hh", ctypes.c_void_p),
+                ("m", ctypes.c_void_p), ("out", ctypes.c_void_p), ("hm", ctypes.c_void_p), ("save", ctypes.c_void_p),
+                ("nh", ctypes.c_int64), ("x", ctypes.c_void_p), ("w_ih", ctypes.c_void_p), ("b_ih", ctypes.c_void_p),
+                ("F", ctypes.c_int64)]
+
+
+class GruSeqBwd(ctypes.Structure):
+    """cn_gru_seq_bwd (include/crowdnav.h): one GRU of a cn_gru_bwd_seq call (device pointers)."""
+    _fields_ = [("B", ctypes.c_int64), ("w_hh_t", ctypes.c_void_p), ("m", ctypes.c_void_p), ("dout", ctypes.c_void_p),
+                ("save", ctypes.c_void_p), ("hm", ctypes.c_void_p), ("acc", ctypes.c_void_p), ("g", ctypes.c_void_p),
+                ("db_ih", ctypes.c_void_p), ("db_hh", ctypes.c_void_p)]
+
+
+class RolloutOut(ctypes.Structure):
+    """cn_rollout_out (include/crowdnav.h): the per-step records of a cn_rollout call (device pointers)."""
+    _fields_ = [("actions", ctypes.c_void_p), ("robot_node", ctypes.c_void_p), ("temporal_edges", ctypes.c_void_p),
+                ("spatial_edges", ctypes.c_void_p), ("reward", ctypes.c_void_p), ("done", ctypes.c_void_p),
+                ("event", ctypes.c_void_p), ("info", ctypes.c_void_p), ("ep_return", ctypes.c_void_p),
+                ("ep_len", ctypes.c_void_p), ("flags", ctypes.c_int32)]
+
+
+ROLLOUT_OBS_EVERY_STEP = 1   # CN_ROLLOUT_OBS_EVERY_STEP
+
+
+class RolloutNoise(ctypes.Structure):
+    """cn_rollout_noise (include/crowdnav.h): the perturbation of a cn_rollout_noisy call."""
+    _fields_ = [("sigma", ctypes.c_float), ("seed", ctypes.c_uint32), ("step0", ctypes.c_int64),
+                ("executed", ctypes.c_void_p)]
+
+
+class RolloutLidar(ctypes.Structure):
+    """struct cn_rollout_lidar (include/crowdnav.h): the LiDAR rows and state rows of a cn_rollout_lidar call."""
+    _fields_ = [("obs", ctypes.c_void_p), ("beams", ctypes.c_int32), ("max_range", ctypes.c_double),
+                ("robot_radius", ctypes.c_double), ("robot_state", ctypes.c_void_p), ("human_state", ctypes.c_void_p)]
 
 
 # --- state blob (include/crowdnav_state.h) ---------------------------------------------------------

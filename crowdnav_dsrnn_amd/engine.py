@@ -293,7 +293,7 @@ class CrowdNavEngine:
             _lib.check(_lib.lib().cn_visible_mask(self._h, self._stream(), out.data_ptr()))
         return out
 
-    ROBOT_POLICIES = {"orca": 0, "social_force": 1, "dwa": 2}   # CN_ROBOT_ORCA / CN_ROBOT_SOCIAL_FORCE / CN_ROBOT_DWA
+    ROBOT_POLICIES = {"orca": abi.ROBOT_ORCA, "social_force": abi.ROBOT_SOCIAL_FORCE, "dwa": abi.ROBOT_DWA}   # CN_ROBOT_*
 
     def _regret_arg(self, who, regret):
         """robot_act's / robot_mix's `regret`: a contiguous float32 (E, 64) tensor on the engine's device."""
