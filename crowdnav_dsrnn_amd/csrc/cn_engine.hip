@@ -184,6 +184,8 @@ __global__ void __launch_bounds__(CN_BLK, 3) cn_step_kernel(StepArgs g, cn_confi
     // stores of waves 0 and 1, and phase 5 serves the resets alone (the A/B of DESIGN.md §4). These instantiations
     // alone, the others compile as without it
     constexpr bool GOAL_EARLY = SEQ && !ROBOT && !KD && !MIX;
+    // linearProgram2 as a walk (lp2_r, orca_lp.h): the same instantiations, the ones its A/B measured
+    constexpr bool LP2W = SEQ && !ROBOT && !KD && !MIX;
     // this launch's spawn / parked-spawn lists (triple-buffered: launch t appends to t % 3, reads (t - 1) % 3,
     // zeroes (t + 1) % 3) and id, from the device-side step counter
     const uint32_t ns = DEVSEQ ? g.ctl[CN_CTL_NSTEP] : 0u;
@@ -1081,6 +1083,7 @@ __global__ void __launch_bounds__(CN_BLK, 3) cn_step_kernel(StepArgs g, cn_confi
                 }
                 wsync();
                 STAMP_A(7);
+                STAMP_W(0);
                 if constexpr (!KD) {   // <= 12 lines: register-resident linear programs
                     uint32_t *l3b = (uint32_t *)(smem + P.o_l3b);
                     float2 *l3r = (float2 *)(smem + P.o_l3r);
@@ -1091,10 +1094,22 @@ __global__ void __launch_bounds__(CN_BLK, 3) cn_step_kernel(StepArgs g, cn_confi
 #pragma unroll
                     for (int u = 0; u < 3; ++u)
                         R[u] = hq && sq + 4 * u < cnt ? Lb[sq + 4 * u] : make_float4(0.f, 0.f, 0.f, 0.f);
-                    if (hq) {
-                        fail_at = lp2_r<3>(R, cnt, sl.vmax[h], (float)gdx, (float)gdy, sq, rx, ry);
+#ifdef CN_STAMPS
+                    LpCount lc2 = {0, 0}, lc3 = {0, 0};
+                    if (hq) fail_at = lp2_r<3, LP2W>(R, cnt, sl.vmax[h], (float)gdx, (float)gdy, sq, rx, ry, Lb, &lc2);
+                    {
+                        int uni = 0, mx = 0;
+                        lp_count_wave(lc2, uni, mx);
+                        STAMP_WV(5, (unsigned long long)uni);
+                        STAMP_WV(6, (unsigned long long)mx);
                     }
+#else
+                    if (hq) {
+                        fail_at = lp2_r<3, LP2W>(R, cnt, sl.vmax[h], (float)gdx, (float)gdy, sq, rx, ry, Lb);
+                    }
+#endif
                     STAMP_A(8);
+                    STAMP_W(1);
                     // linearProgram3 of the workgroup's infeasible humans: every sub-problem their loops may
                     // visit, solved by all quads (lp3_tasks), then each human's quad replays its loop
                     const bool l3 = hq && fail_at < cnt;
@@ -1112,8 +1127,15 @@ __global__ void __launch_bounds__(CN_BLK, 3) cn_step_kernel(StepArgs g, cn_confi
                     __syncthreads();
 #ifdef CN_STAMPS
                     const unsigned long long tl3 = clock64();
-#endif
+                    STAMP_W(2);
+                    lp3_tasks<3>(sl.lines, M, sl.vmax, l3b, l3r, l3k, tid, &lc3);
+                    STAMP_W(3);
+                    STAMP_WV(7, (unsigned long long)(lc3.bodies & 0xfff));
+                    STAMP_WV(8, (unsigned long long)(lc3.bodies >> 12 & 0xfff));
+                    STAMP_WV(9, (unsigned long long)(lc3.bodies >> 24));
+#else
                     lp3_tasks<3>(sl.lines, M, sl.vmax, l3b, l3r, l3k, tid);
+#endif
                     __syncthreads();
                     int l3vis = 0;
                     if (l3) l3vis = lp3_replay<3>(R, Lb, cnt, fail_at, l3e, sl.vmax[h], sq, l3r + h * 12, l3k + h * 12, rx, ry);
@@ -1126,6 +1148,7 @@ __global__ void __launch_bounds__(CN_BLK, 3) cn_step_kernel(StepArgs g, cn_confi
                         const bool vr = info_on && path_vr_q(h, sq);   // the whole quad
                         if (sq == 0) human_post(h, (double)rx, (double)ry, vr);
                     }
+                    STAMP_W(4);
                 } else if (hq) {
                     float rx, ry;
                     const float vmq = sl.vmax[h];

@@ -54,7 +54,7 @@ __global__ void __launch_bounds__(64) cn_orca_kernel(int64_t n, int A, const flo
         float4 R[3];
 #pragma unroll
         for (int u = 0; u < 3; ++u) R[u] = sq + 4 * u < cnt ? Ls[q][sq + 4 * u] : make_float4(0.f, 0.f, 0.f, 0.f);
-        const int fail_at = lp2_r<3>(R, cnt, vmax, ox, oy, sq, rx, ry);
+        const int fail_at = lp2_r<3, true>(R, cnt, vmax, ox, oy, sq, rx, ry, Ls[q]);   // the walk: tests/test_lp_walk.py
         if (fail_at < cnt) lp3_r<3>(R, Ls[q], cnt, fail_at, vmax, sq, rx, ry);
         if (sq == 0) {
             out[4 * i] = rx; out[4 * i + 1] = ry; out[4 * i + 2] = (float)fail_at; out[4 * i + 3] = (float)cnt;

@@ -678,6 +678,14 @@ int cn_debug_stamps_x(unsigned long long *x)
     return CN_OK;
 }
 
+// phase 2 per wave [4096][4][CN_NWSTAMP] (stamps.h: STAMP_W)
+int cn_debug_stamps_w(unsigned long long *w)
+{
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpyFromSymbol(w, HIP_SYMBOL(cn_stamp_w), sizeof(unsigned long long) * 4096 * 4 * CN_NWSTAMP));
+    return CN_OK;
+}
+
 int cn_debug_stamps(unsigned long long *a, unsigned long long *b)
 {
     HIPCHK(hipDeviceSynchronize());

@@ -160,6 +160,27 @@ __device__ __forceinline__ void lp3_q(const float4 *Lb, float4 *Pb, int n, int b
 // operations in the same order as lp1_q / lp2_q / lp3_q, so the same bits.
 // ------------------------------------------------------------------------------------------------
 
+// -DCN_STAMPS: the linearProgram1 bodies a quad's linear program ran (count, and their line indices as a mask).
+// A wave runs the unrolled forms' body of index i when any of its quads does (lp_count_wave's `uni`: distinct
+// indices over the wave) and a walk's body once per trip (`mx`: the largest count of one quad).
+#ifdef CN_STAMPS
+struct LpCount { int bodies; uint32_t lines; };
+#define LP_COUNT_ARG , LpCount *lc = nullptr
+#define LP_COUNT(i) do { if (lc) { ++lc->bodies; lc->lines |= 1u << (i); } } while (0)
+__device__ __forceinline__ void lp_count_wave(const LpCount &lc, int &uni, int &mx)   // over the active lanes
+{
+    int m = 0;
+    for (int k = 0; k < 12; ++k) {
+        if (__ballot((lc.lines >> k) & 1u)) ++uni;
+        if (__ballot(lc.bodies > k)) m = k + 1;
+    }
+    mx += m;
+}
+#else
+#define LP_COUNT_ARG
+#define LP_COUNT(i) do { } while (0)
+#endif
+
 // linearProgram1 on line `no` (= ln, already broadcast) against the valid (vmask) lines j < no of R
 template <int NU>
 __device__ __forceinline__ bool lp1_r(const float4 (&R)[NU], uint32_t vmask, int no, const float4 ln, float radius,
@@ -194,22 +215,59 @@ __device__ __forceinline__ bool lp1_r(const float4 (&R)[NU], uint32_t vmask, int
     return !(disc < 0.0f || tl > tr);
 }
 
-// linearProgram2 (optimize closest to (ox, oy)) over the n lines of R; returns the failing line or n
-template <int NU>
+// linearProgram2 (optimize closest to (ox, oy)) over the n lines of R; returns the failing line or n.
+// RVO2's loop acts only at a line the current result violates, and the result changes only there, so the lines a
+// quad acts on are "the lowest index above the last one whose line the current result violates". The unrolled form
+// (WALK false) steps through all indices in lockstep, and a wave runs linearProgram1 at index i when ANY of its 16
+// quads has line i violated: the union of their indices. The walk (WALK true; Lb: the LDS copy of the lines) lets
+// each quad jump to its own next violated line: per trip every lane tests its own lines against the result (the
+// loop's own test, same operands), the quad ORs the bits, masks them to the indices above the last line acted on
+// and takes the lowest; line i, a run-time index now, is read from Lb. A wave makes as many trips as its busiest
+// quad has lines to act on (C2: 3.2 instead of 5.8 linearProgram1 bodies per wave and step). Every arithmetic
+// operation of a quad is one the unrolled form performs, on the same operands in the same order: the same bits.
+// The loop's control flow is quad-uniform (vm, i and the failure are), so every DPP runs with whole quads.
+// The walk serves the instantiations its A/B measured: the plain multi-step step kernels and
+// cn_debug_orca, through which tests/test_lp_walk.py pins it to the oracle; the others keep the unrolled form.
+template <int NU, bool WALK = false>
 __device__ __forceinline__ int lp2_r(const float4 (&R)[NU], int n, float radius, float ox, float oy, int s, float &rx,
-                                     float &ry)
+                                     float &ry, const float4 *Lb = nullptr LP_COUNT_ARG)
 {
     if (ox * ox + oy * oy > radius * radius) {
         const float inv = fdiv(1.0f, fsqrt(ox * ox + oy * oy));
         rx = (ox * inv) * radius; ry = (oy * inv) * radius;
     } else { rx = ox; ry = oy; }
     int fail = n;
+    if constexpr (WALK) {
+        uint32_t above = ~0u;   // the indices above the last line acted on
+        for (;;) {
+            uint32_t vm = 0;
+#pragma unroll
+            for (int u = 0; u < NU; ++u) {
+                const float4 lu = R[u];
+                if (s + 4 * u < n && det2(lu.z, lu.w, lu.x - rx, lu.y - ry) > 0.0f) vm |= 1u << (s + 4 * u);
+            }
+            vm = (uint32_t)quad_or((int)vm) & above;
+            if (vm == 0) break;   // quad-uniform: no line left
+            const int i = __ffs(vm) - 1;
+            above = ~1u << i;
+            const float4 li = Lb[i];
+            LP_COUNT(i);
+            float tL, tR;
+            if (!lp1_r<NU>(R, ~0u, i, li, radius, s, tL, tR)) { fail = i; break; }
+            const float t = li.z * (ox - li.x) + li.w * (oy - li.y);
+            if (t < tL) { rx = li.x + tL * li.z; ry = li.y + tL * li.w; }
+            else if (t > tR) { rx = li.x + tR * li.z; ry = li.y + tR * li.w; }
+            else { rx = li.x + t * li.z; ry = li.y + t * li.w; }
+        }
+        return fail;
+    }
 #pragma unroll
     for (int i = 0; i < 4 * NU; ++i) {
         if (i < n && fail == n) {   // quad-uniform
             const float4 li = qbc4(R[i >> 2], i);
             if (det2(li.z, li.w, li.x - rx, li.y - ry) > 0.0f) {
                 float tL, tR;
+                LP_COUNT(i);
                 if (!lp1_r<NU>(R, ~0u, i, li, radius, s, tL, tR)) fail = i;
                 else {
                     const float t = li.z * (ox - li.x) + li.w * (oy - li.y);
@@ -228,7 +286,7 @@ __device__ __forceinline__ int lp2_r(const float4 (&R)[NU], int n, float radius,
 // Depends on the lines only. Returns false when it fails (RVO2 then keeps the result it had).
 template <int NU>
 __device__ __forceinline__ bool lp3_sub(const float4 (&R)[NU], const float4 li, int i, float radius, int s, float &rx,
-                                        float &ry)
+                                        float &ry LP_COUNT_ARG)
 {
     float4 P[NU];
     uint32_t pv = 0;
@@ -252,6 +310,7 @@ __device__ __forceinline__ bool lp3_sub(const float4 (&R)[NU], const float4 li, 
             const float4 pk = qbc4(P[k >> 2], k);
             if (det2(pk.z, pk.w, pk.x - rx, pk.y - ry) > 0.0f) {
                 float tL, tR;
+                LP_COUNT(k);
                 if (!lp1_r<NU>(P, pv, k, pk, radius, s, tL, tR)) fail = true;
                 else if (ox * pk.z + oy * pk.w > 0.0f) { rx = pk.x + tR * pk.z; ry = pk.y + tR * pk.w; }
                 else { rx = pk.x + tL * pk.z; ry = pk.y + tL * pk.w; }
@@ -289,7 +348,7 @@ __device__ __forceinline__ void lp3_r(const float4 (&R)[NU], const float4 *Lb, i
 // bn[h] = fail | n << 8 (0: no linearProgram3); results to res / rok [h][12].
 template <int NU>
 __device__ __forceinline__ void lp3_tasks(const float4 *lines, int M, const float *vmax, const uint32_t *bn,
-                                          float2 *res, uint8_t *rok, int tid)
+                                          float2 *res, uint8_t *rok, int tid LP_COUNT_ARG)
 {
     const int q = tid >> 2, sq = tid & 3;
     const uint32_t b = bn[tid & 63];
@@ -318,7 +377,15 @@ __device__ __forceinline__ void lp3_tasks(const float4 *lines, int M, const floa
 #pragma unroll
         for (int u = 0; u < NU; ++u) R[u] = sq + 4 * u < i ? Lh[sq + 4 * u] : make_float4(0.f, 0.f, 0.f, 0.f);
         float qx, qy;
+#ifdef CN_STAMPS
+        LpCount l1 = {0, 0};   // per round: lc->bodies += its distinct indices | largest quad count << 12 | 1 << 24
+        const bool ok = lp3_sub<NU>(R, Lh[i], i, vmax[h], sq, qx, qy, &l1);
+        int uni = 0, mx = 0;
+        lp_count_wave(l1, uni, mx);
+        if (lc) lc->bodies += uni | mx << 12 | 1 << 24;
+#else
         const bool ok = lp3_sub<NU>(R, Lh[i], i, vmax[h], sq, qx, qy);
+#endif
         if (sq == 0) { res[h * 12 + i] = make_float2(qx, qy); rok[h * 12 + i] = ok ? 1 : 0; }
     }
 }

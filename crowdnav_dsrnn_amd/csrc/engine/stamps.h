@@ -35,10 +35,20 @@ __device__ unsigned long long cn_stamp_x[8192 * 4];
 #define STAMP_B(w, k) do { if ((threadIdx.x & 63) == 0 && (unsigned long long)(w) < 8192) cn_stamp_b[(w) * CN_NSTAMP + (k)] = clock64(); } while (0)
 // stamp k by thread t (a lane of another wave than thread 0's)
 #define STAMP_T(k, t) do { const unsigned sb_ = (unsigned)sb; if (threadIdx.x == (t) && sb_ < 4096 && CN_STAMP_ON) cn_stamp_a[sb_ * CN_NSTAMP + (k)] = clock64(); } while (0)
+// phase 2 of the quad path per WAVE (lane 0 of each of the workgroup's four waves), [workgroup][wave][CN_NWSTAMP]:
+// clocks at 0 lines + ranking done, 1 lp2_r done, 2 past the barrier before lp3_tasks, 3 lp3_tasks done,
+// 4 lp3_replay + human_post done; then the linearProgram1 bodies the wave's linear programs ran (LpCount, orca_lp.h):
+// 5 / 6 lp2_r's distinct line indices over the wave / largest count of one quad, 7 / 8 the same of lp3_tasks, summed
+// over its rounds, 9 those rounds. Read back with cn_debug_stamps_w() (tools/probe_stamps.py phase2)
+#define CN_NWSTAMP 16
+__device__ unsigned long long cn_stamp_w[4096 * 4 * CN_NWSTAMP];
+#define STAMP_WV(k, v) do { const unsigned sb_ = (unsigned)sb; if ((threadIdx.x & 63) == 0 && sb_ < 4096 && CN_STAMP_ON) cn_stamp_w[(sb_ * 4 + (threadIdx.x >> 6)) * CN_NWSTAMP + (k)] = (v); } while (0)
+#define STAMP_W(k) STAMP_WV(k, clock64())
 #else
 #define CN_LABEL_ROT 0
 #define CN_STAMP_ON true
 #define STAMP_T(k, t) do { } while (0)
+#define STAMP_W(k) do { } while (0)
 #define STAMP_A(k) do { } while (0)
 #define STAMP_B(w, k) do { } while (0)
 #define STAMP_R(k) do { } while (0)

@@ -3,6 +3,9 @@
     bash tools/build_stamps.sh      (python -m crowdnav_dsrnn_amd.build -DCN_STAMPS --out .../libcrowdnav_hip_stamps.so)
 
     CN_LIB_PATH=crowdnav_dsrnn_amd/lib/libcrowdnav_hip_stamps.so python tools/probe_stamps.py [variant]
+
+"xcd [rot [step]]" (run_xcd) and "phase2 <step> [walk]" (run_phase2: phase 2 per wave, with the linear programs'
+linearProgram1 body counts) read a -DCN_STAMP_STEP=<step> build through C2's multi-step launches.
 """
 import ctypes
 import os
@@ -415,7 +418,90 @@ def step_detail(A, B, E, epb, launch_over_wg):
     print("  launch / mean step workgroup %.3f" % launch_over_wg)
 
 
+def run_phase2(step, walk=False, launches=12, warm=130, chunk=32, E=4096, N=10):
+    """Phase 2 of one step of C2's multi-step launches per WAVE (a -DCN_STAMPS -DCN_STAMP_STEP=<step> build):
+    lines + ranking, lp2_r, the wait at the barrier before lp3_tasks, lp3_tasks, lp3_replay + human_post, and the
+    linearProgram1 bodies the wave ran in lp2_r and lp3_tasks beside what its busiest quad needed (stamps.h: STAMP_W).
+
+        CN_LIB_PATH=<stamps build> python tools/probe_stamps.py phase2 <step> [walk]
+
+    walk: the library's lp2_r is the walk, whose waves run one body per trip (the busiest quad's count), not one per
+    distinct line index of the wave."""
+    c = clone_config(Config())
+    c.humans.policy = "orca"
+    c.sim.human_num = N
+    c.sim.train_val_sim = c.sim.test_sim = ["circle_crossing"]
+    c.action_space.kinematics = "unicycle"
+    eng = CrowdNavEngine(make_cn_config(c, num_envs=E), "cuda:0")
+    eng.reset()
+    eng.set_seq_chunk(chunk)
+    L = _lib.lib()
+    L.cn_debug_stamps.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+    L.cn_debug_stamps_w.argtypes = [ctypes.c_void_p]
+    g = torch.Generator(device="cuda:0")
+    g.manual_seed(0)
+    acts = torch.rand((warm + chunk * launches, E, 2), generator=g, device="cuda:0") * 0.2 - 0.1
+    eng.step_seq(acts[:warm])
+    epb = min(64 // N, 16)
+    nstep = (E + epb - 1) // epb
+    nwave = (epb * N + 15) // 16          # waves that hold quads
+    a = np.zeros(4096 * 24, np.uint64)
+    b = np.zeros(8192 * 24, np.uint64)
+    w = np.zeros(4096 * 4 * 16, np.uint64)
+    As, Ws = [], []
+    for k in range(launches):
+        eng.step_seq(acts[warm + k * chunk:warm + (k + 1) * chunk])
+        L.cn_debug_stamps(a.ctypes.data_as(ctypes.c_void_p), b.ctypes.data_as(ctypes.c_void_p))
+        L.cn_debug_stamps_w(w.ctypes.data_as(ctypes.c_void_p))
+        As.append(a.reshape(-1, 24)[:nstep].astype(np.int64))
+        Ws.append(w.reshape(-1, 4, 16)[:nstep, :nwave].astype(np.int64))
+    A = np.concatenate(As)
+    W = np.concatenate(Ws)                 # [launch x workgroup][wave][16]
+    tot = A[:, 6] - A[:, 0]
+    p2 = A[:, 3] - A[:, 2]
+    print("[phase2] step %d of %d-step launches, %d launches after %d warm-up steps, %d workgroups x %d quad waves; lp2_r: %s"
+          % (step, chunk, launches, warm, nstep, nwave, "walk" if walk else "unrolled"))
+    print("  cycles per workgroup: step median %d max %d; phase 2 (barrier to barrier) median %d max %d (%.1f%% of the step)"
+          % (np.median(tot), tot.max(), np.median(p2), p2.max(), 100 * np.median(p2) / np.median(tot)))
+    t2 = A[:, 2][:, None]
+    spans = [("lines + ranking", W[:, :, 0] - t2), ("lp2_r", W[:, :, 1] - W[:, :, 0]),
+             ("wait at the barrier", W[:, :, 2] - W[:, :, 1]), ("lp3_tasks", W[:, :, 3] - W[:, :, 2]),
+             ("lp3_replay + human_post", W[:, :, 4] - W[:, :, 3])]
+    print("  span (cycles)              all waves: median   mean    max | slowest wave of the workgroup: median   mean | per wave medians")
+    for nm, v in spans:
+        print("    %-26s %8d %8d %8d | %8d %8d | %s" % (nm, np.median(v), v.mean(), v.max(), np.median(v.max(axis=1)),
+                                                        v.max(axis=1).mean(), " ".join("%d" % np.median(v[:, k]) for k in range(nwave))))
+    lp2 = W[:, :, 1] - W[:, :, 0]
+    uni, mx = W[:, :, 5], W[:, :, 6]
+    ran = mx if walk else uni
+    print("  lp2_r linearProgram1 bodies per wave: distinct indices of the wave mean %.2f, busiest quad mean %.2f (the wave "
+          "ran: %.2f)" % (uni.mean(), mx.mean(), ran.mean()))
+    # cycles per body: the slope of the span over the bodies the wave ran (least squares), and the plain ratio
+    x, y = ran.ravel().astype(float), lp2.ravel().astype(float)
+    slope, icpt = np.polyfit(x, y, 1)
+    print("    lp2_r span vs bodies run: %.0f cycles per body + %.0f (least squares); mean span / mean bodies %.0f"
+          % (slope, icpt, y.mean() / max(x.mean(), 1e-9)))
+    if not walk:
+        rem = (uni - mx).mean()
+        print("    a walk removes %.2f bodies per wave (%.0f%%): predicted %.0f cycles per wave, %.2f%% of the step's median"
+              % (rem, 100 * rem / max(uni.mean(), 1e-9), rem * slope, 100 * rem * slope / np.median(tot)))
+    u3, m3, r3 = W[:, :, 7], W[:, :, 8], W[:, :, 9]
+    l3 = W[:, :, 3] - W[:, :, 2]
+    has = r3 > 0
+    print("  lp3_tasks: waves with a sub-problem %.3f; rounds mean %.2f; bodies per wave: distinct indices %.2f, busiest quad "
+          "%.2f (over all waves)" % (has.mean(), r3.mean(), u3.mean(), m3.mean()))
+    if has.any():
+        s3, i3 = np.polyfit(u3.ravel().astype(float), l3.ravel().astype(float), 1)
+        rem3 = (u3 - m3).mean()
+        print("    span vs bodies run: %.0f cycles per body + %.0f; a walk removes %.2f bodies per wave: predicted %.0f cycles "
+              "per wave, %.2f%% of the step's median" % (s3, i3, rem3, rem3 * s3, 100 * rem3 * s3 / np.median(tot)))
+    eng.close()
+
+
 if __name__ == "__main__":
+    if sys.argv[1:2] == ["phase2"]:
+        run_phase2(int(sys.argv[2]), walk=sys.argv[3:4] == ["walk"])
+        sys.exit(0)
     if sys.argv[1:2] == ["xcd"]:
         run_xcd(int(sys.argv[2]) if len(sys.argv) > 2 else 0, int(sys.argv[3]) if len(sys.argv) > 3 else None)
         sys.exit(0)
